@@ -8,8 +8,11 @@ fp32 master, 256x2048 images, T=512, V=6997, dropout ON, teacher-forcing noise O
 is kept under profiles/): c1 tiny (d=128, L=2, 128x1024, T=128, fp32), c3 audio-only 195x512 log-STFT, c3mel audio-only
 80x1024 mel, c4 multimodal (image 256x2048 + audio 195x512, `concat` mixer, per-GPU batch 8 = global 64 on 8 GPUs).
 
-Rank 0 prints ONE JSON line with the driver's contract plus `roofline` (dominant kernel, live HIP-event timing against the
-MI355X peak) and `cpu_baseline` (the CPU oracle timed on this node's host cores on a bounded sample).
+Rank 0 prints ONE JSON line with the driver's contract.  A plain run does only what that line needs: set up, warm up, time the
+steps.  `--full` adds `roofline` (dominant kernel and the other large ones, live HIP-event timing against the MI355X peak),
+`decode` (greedy decode rates) and `cpu_baseline` (the CPU oracle timed on this node's host cores on a bounded sample); each
+takes runs of its own after the timed steps.  Every warm-up and timed step starts from the same initial parameters and Adam
+state (see main), so `--dump-outputs DIR` writes what the last timed step computed the same way in every run (see dump_outputs).
 """
 import argparse
 import json
@@ -62,8 +65,12 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override (weak scaling)")
     ap.add_argument("--layers", type=int, default=0)
     ap.add_argument("--dtype", default="", choices=["", "bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure roofline, decode rates and the CPU baseline (each run of its own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out roofline and decode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's loss, updated parameters and gradients to DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-side-stream", action="store_true",
                     help="profiling aid: weight gradients on the main stream (kernel durations in a trace are then not stretched by overlap)")
     ap.add_argument("--dry-launch", action="store_true",
@@ -134,7 +141,19 @@ def main():
     reducer = model.attach_reducer() if world > 1 else None
     opt = model.configure_optimizers()
 
+    # Every step starts from the initial parameters and Adam state.  The weight-gradient sums use fp32 atomics whose order
+    # varies from run to run; over successive Adam steps those last-bit differences grow into different encoder gradients.
+    # Restarting each step keeps its work unchanged (plus about 0.2 GB of device copies and fills) and makes what the last step
+    # computes the same from run to run to rounding, so that two builds can be compared output for output.
+    flat = opt.flat
+    master0, adam_steps0 = flat.master.clone(), dict(opt.steps)
+
     def step(i):
+        flat.master.copy_(master0)
+        flat.exp_avg.zero_()
+        flat.exp_avg_sq.zero_()
+        flat.sync_lowp()
+        opt.steps = dict(adam_steps0)
         opt.zero_grad()
         loss = model.training_step(batch, i)
         loss.backward()
@@ -164,6 +183,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.detach())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, model)
 
     fwd_flops, S = fwd_flops_per_sample(c, V)
     step_flops = 3.0 * fwd_flops
@@ -184,18 +205,41 @@ def main():
         "mfma_frac_whole_step": round(step_flops * samples_per_s / world / 1e12 / peak_tf, 4),
     }
 
-    if rank == 0 and not args.no_roofline and args.config == "c2":
+    roofline = args.full and not args.no_roofline
+    if rank == 0 and roofline and args.config == "c2":
         out["roofline"] = roofline_dominant_kernel(B, c["img"][0], c["img"][1], c["dtype"])
         out["roofline"]["others"] = roofline_others(B, c["img"][0], c["img"][1], T, c["d"], 4)
-    if rank == 0 and not args.no_roofline and x1 is not None:
+    if rank == 0 and roofline and x1 is not None:
         out["decode"] = decode_rate(model, x1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(c, V)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 1 << 22       # per array: 16 MiB of float32, so the three files stay far below 64 MB
+
+
+def dump_outputs(path, loss, model):
+    """What a caller of the timed step receives, as float32/float64 .npy files: loss.npy (the last step's loss), params.npy (every
+    parameter after that step's Adam update) and grads.npy (that step's gradients).  Parameters and gradients are flattened in
+    logical layout, state-dict order, so the files do not depend on how the flat buffers are laid out; above DUMP_MAX_ELEMS
+    elements both keep the same fixed, seeded sample of positions (it depends on the element count alone)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    ps = [p for _, p in model.named_parameters()]
+    params = torch.cat([p.detach().reshape(-1).float() for p in ps])
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in ps])
+    if params.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randperm(params.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+        idx = idx.to(params.device)
+        params, grads = params[idx], grads[idx]
+    np.save(os.path.join(path, "loss.npy"), np.array([float(loss.detach())], dtype=np.float64))
+    np.save(os.path.join(path, "params.npy"), params.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "grads.npy"), grads.cpu().numpy().astype(np.float32))
 
 
 def free_port():

@@ -12,7 +12,7 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/dom_fetch -- python3 tools/
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/dom_write -- python3 tools/run_dominant_kernel.py > /dev/null 2>&1 || exit 1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_BF16 SQ_ACTIVE_INST_LDS --output-format csv -d $O/attn_pmc -- python3 tools/attn_shapes.py > $O/attn_pmc.log 2>&1 || exit 1
 python tools/attn_pmc.py $O/attn_pmc $O/attention_pmc_SQ.json > $O/attention_pmc_summary.txt
-for c in c1 c3 c3mel c4; do python bench.py --config $c --no-cpu-baseline > $O/bench_$c.json 2> /dev/null || exit 1; done
-python bench.py > $O/bench_c2.json 2> $O/bench_c2.err || exit 1
+for c in c1 c3 c3mel c4; do python bench.py --full --config $c --no-cpu-baseline > $O/bench_$c.json 2> /dev/null || exit 1; done
+python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || exit 1
 python tools/host_overhead.py > $O/host.txt 2>&1
 echo done
