@@ -84,6 +84,10 @@ int omr_image_vpass_to_float(const unsigned char* src, int h, int w, const int* 
 int omr_teacher_forcing_noise(long* tokens, long count, double prob, long pad_idx, long vocab, unsigned int* mt_state, int* mt_index);
 int omr_sw_align(const int* ref, int nr, const int* query, int nq, int match, int mismatch, int gap_penalty,
                  int gap_extension_penalty, char* ops, int* r_pos, int* q_pos, int* score);
+/* Sym-ER / Seq-ER edit distances (src/utils/metrics.py:59-88, levenshtein over token lists): unit-cost Levenshtein distance
+ * of n pairs of int32 id sequences.  Pair i is a[a_off[i] .. a_off[i+1]) against b[b_off[i] .. b_off[i+1]) (offsets: n + 1
+ * entries, non-decreasing); dist[i] receives its distance.  HOST function (no GPU work), two-row dynamic programme. */
+int omr_edit_distance_batch(const int* a, const long* a_off, const int* b, const long* b_off, long n, long* dist);
 /* beam-search expansion (BASELINE config C5; an extension: the reference decodes greedily): per row the k largest
  * log_softmax values and their token ids, same tie rule as omr_argmax, idx_out / val_out [rows][k] */
 int omr_topk_logprob(const float* x, int rows, int n, long ld, int k, long* idx_out, float* val_out, void* stream);
@@ -255,6 +259,15 @@ int omr_attn_fwd_split(int dtype, const void* q, const void* k, const void* v, v
 int omr_attn_fwd_split_partials(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
                                 long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim, float* split_ws,
                                 long split_ws_floats, int* nsplit, void* stream);
+/* omr_attn_fwd_split over a ragged batch (the cross-attention of batched greedy decoding over memories of different lengths;
+ * the reference decodes one memory at a time, src/transformer/model.py:171-199): S is the padded key count and batch row b
+ * attends over keys [0, kv_len[b]) (device int32 [B], 1 <= kv_len[b] <= S; NULL = every row sees S).  The key split is the
+ * plan of S; a split past a row's end contributes nothing.  Rows with kv_len[b] > 64 are bit-equal to omr_attn_fwd_split of
+ * that row alone with S = kv_len[b].  S <= 64 with a non-NULL kv_len returns OMR_ERR_UNSUPPORTED (that shape does not take
+ * the key-split kernel, which alone reads kv_len). */
+int omr_attn_fwd_split_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                              long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                              const float* key_bias, const int* kv_len, float* split_ws, long split_ws_floats, void* stream);
 /* Test / debug entry: the attention-probability dropout keep-mask (1 = kept) for (seed, dropout_p) -- the function
  * omr_attn_dropout_words packs -- one byte per score, mask[B][H][T][S].  Lets a checker inject the very same mask into a CPU
  * restatement of nn.MultiheadAttention's dropout (tests/test_dropout_parity_gpu.py). */
@@ -324,6 +337,12 @@ typedef struct omr_decode_linear_args {
 int omr_decode_linear(const omr_decode_linear_args* args, void* stream);
 int omr_decode_steps(const omr_decode_desc* desc, long* tokens, int t0, int n_steps, long* out_tokens, float* out_top1, float* last_logits,
                      void* stream);
+/* omr_decode_steps over memories of different lengths in one batch (validation at batch size > 1; the reference's greedy loop,
+ * src/transformer/model.py:171-199, runs one memory at a time): desc->S is the padded memory length (cross_kv rows past a
+ * row's own length are never read) and row b's cross-attention sees mem_len[b] keys (device int32 [B], 1 <= mem_len[b] <=
+ * S).  A row with mem_len[b] > 64 gets, token for token, what omr_decode_steps gives for that memory alone. */
+int omr_decode_steps_varlen(const omr_decode_desc* desc, const int* mem_len, long* tokens, int t0, int n_steps, long* out_tokens,
+                            float* out_top1, float* last_logits, void* stream);
 /* Weighted late fusion (src/multimodal/weighted_multimodal/test.py:21-70) without a host round trip per token: positions
  * t0 .. t0+n_steps-1 of TWO models (descriptors with B = 1 and the same vocabulary) in lock-step; per position
  * argmax(alpha * softmax(logits_a) + (1 - alpha) * softmax(logits_b)) (omr_weighted_argmax) is written to out_tokens[s]

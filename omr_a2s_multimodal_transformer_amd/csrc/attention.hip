@@ -123,8 +123,8 @@ template <typename T, int HD, int NR> struct RowTile {
 // Visibility (length limits, causal / window band, CrossAttention's block mask) as a per-lane RANGE, computed once per kernel:
 // the keys a query row sees are [lo, lo + span) (lane = query: forward, dQ); the queries that see a key are such a range too
 // (lane = key: dK/dV).  A boundary tile then tests  (unsigned)(index - lo) < span  per score: no branches.
-__device__ __forceinline__ void visible_keys(const AttnArgs& a, int q, int lq, int lkv, int& lo, unsigned& span) {
-    int hi = q < a.T ? a.S : 0;
+__device__ __forceinline__ void visible_keys(const AttnArgs& a, int q, int S, int lq, int lkv, int& lo, unsigned& span) {
+    int hi = q < a.T ? S : 0;
     lo = 0;
     if (a.causal) {
         hi = min(hi, q + 1);
@@ -233,8 +233,11 @@ __device__ __forceinline__ long drop_word_base(const AttnArgs& a, int bh, int qb
 // SPLITW (T <= 32: KV-cached greedy decode, one query row): the four waves would own the same 32 rows, so they split the KEYS
 // instead -- 256 keys are staged per step, wave w takes keys [64w, 64w+64) of them -- and their (max, sum, O) partials are
 // merged through LDS at the end.  Same arithmetic per score, a quarter of the serial tile walk.
+// kv_len (SPLITW only, nullable): batch row b attends over keys [0, kv_len[b]) of its padded S (a ragged batch of decode
+// memories).  Every key bound below is that row's; a key split or wave past it walks nothing and leaves (O 0, max -inf,
+// sum 0), which both mergers weigh with 0.  The tile loads clamp to the row's last key, so nothing past it is ever read.
 template <typename T, int HD, bool SPLITW, bool DROP>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint64_t* __restrict__ dmask) {
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint64_t* __restrict__ dmask, const int* __restrict__ kv_len) {
     typedef typename Frag<T>::type F;
     constexpr int VEC = ACfg<T>::VEC, NFR = ACfg<T>::NFR, KS = KStep<T>::value;
     constexpr int NKS = HD / KS, NDB = HD / 32, BKV = 64;
@@ -263,6 +266,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint
     const T* Q = (const T*)a.q + (long)b * a.bsq + h * HD;
     const T* K = (const T*)a.k + (long)b * a.bsk + h * HD;
     const T* V = (const T*)a.v + (long)b * a.bsv + h * HD;
+    int S = a.S;                                                // this row's key count (never past the padded S; <= 0: no keys)
+    if constexpr (SPLITW) { if (kv_len) S = min(kv_len[b], a.S); }
 
     const float sc2 = a.scale * LOG2E;
     F qf[NKS];                                                  // Q * scale * log2 e
@@ -275,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint
     int lq = -1, lkv = 0;
     if (a.blk_lq) { const int bb = (b * a.H + h) % a.B; lq = a.blk_lq[bb]; lkv = a.blk_lkv[bb]; }
     int vis_lo; unsigned vis_span;
-    visible_keys(a, q, lq, lkv, vis_lo, vis_span);
+    visible_keys(a, q, S, lq, lkv, vis_lo, vis_span);
 
     f32x16 acc_o[NDB];
 #pragma unroll
@@ -289,18 +294,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint
     F qa = hh ? frag_zero<T>() : Aug<T>::y(0.f);
     const bool win_on = a.window > 0 && a.window < a.T;
 
-    int kv_beg = 0, kv_end = a.S;
+    int kv_beg = 0, kv_end = S;
     if (a.causal) {
-        kv_end = min(a.S, q0 + 128);
+        kv_end = min(S, q0 + 128);
         if (a.window > 0 && a.window < a.T) kv_beg = max(0, q0 - a.window) / BKV * BKV;
     }
     if (a.nsplit > 1) { kv_beg = max(kv_beg, ksplit * a.split_len); kv_end = min(kv_end, (ksplit + 1) * a.split_len); }
     RowTile<T, HD, BST> kt, vt;
     float bias_r = 0.f;
     auto prefetch = [&](int kvb) {
-        kt.load(K, a.ldk, kvb, a.S, tid);
-        vt.load(V, a.ldv, kvb, a.S, tid);
-        if (tid < BST) bias_r = a.key_bias ? a.key_bias[(long)b * a.S + min(kvb + tid, a.S - 1)] * LOG2E : 0.f;     // keys >= S: masked
+        kt.load(K, a.ldk, kvb, S, tid);
+        vt.load(V, a.ldv, kvb, S, tid);
+        if (tid < BST) bias_r = a.key_bias ? a.key_bias[(long)b * a.S + min(kvb + tid, S - 1)] * LOG2E : 0.f;     // keys >= S: masked
     };
     if (tid < NBUF) Ka_[tid][BST] = frag_zero<T>();
     auto commit = [&](int buf) {
@@ -371,7 +376,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint
             __builtin_amdgcn_sched_barrier(0);
         }
         // Tiles that are entirely visible for this wave's 32 query rows (the common case) skip every per-element mask test.
-        const bool full = (kv0 + BKV <= a.S) && (qw0 + 32 <= a.T) && lq < 0 &&
+        const bool full = (kv0 + BKV <= S) && (qw0 + 32 <= a.T) && lq < 0 &&
                           (!a.causal || (kv0 + BKV - 1 <= qw0 && (!win_on || kv0 >= qw0 + 31 - a.window)));
         if (!full) {
             const int rel = kv0 + 4 * hh - vis_lo;
@@ -576,7 +581,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a, const u
     int lq = -1, lkv = 0;
     if (a.blk_lq) { const int bb = (b * a.H + h) % a.B; lq = a.blk_lq[bb]; lkv = a.blk_lkv[bb]; }
     int vis_lo; unsigned vis_span;
-    visible_keys(a, q, lq, lkv, vis_lo, vis_span);
+    visible_keys(a, q, a.S, lq, lkv, vis_lo, vis_span);
     const F qa = hh ? frag_zero<T>() : Aug<T>::y(-lse2);        // query side of the score chain: minus the row's log-sum-exp
     const F da = hh ? frag_zero<T>() : Aug<T>::y(ndc);          // dO side of the dP chain: minus delta / c
     const F va = hh ? frag_zero<T>() : Aug<T>::x(0.f);          // V side of the dP chain: the unit slots
@@ -1040,19 +1045,20 @@ __global__ __launch_bounds__(256) void attn_dropout_words_kernel(uint64_t* __res
     if (lane < 32) out[drop_word_base(a, bh, qb32, kt) + lane] = mine;
 }
 
-template <typename T, int HD> int run_fwd(const AttnArgs& a, hipStream_t s, bool merge = true) {
+template <typename T, int HD> int run_fwd(const AttnArgs& a, hipStream_t s, bool merge = true, const int* kv_len = nullptr) {
     // a single 32-row query block (KV-cached decode): split the keys over the waves (and, with a workspace, over workgroups).
     // Inference only: a training forward with dropout and T <= 32 takes the query-per-wave kernel below.
     if (a.T <= 32 && a.S > 64 && !a.drop_thresh) {
         const dim3 g(a.nsplit > 1 ? a.nsplit : 1, a.H, a.B);
-        hipLaunchKernelGGL((attn_fwd_kernel<T, HD, true, false>), g, dim3(256), 0, s, a, a.dmask);
+        hipLaunchKernelGGL((attn_fwd_kernel<T, HD, true, false>), g, dim3(256), 0, s, a, a.dmask, kv_len);
         if (a.nsplit > 1 && merge) hipLaunchKernelGGL((attn_split_merge_kernel<T, HD>), dim3(a.B * a.H * a.T), dim3(64), 0, s, a);
         OMR_CHECK_LAUNCH();
         return OMR_OK;
     }
     dim3 grid(cdiv(a.T, 128) * (a.nsplit > 1 ? a.nsplit : 1), a.H, a.B);
-    if (a.drop_thresh) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, false, true>), grid, dim3(256), 0, s, a, a.dmask);
-    else hipLaunchKernelGGL((attn_fwd_kernel<T, HD, false, false>), grid, dim3(256), 0, s, a, a.dmask);
+    if (kv_len) return OMR_ERR_UNSUPPORTED;                    // per-row key counts: the key-split kernel above only
+    if (a.drop_thresh) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, false, true>), grid, dim3(256), 0, s, a, a.dmask, (const int*)nullptr);
+    else hipLaunchKernelGGL((attn_fwd_kernel<T, HD, false, false>), grid, dim3(256), 0, s, a, a.dmask, (const int*)nullptr);
     if (a.nsplit > 1) hipLaunchKernelGGL((attn_split_merge_kernel<T, HD>), dim3(a.B * a.H * a.T), dim3(64), 0, s, a);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
@@ -1155,7 +1161,8 @@ extern "C" long omr_attn_workspace_floats(int B, int H, int T, int S, int head_d
 static int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv, long ldo,
                          long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim, int causal, int window,
                          const float* key_bias, const int* blk_lq, const int* blk_lkv, float dropout_p, unsigned long long seed,
-                         const unsigned long long* drop_words, float* split_ws, long split_ws_floats, void* stream, int* nsplit_out = nullptr);
+                         const unsigned long long* drop_words, float* split_ws, long split_ws_floats, void* stream, int* nsplit_out = nullptr,
+                         const int* kv_len = nullptr);
 
 /* omr_attn_fwd with caller-provided scratch for the key split (omr_attn_workspace_floats(..., backward = 0) floats) */
 extern "C" int omr_attn_fwd_ws(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv, long ldo,
@@ -1194,7 +1201,8 @@ extern "C" int omr_attn_fwd_split(int dtype, const void* q, const void* k, const
 static int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv, long ldo,
                          long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim, int causal, int window,
                          const float* key_bias, const int* blk_lq, const int* blk_lkv, float dropout_p, unsigned long long seed,
-                         const unsigned long long* drop_words, float* split_ws, long split_ws_floats, void* stream, int* nsplit_out) {
+                         const unsigned long long* drop_words, float* split_ws, long split_ws_floats, void* stream, int* nsplit_out,
+                         const int* kv_len) {
     AttnArgs a = {};
     int rc = fill_common(a, B, H, T, S, head_dim, dropout_p, seed, causal, window, key_bias, blk_lq, blk_lkv, drop_words, true);
     if (rc) return rc;
@@ -1211,12 +1219,14 @@ static int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v,
             a.nsplit = nsplit; a.split_len = len; a.part = split_ws;
         }
     }
+    // per-row key counts exist only in the key-split decode kernel: a shape that would not take it is refused, not run unmasked
+    if (kv_len && !(T <= 32 && S > 64 && a.drop_thresh == 0 && !causal && !blk_lq)) return OMR_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const bool merge = nsplit_out == nullptr;           // a caller that asks for the split count merges the partials itself
     if (nsplit_out) *nsplit_out = (T <= 32 && S > 64) ? a.nsplit : 1;
     if (!merge && !(T <= 32 && S > 64)) { a.nsplit = 1; a.split_len = 0; a.part = nullptr; }
-    if (dtype == OMR_BF16) return head_dim == 64 ? run_fwd<bf16, 64>(a, s, merge) : run_fwd<bf16, 32>(a, s, merge);
-    if (dtype == OMR_F32) return head_dim == 64 ? run_fwd<float, 64>(a, s, merge) : run_fwd<float, 32>(a, s, merge);
+    if (dtype == OMR_BF16) return head_dim == 64 ? run_fwd<bf16, 64>(a, s, merge, kv_len) : run_fwd<bf16, 32>(a, s, merge, kv_len);
+    if (dtype == OMR_F32) return head_dim == 64 ? run_fwd<float, 64>(a, s, merge, kv_len) : run_fwd<float, 32>(a, s, merge, kv_len);
     return OMR_ERR_UNSUPPORTED;
 }
 
@@ -1229,6 +1239,25 @@ extern "C" int omr_attn_fwd_split_partials(int dtype, const void* q, const void*
     if (T > 32 || !nsplit) return OMR_ERR_ARG;
     return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, nullptr, nullptr, nullptr, 0.f, 0,
                          nullptr, split_ws, split_ws_floats, stream, nsplit);
+}
+
+/* omr_attn_fwd_split over a ragged batch: S is the padded key count, row b attends over keys [0, kv_len[b]) (device int32 [B],
+ * 1 <= kv_len[b] <= S; NULL = every row sees S).  The split plan stays that of S. */
+extern "C" int omr_attn_fwd_split_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                                         long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                                         const float* key_bias, const int* kv_len, float* split_ws, long split_ws_floats, void* stream) {
+    if (T > 32) return OMR_ERR_ARG;
+    return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, key_bias, nullptr, nullptr, 0.f, 0,
+                         nullptr, split_ws, split_ws_floats, stream, nullptr, kv_len);
+}
+
+/* omr_attn_fwd_split_partials with per-row key counts, for the ragged decode executor (decode.hip).  A C++ symbol, not part of the C ABI */
+int attn_fwd_split_partials_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                                   long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                                   const int* kv_len, float* split_ws, long split_ws_floats, int* nsplit, void* stream) {
+    if (T > 32 || !nsplit) return OMR_ERR_ARG;
+    return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, nullptr, nullptr, nullptr, 0.f, 0,
+                         nullptr, split_ws, split_ws_floats, stream, nsplit, kv_len);
 }
 
 extern "C" int omr_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,

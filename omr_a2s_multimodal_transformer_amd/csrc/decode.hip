@@ -293,8 +293,9 @@ extern "C" long omr_decode_workspace_bytes(const omr_decode_desc* d) {
     return (long)carve(*d, nullptr, nullptr);
 }
 
-extern "C" int omr_decode_steps(const omr_decode_desc* dp, long* tokens, int t0, int n_steps, long* out_tokens, float* out_top1,
-                                float* last_logits, void* stream) {
+// mem_len (nullable, device int32 [B]): row b's cross-attention sees the first mem_len[b] of the d.S memory rows (ragged batch)
+static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tokens, int t0, int n_steps, long* out_tokens, float* out_top1,
+                        float* last_logits, void* stream) {
     if (!dp || !tokens || n_steps < 1 || t0 < 0) return OMR_ERR_ARG;
     const omr_decode_desc& d = *dp;
     if (d.B <= 0 || d.L <= 0 || d.d <= 0 || d.d % d.nhead || d.V <= 0 || d.ldv < d.V || d.ldv % 8) return OMR_ERR_ARG;
@@ -364,8 +365,8 @@ extern "C" int omr_decode_steps(const omr_decode_desc* dp, long* tokens, int t0,
                 TRY(lin(1, w.proj, xa, (const float*)Wl[4], (const float*)Wl[5], xb, nullptr, 0, Wl[6], (const float*)Wl[7], dm, dm, 0, w.q, dm, dm, nullptr, 0, nullptr, nullptr, nullptr, W8l ? W8l[2] : nullptr, S8l ? S8l[2] : nullptr));
                 { char* tsw = xa; xa = xb; xb = tsw; }
                 const char* ck = (const char*)d.cross_kv + (size_t)l * 2 * dm * es;
-                TRY(omr_attn_fwd_split_partials(dt, w.q, ck, ck + (size_t)dm * es, w.o, w.lse, dm, d.cross_ld, d.cross_ld, dm, dm, d.cross_bs, d.cross_bs, dm,
-                                                B, d.nhead, 1, d.S, hd, w.split, w.split_floats, &ns, stream));
+                TRY(attn_fwd_split_partials_varlen(dt, w.q, ck, ck + (size_t)dm * es, w.o, w.lse, dm, d.cross_ld, d.cross_ld, dm, dm, d.cross_bs, d.cross_bs,
+                                                   dm, B, d.nhead, 1, d.S, hd, mem_len, w.split, w.split_floats, &ns, stream));
                 TRY(lin(ns > 1 ? 3 : 0, w.o, nullptr, nullptr, nullptr, nullptr, w.split, ns, Wl[8], (const float*)Wl[9], dm, dm, 0, w.proj, dm, dm, nullptr, 0, nullptr, nullptr, nullptr, W8l ? W8l[3] : nullptr, S8l ? S8l[3] : nullptr));
                 // feed-forward from norm2(x + cross-attention)
                 TRY(lin(1, w.proj, xa, (const float*)Wl[10], (const float*)Wl[11], xb, nullptr, 0, Wl[12], (const float*)Wl[13], d.ff, dm, 1, w.h, d.ff, d.ff, nullptr, 0, nullptr, nullptr, nullptr, W8l ? W8l[4] : nullptr, S8l ? S8l[4] : nullptr));
@@ -409,8 +410,8 @@ extern "C" int omr_decode_steps(const omr_decode_desc* dp, long* tokens, int t0,
             // cross-attention over the memory K|V projected once (init): layer l's block of the [B][S][L*2d] buffer
             TRY(gemm(w.x, dm, 6, (const float*)W[7], w.q, dm, dm, dm, 0, 2, 0));
             const char* ck = (const char*)d.cross_kv + (size_t)l * 2 * dm * es;
-            TRY(omr_attn_fwd_split(dt, w.q, ck, ck + (size_t)dm * es, w.o, w.lse, dm, d.cross_ld, d.cross_ld, dm, dm, d.cross_bs, d.cross_bs, dm,
-                                   B, d.nhead, 1, d.S, hd, nullptr, w.split, w.split_floats, stream));
+            TRY(omr_attn_fwd_split_varlen(dt, w.q, ck, ck + (size_t)dm * es, w.o, w.lse, dm, d.cross_ld, d.cross_ld, dm, dm, d.cross_bs, d.cross_bs, dm,
+                                          B, d.nhead, 1, d.S, hd, nullptr, mem_len, w.split, w.split_floats, stream));
             TRY(gemm(w.o, dm, 8, (const float*)W[9], w.proj, dm, dm, dm, 0, 3, 0));
             TRY(omr_add_layernorm_fwd(dt, w.proj, w.x, (const float*)W[10], (const float*)W[11], w.x, w.mean, w.rstd, B, dm, 1e-5f, 0.f, 0, stream));
             // feed-forward
@@ -440,6 +441,18 @@ extern "C" int omr_decode_steps(const omr_decode_desc* dp, long* tokens, int t0,
         }
     }
     return OMR_OK;
+}
+
+extern "C" int omr_decode_steps(const omr_decode_desc* dp, long* tokens, int t0, int n_steps, long* out_tokens, float* out_top1,
+                                float* last_logits, void* stream) {
+    return decode_steps(dp, nullptr, tokens, t0, n_steps, out_tokens, out_top1, last_logits, stream);
+}
+
+/* omr_decode_steps over a ragged batch of memories: desc->S is the padded memory length, row b attends over mem_len[b] of it */
+extern "C" int omr_decode_steps_varlen(const omr_decode_desc* dp, const int* mem_len, long* tokens, int t0, int n_steps, long* out_tokens,
+                                       float* out_top1, float* last_logits, void* stream) {
+    if (!mem_len) return OMR_ERR_ARG;
+    return decode_steps(dp, mem_len, tokens, t0, n_steps, out_tokens, out_top1, last_logits, stream);
 }
 
 /* Weighted late fusion (src/multimodal/weighted_multimodal/test.py:21-70) as ONE host call per run of tokens: two unimodal

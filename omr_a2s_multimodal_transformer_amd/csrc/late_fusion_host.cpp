@@ -1,4 +1,5 @@
-// Host side of the late (prediction-level) fusion: Smith-Waterman local alignment of two token-id sequences.
+// Host-side sequence dynamic programmes: Smith-Waterman local alignment of two token-id sequences (late fusion) and the
+// batched edit distance of the evaluation metrics.
 // Reference: src/multimodal/smith_waterman/test.py:136-150 calls swalign.LocalAlignment(NucleotideScoringMatrix(match,
 // mismatch), gap_penalty).align(ref, query).  swalign (0.3.x) is a third-party package that is absent from the reference
 // tree and from this image: this file restates its published dynamic programme -- cell = max(diag + score, up + gap,
@@ -62,4 +63,33 @@ extern "C" int omr_sw_align(const int* ref, int nr, const int* query, int nq, in
     *r_pos = col; *q_pos = row;
     if (score) *score = max_val;
     return n;                      // number of alignment columns (<= nr + nq); ops[i] in {'m', 'i', 'd'}
+}
+
+// Edit distance of the Sym-ER / Seq-ER metrics (metrics.edit_distance restated): unit-cost Levenshtein, two rows over the
+// shorter sequence of each pair.
+extern "C" int omr_edit_distance_batch(const int* a, const long* a_off, const int* b, const long* b_off, long n, long* dist) {
+    if (n < 0 || (n > 0 && (!a_off || !b_off || !dist))) return OMR_ERR_ARG;
+    std::vector<long> prev, cur;
+    for (long i = 0; i < n; ++i) {
+        const long la = a_off[i + 1] - a_off[i], lb = b_off[i + 1] - b_off[i];
+        if (la < 0 || lb < 0 || (la && !a) || (lb && !b)) return OMR_ERR_ARG;
+        const int* s = a + a_off[i]; const int* t = b + b_off[i];
+        long ns = la, nt = lb;
+        if (ns > nt) { const int* x = s; s = t; t = x; const long y = ns; ns = nt; nt = y; }
+        prev.resize(ns + 1); cur.resize(ns + 1);
+        for (long j = 0; j <= ns; ++j) prev[j] = j;
+        for (long r = 1; r <= nt; ++r) {
+            cur[0] = r;
+            const int tr = t[r - 1];
+            for (long j = 1; j <= ns; ++j) {
+                long c = prev[j - 1] + (s[j - 1] != tr);
+                if (prev[j] + 1 < c) c = prev[j] + 1;
+                if (cur[j - 1] + 1 < c) c = cur[j - 1] + 1;
+                cur[j] = c;
+            }
+            prev.swap(cur);
+        }
+        dist[i] = prev[ns];
+    }
+    return 0;
 }

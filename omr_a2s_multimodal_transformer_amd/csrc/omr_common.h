@@ -133,3 +133,8 @@ __device__ __forceinline__ bool drop_keep(uint64_t seed, uint64_t idx, uint32_t 
 }
 
 __host__ __device__ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// attention.hip -> decode.hip: omr_attn_fwd_split_partials with per-row key counts kv_len[B] (omr_attn_fwd_split_varlen's rule)
+int attn_fwd_split_partials_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                                   long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                                   const int* kv_len, float* split_ws, long split_ws_floats, int* nsplit, void* stream);

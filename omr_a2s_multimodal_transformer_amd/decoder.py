@@ -265,12 +265,20 @@ class Decoder(nn.Module):
     #      its self-attention K|V to the cache, reads the cross-attention K|V projected once, and chains the chosen token to
     #      the next position through device memory.  Same kernels, same per-row arithmetic order as the training forward.
     @torch.no_grad()
-    def init_decode(self, memory: torch.Tensor) -> "DecodeState":
+    def init_decode(self, memory) -> "DecodeState":
+        """memory [B, S, d] -> the decode state of B same-sized inputs.  A LIST of memories ([1, S_b, d] or [S_b, d] each) gives
+        one ragged state: padded to S = max S_b, row b's cross-attention sees its own S_b keys (omr_decode_steps_varlen)."""
         emb_w = self.embedding.weight
         dt = torch.bfloat16 if getattr(emb_w, "omr_lowp", None) is not None else torch.float32
-        if memory.dtype != dt:
-            memory = K.cast(memory.contiguous(), dt)
-        return DecodeState(self, memory.contiguous(), dt)
+
+        def as_dt(m):
+            return K.cast(m.contiguous(), dt) if m.dtype != dt else m.contiguous()
+
+        if isinstance(memory, (list, tuple)):
+            mems = [m[0] if m.dim() == 3 else m for m in memory]
+            check_ragged_memories([m.shape for m in mems], self.embedding.weight.shape[1])
+            return DecodeState(self, [as_dt(m) for m in mems], dt)
+        return DecodeState(self, as_dt(memory), dt)
 
     @torch.no_grad()
     def decode_step(self, token: torch.Tensor, st: "DecodeState") -> torch.Tensor:
@@ -320,6 +328,27 @@ class Decoder(nn.Module):
         return logits.permute(0, 2, 1)  # [B, V, T] (decoder.py:145-146)
 
 
+# A ragged decode state (memories of different lengths in one batch) keeps every row bit-equal to its batch-size-1 decode
+# only in the key-split cross-attention kernel with 256-key splits: at most 64 splits (decode.hip MAXSPLIT), and more than
+# 64 keys per row (a shorter memory alone takes the query-per-wave kernel).  Python routes the short rows to batch size 1.
+MAX_RAGGED_MEMORY = 64 * 256
+MIN_RAGGED_MEMORY = 64
+
+
+def check_ragged_memories(shapes, d: int) -> None:
+    """Refuse, before anything is launched, memories a ragged decode state cannot take."""
+    if not shapes:
+        raise ValueError("ragged decode: no memories given")
+    for i, shp in enumerate(shapes):
+        if len(shp) != 2 or shp[1] != d:
+            raise ValueError(f"ragged decode: memory {i} has shape {tuple(shp)}, expected [S, {d}] or [1, S, {d}]")
+        if shp[0] < 1:
+            raise ValueError(f"ragged decode: memory {i} is empty (0 rows)")
+        if shp[0] > MAX_RAGGED_MEMORY:
+            raise ValueError(f"ragged decode: memory {i} has {shp[0]} rows, more than the {MAX_RAGGED_MEMORY} a ragged batch takes "
+                             "(64 key splits of 256); decode it alone")
+
+
 class _DecodeDesc(ctypes.Structure):
     """omr_decode_desc of include/omr_hip.h."""
     _fields_ = [(n, ctypes.c_int) for n in ("dtype", "B", "L", "d", "nhead", "ff", "V", "ldv", "max_len", "S", "window", "fp8")] + [
@@ -341,28 +370,34 @@ class DecodeState:
     FP8_PARAMS = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "multihead_attn.in_proj_weight",
                   "multihead_attn.out_proj.weight", "linear1.weight", "linear2.weight")          # OMR_DECODE_LAYER_FP8 order
 
-    def __init__(self, dec: "Decoder", memory: torch.Tensor, dt: torch.dtype):
+    def __init__(self, dec: "Decoder", memory, dt: torch.dtype):
         layers = dec.transformer_decoder.layers
         self.dec, self.dtype, self.t = dec, dt, 0
         self.L, self.d = len(layers), dec.embedding.weight.shape[1]
-        self.B, self.S = memory.shape[0], memory.shape[1]
+        ragged = isinstance(memory, list)              # [S_b, d] memories of different lengths (Decoder.init_decode)
+        mems = memory if ragged else [memory.reshape(-1, self.d)]
+        self.B = len(memory) if ragged else memory.shape[0]
+        self.S = max(m.shape[0] for m in memory) if ragged else memory.shape[1]
         self.max_len = dec.pos_1d.pe.shape[1]
         self.V, self.ldv = dec.output_size, K.round_up(dec.output_size, 8)
-        L, d, dev = self.L, self.d, memory.device
+        L, d, dev = self.L, self.d, mems[0].device
         # cross-attention K|V rows [d, 3d) of every layer's packed in_proj over the memory: one GEMM where the flat buffer
-        # holds the layers back to back (Decoder._cross_kv_pack), else one GEMM per layer into its column block
-        mem2 = memory.reshape(-1, d)
+        # holds the layers back to back (Decoder._cross_kv_pack), else one GEMM per layer into its column block.  Ragged: one
+        # GEMM per memory into the first S_b rows of its slot -- the very GEMM a batch-size-1 state of that memory runs
         self.cross_kv = torch.empty((self.B, self.S, L * 2 * d), dtype=dt, device=dev)
-        kv2 = self.cross_kv.view(-1, L * 2 * d)
         pack = dec._cross_kv_pack(dt)
-        if pack is not None:
-            K.gemm_row_groups(mem2, pack["w"], kv2, mem2.shape[0], L * 2 * d, d, bias=pack["b"], group=(2 * d, 3 * d, d, 1))
-        else:
-            for li, layer in enumerate(layers):
-                mha = layer.multihead_attn
-                w = Fn.wt(mha.in_proj_weight, dt)
-                K.gemm(mem2, w[d:], bias=mha.in_proj_bias.omr_phys[d:], out=kv2[:, li * 2 * d:(li + 1) * 2 * d])
+        for b, mem2 in enumerate(mems):
+            kv2 = self.cross_kv[b, :mem2.shape[0]] if ragged else self.cross_kv.view(-1, L * 2 * d)
+            if pack is not None:
+                K.gemm_row_groups(mem2, pack["w"], kv2, mem2.shape[0], L * 2 * d, d, bias=pack["b"], group=(2 * d, 3 * d, d, 1))
+            else:
+                for li, layer in enumerate(layers):
+                    mha = layer.multihead_attn
+                    w = Fn.wt(mha.in_proj_weight, dt)
+                    K.gemm(mem2, w[d:], bias=mha.in_proj_bias.omr_phys[d:], out=kv2[:, li * 2 * d:(li + 1) * 2 * d])
         self.cross_bs = self.S * L * 2 * d
+        # row b's memory length (device int32), or None: every row sees all S rows
+        self.mem_len = torch.tensor([m.shape[0] for m in mems], dtype=torch.int32).to(dev) if ragged else None
         self.self_kv = torch.empty((L, self.B, self.max_len, 2 * d), dtype=dt, device=dev)
 
         def pointer(p):            # matrices in the compute dtype, vectors (biases, LayerNorm) fp32
@@ -416,6 +451,8 @@ class DecodeState:
 
     def share_memory_between(self, rows: int) -> None:
         """Beam search: `rows` hypotheses over the ONE memory this state was initialised with (cross K|V batch stride 0)."""
+        if self.mem_len is not None:
+            raise RuntimeError("share_memory_between: beam search does not take a ragged decode state")
         assert self.B == 1 and self.t == 0
         self.B, self.cross_bs = rows, 0
         self.self_kv = torch.empty((self.L, rows, self.max_len, 2 * self.d), dtype=self.dtype, device=self.self_kv.device)
@@ -423,6 +460,8 @@ class DecodeState:
 
     def reorder_rows(self, parents: torch.Tensor) -> None:
         """Beam search: row i continues hypothesis parents[i] (re-gathers the self-attention cache rows)."""
+        if self.mem_len is not None:
+            raise RuntimeError("reorder_rows: beam search does not take a ragged decode state")
         self.self_kv = self.self_kv.index_select(1, parents)
         self.desc.self_kv = self.self_kv.data_ptr()
 
@@ -433,11 +472,18 @@ class DecodeState:
         if self.t + n > self.max_len:
             raise RuntimeError("decode_step beyond max_seq_len (positional-encoding table exhausted)")
 
+    def _steps(self, t0: int, n_steps: int, toks, top1, logits) -> None:
+        if self.mem_len is None:
+            lib().call("omr_decode_steps", ctypes.byref(self.desc), ptr(self.tok), t0, n_steps, ptr(toks), ptr(top1), ptr(logits), cur_stream())
+        else:
+            lib().call("omr_decode_steps_varlen", ctypes.byref(self.desc), ptr(self.mem_len), ptr(self.tok), t0, n_steps, ptr(toks), ptr(top1),
+                       ptr(logits), cur_stream())
+
     def step_logits(self, token: torch.Tensor) -> torch.Tensor:
         """One position, no token pick: fp32 logits [B, V] (a view of this state's buffer, valid until the next call)."""
         self._check(token, 1)
         self.tok.copy_(token.reshape(-1))
-        lib().call("omr_decode_steps", ctypes.byref(self.desc), ptr(self.tok), self.t, 1, None, None, ptr(self.logits), cur_stream())
+        self._steps(self.t, 1, None, None, self.logits)
         self.t += 1
         return self.logits[:, :self.V]
 
@@ -446,6 +492,6 @@ class DecodeState:
         self.tok.copy_(token.reshape(-1))
         toks = torch.empty((n_steps, self.B), dtype=torch.int64, device=self.tok.device)
         top1 = torch.empty((n_steps, self.B), dtype=torch.float32, device=self.tok.device)
-        lib().call("omr_decode_steps", ctypes.byref(self.desc), ptr(self.tok), self.t, n_steps, ptr(toks), ptr(top1), None, cur_stream())
+        self._steps(self.t, n_steps, toks, top1, None)
         self.t += n_steps
         return toks, top1

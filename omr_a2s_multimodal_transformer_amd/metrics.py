@@ -2,7 +2,7 @@
 off by default in the reference, metrics.py:18) is out of scope."""
 from __future__ import annotations
 
-from typing import Dict, List, Sequence
+from typing import Dict, List, Sequence, Tuple
 
 
 def edit_distance(a: Sequence, b: Sequence) -> int:
@@ -18,16 +18,43 @@ def edit_distance(a: Sequence, b: Sequence) -> int:
     return prev[-1]
 
 
+def edit_distances(pairs: Sequence[Tuple[Sequence, Sequence]]) -> List[int]:
+    """edit_distance of every (a, b) pair, by the library's host function omr_edit_distance_batch.  The tokens are mapped to
+    int ids afresh on each call: the two sides may come from different vocabularies (ytest_i2w vs i2w), so only the tokens
+    themselves can be compared."""
+    import ctypes
+
+    import numpy as np
+
+    from ._lib import lib
+    if not pairs:
+        return []
+    ids: Dict[object, int] = {}
+
+    def flat(seqs):
+        vals = [ids.setdefault(tok, len(ids)) for s in seqs for tok in s]
+        off = np.zeros(len(seqs) + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in seqs], out=off[1:])
+        return np.asarray(vals, dtype=np.int32), off
+
+    a, a_off = flat([p[0] for p in pairs])
+    b, b_off = flat([p[1] for p in pairs])
+    dist = np.zeros(len(pairs), dtype=np.int64)
+    vp = lambda x: ctypes.c_void_p(x.ctypes.data)
+    lib().call("omr_edit_distance_batch", vp(a), vp(a_off), vp(b), vp(b_off), len(pairs), vp(dist))
+    return dist.tolist()
+
+
 def ed_counts(y_true: List[List[str]], y_pred: List[List[str]]) -> List[int]:
     """[sum of edit distances, sum of truth lengths, sequences with any error, sequences]: the four integers sym-er / seq-er
     are ratios of.  They ADD over shards of the evaluation set, so a data-parallel evaluation all-reduces them and every rank
-    gets exactly the single-process metrics (metrics.py:76-88)."""
-    ed_acc = length_acc = wrong = 0
-    for t, h in zip(y_true, y_pred):
-        ed = edit_distance(t, h)
-        ed_acc += ed
-        length_acc += len(t)
-        wrong += ed > 0
+    gets exactly the single-process metrics (metrics.py:76-88).  The distances are edit_distance's,
+    computed natively (edit_distances)."""
+    pairs = list(zip(y_true, y_pred))
+    dists = edit_distances(pairs)
+    ed_acc = sum(dists)
+    length_acc = sum(len(t) for t, _ in pairs)
+    wrong = sum(1 for ed in dists if ed > 0)
     return [ed_acc, length_acc, wrong, len(y_pred)]
 
 

@@ -5,9 +5,10 @@ for the parameterised builds BASELINE.json names.  The three reference quirks (S
 from __future__ import annotations
 
 import ctypes
+import itertools
 import math
 import random
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -16,8 +17,9 @@ from . import functional as Fn
 from . import kernels as K
 from ._lib import lib
 from .config import ModelConfig
-from .decoder import Decoder, MultiheadAttention
+from .decoder import MIN_RAGGED_MEMORY, Decoder, MultiheadAttention, check_ragged_memories
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
+from .evaluation import WINDOW_BATCHES, plan_groups
 from .lightning_shim import LightningModule
 from .metrics import compute_metrics, compute_metrics_sharded
 from .runtime import FlatModuleMixin
@@ -191,15 +193,39 @@ class _Base(FlatModuleMixin, LightningModule):
         return yhat, probs
 
     @torch.no_grad()
-    def greedy_batch(self, memory: torch.Tensor, sync_every: int = 8) -> List[List[str]]:
-        """KV-cached greedy decode of B same-sized inputs at once (the reference loops bs = 1,
+    def greedy_batch(self, memory, sync_every: int = 8) -> List[List[str]]:
+        """KV-cached greedy decode of B inputs at once (the reference loops bs = 1,
         model.py:182-193).  Rows of the batch never interact, so each sequence equals what `_greedy` returns for that sample
-        alone (tests/test_model_gpu.py).  Inputs must share their size: the reference pads nothing at inference, and padding
-        would change the encoder features.  The host reads the chosen tokens back every `sync_every` steps only."""
+        alone (tests/test_model_gpu.py).  `memory` [B, S, d]: same-sized inputs.  A LIST of memories ([1, S_b, d] or [S_b, d])
+        of different lengths -- padding would change the encoder features, so the reference pads nothing at inference -- is
+        decoded as one ragged state (tests/test_ragged_decode_gpu.py); memories of at most 64 tokens go through `_greedy`.
+        Returns one word list per memory, in input order.  The host reads the chosen tokens back every `sync_every` steps only."""
+        if isinstance(memory, (list, tuple)):
+            return self._greedy_ragged(list(memory), sync_every)
         B = memory.shape[0]
-        sos, eos = self.w2i[SOS_TOKEN], self.w2i[EOS_TOKEN]
-        tok = torch.full((B, 1), sos, dtype=torch.int64, device=memory.device)
         state = self.decoder.init_decode(memory)
+        return [[self._i2w(t) for t in seq] for seq in self._greedy_rows(state, B, memory.device, sync_every)]
+
+    def _greedy_ragged(self, memories: List[torch.Tensor], sync_every: int) -> List[List[str]]:
+        mems = [m[0] if m.dim() == 3 else m for m in memories]
+        check_ragged_memories([m.shape for m in mems], self.decoder.embedding.weight.shape[1])
+        out: List[Optional[List[str]]] = [None] * len(mems)
+        batched = []
+        for i, m in enumerate(mems):
+            if m.shape[0] <= MIN_RAGGED_MEMORY:          # alone, such a memory takes another attention kernel: decode it alone
+                out[i] = self._greedy(m.unsqueeze(0))[0]
+            else:
+                batched.append(i)
+        if batched:
+            state = self.decoder.init_decode([mems[i] for i in batched])
+            for i, seq in zip(batched, self._greedy_rows(state, len(batched), mems[batched[0]].device, sync_every)):
+                out[i] = [self._i2w(t) for t in seq]
+        return out
+
+    def _greedy_rows(self, state, B: int, device, sync_every: int) -> List[List[int]]:
+        """Token ids of B rows of a decode state, each cut after its <eos> or max_seq_len tokens."""
+        sos, eos = self.w2i[SOS_TOKEN], self.w2i[EOS_TOKEN]
+        tok = torch.full((B, 1), sos, dtype=torch.int64, device=device)
         done = [False] * B
         out: List[List[int]] = [[] for _ in range(B)]
         left = self.max_seq_len
@@ -213,7 +239,48 @@ class _Base(FlatModuleMixin, LightningModule):
                         done[b] = t == eos
             tok = toks[-1].view(B, 1)
             left -= n
-        return [[self._i2w(t) for t in seq] for seq in out]
+        return out
+
+    @torch.no_grad()
+    def _predict(self, items: Iterable, encode: Callable[[object], torch.Tensor], batch_size: int) -> List[List[str]]:
+        """Greedy predictions of inputs of any size, in input order, each equal to `_greedy` of that input alone.  A window
+        of WINDOW_BATCHES * batch_size inputs at a time is encoded at batch size 1 (like validation_step), grouped by memory
+        length (evaluation.plan_groups) and decoded group by group as ragged batches of up to batch_size rows."""
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        it = iter(items)
+        preds: List[List[str]] = []
+        while True:
+            window = list(itertools.islice(it, WINDOW_BATCHES * batch_size))
+            if not window:
+                return preds
+            mems = [encode(x) for x in window]
+            out: List[Optional[List[str]]] = [None] * len(mems)
+            singles, groups = plan_groups([m.shape[1] for m in mems], batch_size)
+            for i in singles:
+                out[i] = self._greedy(mems[i])[0]
+            for g in groups:
+                for i, seq in zip(g, self.greedy_batch([mems[i] for i in g])):
+                    out[i] = seq
+            preds += out
+            del mems
+
+    @torch.no_grad()
+    def _evaluate(self, batches: Iterable, inputs_of: Callable, batch_size: int) -> Dict[str, float]:
+        """validation_step over `batches` + on_validation_epoch_end, decoded in ragged batches: the same metrics dict, without
+        logging and without touching self.Y / self.YHat.  The counts go through metrics.ed_counts (compute_metrics_sharded
+        combines them across ranks)."""
+        truth: List[List[str]] = []
+
+        def inputs():
+            for batch in batches:
+                y = batch[-1]
+                assert y.size(0) == 1, "evaluate takes the batches of validation_step (batch_size = 1)"
+                truth.append([self.ytest_i2w[i] for i in y[0][1:].tolist()])
+                yield inputs_of(batch)
+
+        preds = self._predict(inputs(), self._encode_input, batch_size)
+        return compute_metrics(y_true=truth, y_pred=preds)
 
     @torch.no_grad()
     def beam_search(self, memory: torch.Tensor, beam: int = 4) -> Tuple[List[str], float]:
@@ -348,6 +415,21 @@ class Transformer(_Base):
         assert x.size(0) == 1, "Inference only supports batch_size = 1"
         return self._greedy(self.encode(x), want_probs=True)
 
+    def _encode_input(self, x: torch.Tensor) -> torch.Tensor:
+        assert x.size(0) == 1, "predict takes inputs of batch size 1 ([1, C, H, W]); their sizes may differ"
+        return self.encode(x)
+
+    @torch.no_grad()
+    def predict(self, xs: Iterable[torch.Tensor], batch_size: int = 32) -> List[List[str]]:
+        """Greedy predictions of inputs [1, C, H_b, W_b] of any size, in input order: each equals validation_step's decode
+        of that input, decoded batch_size memories at a time."""
+        return self._predict(xs, self._encode_input, batch_size)
+
+    @torch.no_grad()
+    def evaluate(self, batches: Iterable, batch_size: int = 32) -> Dict[str, float]:
+        """The metrics of validation_step over `batches` ((x, y) each) followed by on_validation_epoch_end, decoded in batches."""
+        return self._evaluate(batches, lambda batch: batch[0], batch_size)
+
 
 ##################################################################### MULTIMODAL TRANSFORMER
 
@@ -473,6 +555,24 @@ class MultimodalTransformer(_Base):
         yhat, _ = self._greedy(x)
         self.Y.append([self.ytest_i2w[i.item()] for i in y[0][1:]])
         self.YHat.append(yhat)
+
+    def _encode_input(self, pair) -> torch.Tensor:
+        xi, xa = pair
+        assert xi.size(0) == xa.size(0) == 1, "predict takes (image, audio) pairs of batch size 1; their sizes may differ"
+        x, _ = self.encoder_forward(xi=xi, xa=xa, xli=None, xla=None, apply_teacher_forcing_modality=False)
+        return x
+
+    @torch.no_grad()
+    def predict(self, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], batch_size: int = 32) -> List[List[str]]:
+        """Greedy predictions of (image, audio) pairs of any size, in input order: each equals validation_step's decode of
+        that pair, decoded batch_size memories at a time."""
+        return self._predict(pairs, self._encode_input, batch_size)
+
+    @torch.no_grad()
+    def evaluate(self, batches: Iterable, batch_size: int = 32) -> Dict[str, float]:
+        """The metrics of validation_step over `batches` ((xi, xa, y) each) followed by on_validation_epoch_end, decoded in
+        batches."""
+        return self._evaluate(batches, lambda batch: (batch[0], batch[1]), batch_size)
 
     ##### MODALITY MIXERS (model.py:644-726)
 
