@@ -52,6 +52,12 @@ int omr_argmax(const float* x, int rows, int n, long ld, long* idx_out, float* v
  * run in lock-step, argmax(alpha * softmax(logits_a) + (1 - alpha) * softmax(logits_b)) over fp32 rows of n logits, first-index
  * tie rule; prob_out (nullable) receives the winning mixed probability.  alpha is rounded like the reference's Python float. */
 int omr_weighted_argmax(const float* logits_a, const float* logits_b, int n, float alpha, long* idx_out, float* prob_out, void* stream);
+/* omr_weighted_argmax for a batch of row pairs (one decoding step of `rows` samples, test.py:50-61 per sample): row r reads
+ * logits_a + r * lda and logits_b + r * ldb (lda, ldb >= n); idx_out[r] / prob_out[r] (nullable) are bit for bit what
+ * omr_weighted_argmax gives for that pair alone (one kernel serves both).  tokens_out (nullable, [rows]) receives the picked
+ * tokens as well: where the next decoding position reads its input. */
+int omr_weighted_argmax_rows(const float* logits_a, long lda, const float* logits_b, long ldb, int rows, int n, float alpha,
+                             long* idx_out, float* prob_out, long* tokens_out, void* stream);
 /* audio front end (preprocessing.py:17-30): after the windowed DFT -- ONE omr_gemm of the centred,
  * hop-strided frames (lda = hop) against the Hann-weighted [cos | -sin] basis of the kept bins -- spec [frames][2*bins] holds
  * (re | im); this turns it into the reference's normalised log-spectrogram out [bins][frames] =
@@ -350,6 +356,16 @@ int omr_decode_steps_varlen(const omr_decode_desc* desc, const int* mem_len, lon
  * 1 entry: in = the token of position t0).  logits_a / logits_b: fp32 scratch of ldv entries each. */
 int omr_weighted_decode_steps(const omr_decode_desc* desc_a, const omr_decode_desc* desc_b, float alpha, long* tokens, int t0, int n_steps,
                               long* out_tokens, float* out_prob, float* logits_a, float* logits_b, void* stream);
+/* omr_weighted_decode_steps for B pairs at once (the reference loops over its test set one pair at a time,
+ * src/multimodal/weighted_multimodal/test.py:21-70,154-172): desc_a->B == desc_b->B == B >= 1, same V.  mem_len_a / mem_len_b:
+ * device int32 [B] as in omr_decode_steps_varlen, or NULL (every row of that model sees its S), independently per model.
+ * Per position both models run their step for all rows, then ONE omr_weighted_argmax_rows launch writes out_tokens[s][B],
+ * out_prob[s][B] (nullable) and `tokens` (device, B entries: in = the tokens of position t0, out = those of the last
+ * position).  logits_a / logits_b: fp32 scratch [B][ldv] of the respective model.  A row whose memories BOTH have more than
+ * 64 tokens gets, token for token and probability bit for bit, what omr_weighted_decode_steps gives for that pair alone. */
+int omr_weighted_decode_steps_varlen(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b,
+                                     const int* mem_len_b, float alpha, long* tokens, int t0, int n_steps, long* out_tokens,
+                                     float* out_prob, float* logits_a, float* logits_b, void* stream);
 
 /* ---- loss ------------------------------------------------------------------------------------------------ */
 /* CrossEntropyLoss(ignore_index=pad) (model.py:109,166) on row-major logits [M][ldv]; acc2 = {sum, count} (fp64). */

@@ -456,18 +456,30 @@ extern "C" int omr_decode_steps_varlen(const omr_decode_desc* dp, const int* mem
 }
 
 /* Weighted late fusion (src/multimodal/weighted_multimodal/test.py:21-70) as ONE host call per run of tokens: two unimodal
- * models with their own KV caches decode the same prefix in lock-step; per position both descriptors run their step
- * (omr_decode_steps without a pick: fp32 logits only), omr_weighted_argmax mixes the two softmaxes and picks, and the token
- * reaches BOTH models' next position through device memory.  bs = 1 like the reference (test.py:27). */
-extern "C" int omr_weighted_decode_steps(const omr_decode_desc* da, const omr_decode_desc* db, float alpha, long* tokens, int t0, int n_steps,
-                                         long* out_tokens, float* out_prob, float* logits_a, float* logits_b, void* stream) {
+ * models with their own KV caches decode the same prefixes in lock-step; per position both descriptors run their step for all
+ * B rows (decode_steps without a pick: fp32 logits only), ONE omr_weighted_argmax_rows launch mixes the two softmaxes of every
+ * row and picks, and the tokens reach BOTH models' next position through device memory (`tokens`, written by the same launch).
+ * mem_len_a / mem_len_b (nullable, independently): ragged memories of that model.  Rows never interact, so a row equals the
+ * pair decoded alone (omr_weighted_decode_steps) whenever both of its memories take the key-split attention (> 64 tokens). */
+extern "C" int omr_weighted_decode_steps_varlen(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
+                                                float alpha, long* tokens, int t0, int n_steps, long* out_tokens, float* out_prob, float* logits_a,
+                                                float* logits_b, void* stream) {
     if (!da || !db || !tokens || !out_tokens || !logits_a || !logits_b || n_steps < 1 || t0 < 0) return OMR_ERR_ARG;
-    if (da->B != 1 || db->B != 1 || da->V != db->V) return OMR_ERR_ARG;
+    if (da->B < 1 || da->B != db->B || da->V != db->V) return OMR_ERR_ARG;
+    if (t0 + n_steps > da->max_len || t0 + n_steps > db->max_len) return OMR_ERR_ARG;      // refuse before the first launch, not at the position that runs out
+    const int B = da->B;
     for (int s = 0; s < n_steps; ++s) {
-        TRY(omr_decode_steps(da, tokens, t0 + s, 1, nullptr, nullptr, logits_a, stream));
-        TRY(omr_decode_steps(db, tokens, t0 + s, 1, nullptr, nullptr, logits_b, stream));
-        TRY(omr_weighted_argmax(logits_a, logits_b, da->V, alpha, out_tokens + s, out_prob ? out_prob + s : nullptr, stream));
-        if (hipMemcpyAsync(tokens, out_tokens + s, sizeof(long), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return OMR_ERR_LAUNCH;
+        TRY(decode_steps(da, mem_len_a, tokens, t0 + s, 1, nullptr, nullptr, logits_a, stream));
+        TRY(decode_steps(db, mem_len_b, tokens, t0 + s, 1, nullptr, nullptr, logits_b, stream));
+        TRY(omr_weighted_argmax_rows(logits_a, da->ldv, logits_b, db->ldv, B, da->V, alpha, out_tokens + (size_t)s * B,
+                                     out_prob ? out_prob + (size_t)s * B : nullptr, tokens, stream));
     }
     return OMR_OK;
+}
+
+/* bs = 1 like the reference (test.py:27): the one-row, full-memory case of the loop above */
+extern "C" int omr_weighted_decode_steps(const omr_decode_desc* da, const omr_decode_desc* db, float alpha, long* tokens, int t0, int n_steps,
+                                         long* out_tokens, float* out_prob, float* logits_a, float* logits_b, void* stream) {
+    if (!da || !db || da->B != 1 || db->B != 1) return OMR_ERR_ARG;
+    return omr_weighted_decode_steps_varlen(da, nullptr, db, nullptr, alpha, tokens, t0, n_steps, out_tokens, out_prob, logits_a, logits_b, stream);
 }

@@ -201,13 +201,17 @@ __global__ void argmax_kernel(const float* __restrict__ x0, int n, long ld, long
 
 // ---------------------------------------------------------------- weighted late fusion (weighted_multimodal/test.py:50-61)
 // token = argmax(alpha * softmax(la) + (1 - alpha) * softmax(lb)), first-index tie rule; also returns the mixed probability.
-// One workgroup, three passes over the two logit rows (V <= a few thousand: L2-resident).  The mix is two roundings of
-// products plus one add like torch's `alpha * p + (1 - alpha) * q` (no fma contraction), so ties break the same way.
-__global__ void weighted_argmax_kernel(const float* __restrict__ la, const float* __restrict__ lb, int n, float wa, float wb,
-                                       long* __restrict__ idx_out, float* __restrict__ prob_out) {
+// One workgroup per row pair, three passes over the two logit rows (V <= a few thousand: L2-resident).  The mix is two roundings
+// of products plus one add like torch's `alpha * p + (1 - alpha) * q` (no fma contraction), so ties break the same way.
+// A row's arithmetic does not depend on how many rows the grid has: row r of a batch equals the same pair launched alone.
+// tokens_out (nullable): a second copy of the picked index, where the next decoding position reads its input token.
+__global__ void weighted_argmax_kernel(const float* __restrict__ la0, long lda, const float* __restrict__ lb0, long ldb, int n, float wa, float wb,
+                                       long* __restrict__ idx_out, float* __restrict__ prob_out, long* __restrict__ tokens_out) {
     __shared__ float sa[256], sb[256];
     __shared__ int si[256];
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, row = blockIdx.x;
+    const float* __restrict__ la = la0 + (long)row * lda;
+    const float* __restrict__ lb = lb0 + (long)row * ldb;
     float ma = -INFINITY, mb = -INFINITY;
     for (int i = tid; i < n; i += 256) { ma = fmaxf(ma, la[i]); mb = fmaxf(mb, lb[i]); }
     sa[tid] = ma; sb[tid] = mb;
@@ -237,7 +241,11 @@ __global__ void weighted_argmax_kernel(const float* __restrict__ la, const float
         }
         __syncthreads();
     }
-    if (tid == 0) { idx_out[0] = si[0]; if (prob_out) prob_out[0] = sa[0]; }
+    if (tid == 0) {
+        idx_out[row] = si[0];
+        if (prob_out) prob_out[row] = sa[0];
+        if (tokens_out) tokens_out[row] = si[0];
+    }
 }
 
 // ---------------------------------------------------------------- top-k log-probabilities per row (beam search)
@@ -438,12 +446,18 @@ extern "C" int omr_topk_logprob(const float* x, int rows, int n, long ld, int k,
     return OMR_OK;
 }
 
-extern "C" int omr_weighted_argmax(const float* logits_a, const float* logits_b, int n, float alpha, long* idx_out, float* prob_out, void* stream) {
-    if (n <= 0 || !logits_a || !logits_b || !idx_out) return OMR_ERR_ARG;
+extern "C" int omr_weighted_argmax_rows(const float* logits_a, long lda, const float* logits_b, long ldb, int rows, int n, float alpha,
+                                        long* idx_out, float* prob_out, long* tokens_out, void* stream) {
+    if (rows < 1 || n < 1 || lda < n || ldb < n || !logits_a || !logits_b || !idx_out) return OMR_ERR_ARG;
     // the reference multiplies fp32 tensors by the Python floats alpha and (1 - alpha): each is rounded to fp32 once
-    hipLaunchKernelGGL(weighted_argmax_kernel, 1, 256, 0, (hipStream_t)stream, logits_a, logits_b, n, alpha, (float)(1.0 - (double)alpha), idx_out, prob_out);
+    hipLaunchKernelGGL(weighted_argmax_kernel, rows, 256, 0, (hipStream_t)stream, logits_a, lda, logits_b, ldb, n, alpha, (float)(1.0 - (double)alpha),
+                       idx_out, prob_out, tokens_out);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
+}
+
+extern "C" int omr_weighted_argmax(const float* logits_a, const float* logits_b, int n, float alpha, long* idx_out, float* prob_out, void* stream) {
+    return omr_weighted_argmax_rows(logits_a, n, logits_b, n, 1, n, alpha, idx_out, prob_out, nullptr, stream);
 }
 
 extern "C" int omr_argmax(const float* x, int rows, int n, long ld, long* idx_out, float* val_out, void* stream) {

@@ -465,6 +465,11 @@ class DecodeState:
         self.self_kv = self.self_kv.index_select(1, parents)
         self.desc.self_kv = self.self_kv.data_ptr()
 
+    def rewind(self) -> None:
+        """Decode again from <sos> over the same memories (an alpha sweep of the weighted fusion): the cross-attention K|V
+        stay as projected; the self-attention cache is overwritten from position 0 and never read beyond t."""
+        self.t = 0
+
     def _check(self, token: torch.Tensor, n: int) -> None:
         require_cuda(token)
         if token.numel() != self.B or token.dtype != torch.int64:

@@ -29,3 +29,30 @@ def plan_groups(lengths: Sequence[int], batch_size: int, window: int = 0) -> Tup
         rest = sorted((i for i in idx if MIN_RAGGED_MEMORY < lengths[i] <= MAX_RAGGED_MEMORY), key=lambda i: (-lengths[i], i))
         groups += [rest[g:g + batch_size] for g in range(0, len(rest), batch_size)]
     return singles, groups
+
+
+def plan_pair_groups(len_a: Sequence[int], len_b: Sequence[int], batch_size: int,
+                     window: int = 0) -> Tuple[List[int], List[List[int]]]:
+    """plan_groups for PAIRS of memories decoded by two models in lock-step (weighted late fusion): pair i has len_a[i] tokens
+    for one model and len_b[i] for the other.  singles: pairs of which EITHER memory has at most MIN_RAGGED_MEMORY or more
+    than MAX_RAGGED_MEMORY tokens (decoded alone, through the batch-size-1 path).  groups: the other indices, sorted by
+    decreasing len_a + len_b (ties: input order; the key affects speed only, never results) within consecutive windows of
+    `window` pairs (0: one window) and cut into groups of at most batch_size.  Every index appears exactly once."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    if len(len_a) != len(len_b):
+        raise ValueError(f"plan_pair_groups: {len(len_a)} lengths for one model, {len(len_b)} for the other")
+
+    def ragged(i: int) -> bool:
+        return MIN_RAGGED_MEMORY < len_a[i] <= MAX_RAGGED_MEMORY and MIN_RAGGED_MEMORY < len_b[i] <= MAX_RAGGED_MEMORY
+
+    n = len(len_a)
+    window = window if window > 0 else max(n, 1)
+    singles: List[int] = []
+    groups: List[List[int]] = []
+    for w0 in range(0, n, window):
+        idx = range(w0, min(n, w0 + window))
+        singles += [i for i in idx if not ragged(i)]
+        rest = sorted((i for i in idx if ragged(i)), key=lambda i: (-(len_a[i] + len_b[i]), i))
+        groups += [rest[g:g + batch_size] for g in range(0, len(rest), batch_size)]
+    return singles, groups

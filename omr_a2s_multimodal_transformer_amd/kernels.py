@@ -304,6 +304,23 @@ def weighted_argmax(la: Tensor, lb: Tensor, alpha: float) -> Tuple[Tensor, Tenso
     return idx, prob
 
 
+def weighted_argmax_rows(la: Tensor, lb: Tensor, alpha: float, n: Optional[int] = None,
+                         tokens_out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """weighted_argmax row by row in one launch: fp32 [rows, >= n] logits (row strides free, unit column stride; n defaults to
+    the narrower width) -> (indices int64 [rows], probabilities fp32 [rows]); tokens_out (int64 [rows]) gets the indices too."""
+    require_cuda(la, lb, tokens_out)
+    assert la.dtype == lb.dtype == torch.float32 and la.dim() == lb.dim() == 2 and la.shape[0] == lb.shape[0]
+    rows = la.shape[0]
+    n = min(la.shape[1], lb.shape[1]) if n is None else n
+    assert n <= min(la.shape[1], lb.shape[1]) and (la.stride(1) == 1 and lb.stride(1) == 1 or n == 1)
+    assert tokens_out is None or (tokens_out.dtype == torch.int64 and tokens_out.numel() == rows and tokens_out.is_contiguous())
+    idx = torch.empty(rows, dtype=torch.int64, device=la.device)
+    prob = torch.empty(rows, dtype=torch.float32, device=la.device)
+    lib().call("omr_weighted_argmax_rows", ptr(la), la.stride(0), ptr(lb), lb.stride(0), rows, n, float(alpha), ptr(idx), ptr(prob), ptr(tokens_out),
+               cur_stream())
+    return idx, prob
+
+
 def topk_logprob(x: Tensor, k: int) -> Tuple[Tensor, Tensor]:
     """x fp32 [rows, n] -> (token ids int64 [rows, k], log-probabilities fp32 [rows, k]), best first."""
     require_cuda(x)

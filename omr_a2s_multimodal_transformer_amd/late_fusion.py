@@ -7,11 +7,14 @@ The alignment itself is a host function of libomr_hip.so (`omr_sw_align`, intege
 restates `swalign.LocalAlignment`; `swalign` is absent from the reference tree and from this image, so the alignment is
 **parity unpinned**.  What follows the alignment is the reference's own Python and is reproduced as it is written,
 including `preprocess_prob`, which inserts the sentinel / gap probabilities at `position + insertions so far` (so the
-probabilities behind the first gap are shifted by one -- kept, because the fused output depends on it)."""
+probabilities behind the first gap are shifted by one -- kept, because the fused output depends on it).
+
+`sw_predict` / `sw_evaluate` run the whole evaluation of test.py:113-161: each model decodes its own inputs in ragged batches
+(Transformer.predict_with_probs instead of the batch-size-1 get_pred_seq_and_pred_prob_seq loop), then `fuse` per sample."""
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -101,3 +104,28 @@ def fuse(r: List[str], r_prob: List[float], q: List[str], q_prob: List[float], m
     qa, ma, ra = dump(rs, qs, ops, r_pos, q_pos)
     fused = get_alignment(qa, ma, ra, preprocess_prob(qa, q_prob), preprocess_prob(ra, r_prob))
     return [t for t in fused if t not in (START, END)]          # undo_swalign_preprocess (smith_waterman.py:162-173)
+
+
+def sw_predict(pairs: Iterable, img_model, audio_model, batch_size: int = 32, match: int = 2, mismatch: int = -1,
+               gap_penalty: int = -1) -> List[List[str]]:
+    """test.py:113-157 over (image, audio) pairs ([1, C, H, W] each, sizes free): the fused prediction of every pair, in input
+    order.  Each model decodes all of its inputs batch_size memories at a time (grouping its own memory lengths); every fused
+    sequence equals fuse() of the two get_pred_seq_and_pred_prob_seq results of that pair."""
+    pairs = list(pairs)
+    r, r_prob = img_model.predict_with_probs((xi for xi, _ in pairs), batch_size)
+    q, q_prob = audio_model.predict_with_probs((xa for _, xa in pairs), batch_size)
+    return [fuse(ri, rpi, qi, qpi, match, mismatch, gap_penalty) for ri, rpi, qi, qpi in zip(r, r_prob, q, q_prob)]
+
+
+def sw_evaluate(batches: Iterable, img_model, audio_model, batch_size: int = 32, match: int = 2, mismatch: int = -1,
+                gap_penalty: int = -1) -> Dict[str, float]:
+    """test.py:113-161 over `batches` ((xi, xa, y) as the test loader yields them): compute_metrics of sw_predict against the
+    ytest_i2w-decoded targets (without <sos>)."""
+    from .metrics import compute_metrics
+    truth: List[List[str]] = []
+    pairs = []
+    for xi, xa, y in batches:
+        assert y.size(0) == 1, "sw_evaluate takes the batches of the test loader (batch_size = 1)"
+        truth.append([img_model.ytest_i2w[i] for i in y[0][1:].tolist()])
+        pairs.append((xi, xa))
+    return compute_metrics(y_true=truth, y_pred=sw_predict(pairs, img_model, audio_model, batch_size, match, mismatch, gap_penalty))

@@ -222,47 +222,62 @@ class _Base(FlatModuleMixin, LightningModule):
                 out[i] = [self._i2w(t) for t in seq]
         return out
 
-    def _greedy_rows(self, state, B: int, device, sync_every: int) -> List[List[int]]:
-        """Token ids of B rows of a decode state, each cut after its <eos> or max_seq_len tokens."""
+    def _greedy_rows(self, state, B: int, device, sync_every: int, want_probs: bool = False):
+        """Token ids of B rows of a decode state, each cut after its <eos> or max_seq_len tokens.  want_probs: -> (ids, the
+        top-1 logit of every kept position), the floats get_pred_seq_and_pred_prob_seq returns for that row alone."""
         sos, eos = self.w2i[SOS_TOKEN], self.w2i[EOS_TOKEN]
         tok = torch.full((B, 1), sos, dtype=torch.int64, device=device)
         done = [False] * B
         out: List[List[int]] = [[] for _ in range(B)]
+        probs: List[List[float]] = [[] for _ in range(B)]
         left = self.max_seq_len
         while left > 0 and not all(done):
             n = min(sync_every, left)
-            toks, _ = self.decoder.decode_tokens(tok, state, n)      # n positions, tokens chained on the device
-            for row in toks.cpu().tolist():                           # one device sync for the whole chunk
+            toks, top1 = self.decoder.decode_tokens(tok, state, n)   # n positions, tokens chained on the device
+            top1_h = top1.cpu().tolist() if want_probs else None
+            for s, row in enumerate(toks.cpu().tolist()):             # one device sync for the whole chunk
                 for b, t in enumerate(row):
                     if not done[b]:
                         out[b].append(t)
+                        if want_probs:
+                            probs[b].append(float(top1_h[s][b]))
                         done[b] = t == eos
             tok = toks[-1].view(B, 1)
             left -= n
-        return out
+        return (out, probs) if want_probs else out
 
     @torch.no_grad()
-    def _predict(self, items: Iterable, encode: Callable[[object], torch.Tensor], batch_size: int) -> List[List[str]]:
+    def _predict(self, items: Iterable, encode: Callable[[object], torch.Tensor], batch_size: int, want_probs: bool = False):
         """Greedy predictions of inputs of any size, in input order, each equal to `_greedy` of that input alone.  A window
         of WINDOW_BATCHES * batch_size inputs at a time is encoded at batch size 1 (like validation_step), grouped by memory
-        length (evaluation.plan_groups) and decoded group by group as ragged batches of up to batch_size rows."""
+        length (evaluation.plan_groups) and decoded group by group as ragged batches of up to batch_size rows.
+        want_probs: -> (predictions, the top-1 logits of their positions) like `_greedy(..., want_probs=True)`."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         it = iter(items)
         preds: List[List[str]] = []
+        probs: List[List[float]] = []
         while True:
             window = list(itertools.islice(it, WINDOW_BATCHES * batch_size))
             if not window:
-                return preds
+                return (preds, probs) if want_probs else preds
             mems = [encode(x) for x in window]
             out: List[Optional[List[str]]] = [None] * len(mems)
+            outp: List[Optional[List[float]]] = [None] * len(mems)
             singles, groups = plan_groups([m.shape[1] for m in mems], batch_size)
             for i in singles:
-                out[i] = self._greedy(mems[i])[0]
+                out[i], outp[i] = self._greedy(mems[i], want_probs=want_probs)
             for g in groups:
-                for i, seq in zip(g, self.greedy_batch([mems[i] for i in g])):
-                    out[i] = seq
+                if want_probs:
+                    state = self.decoder.init_decode([mems[i] for i in g])
+                    seqs, top1 = self._greedy_rows(state, len(g), mems[g[0]].device, 8, want_probs=True)
+                    for i, seq, pr in zip(g, seqs, top1):
+                        out[i], outp[i] = [self._i2w(t) for t in seq], pr
+                else:
+                    for i, seq in zip(g, self.greedy_batch([mems[i] for i in g])):
+                        out[i] = seq
             preds += out
+            probs += outp
             del mems
 
     @torch.no_grad()
@@ -424,6 +439,12 @@ class Transformer(_Base):
         """Greedy predictions of inputs [1, C, H_b, W_b] of any size, in input order: each equals validation_step's decode
         of that input, decoded batch_size memories at a time."""
         return self._predict(xs, self._encode_input, batch_size)
+
+    @torch.no_grad()
+    def predict_with_probs(self, xs: Iterable[torch.Tensor], batch_size: int = 32) -> Tuple[List[List[str]], List[List[float]]]:
+        """get_pred_seq_and_pred_prob_seq (model.py:226-262) of inputs [1, C, H_b, W_b] of any size, decoded batch_size
+        memories at a time: (words, top-1 logits) per input, in input order, each equal to the batch-size-1 call's."""
+        return self._predict(xs, self._encode_input, batch_size, want_probs=True)
 
     @torch.no_grad()
     def evaluate(self, batches: Iterable, batch_size: int = 32) -> Dict[str, float]:

@@ -8,38 +8,39 @@ cache (Decoder.init_decode: cross-attention K|V projected once, self-attention K
 a step is one kernel (omr_weighted_argmax) and a CHUNK of positions is one host call (omr_weighted_decode_steps: the picked
 token reaches both models' next position through device memory; the host reads a chunk of tokens back at a time and cuts
 the sequence after <eos>).  Same tokens as the reference (tests/golden/f15_weighted.npz).
+
+The reference evaluates a test set one pair at a time (test.py:154-172).  `weighted_predict` / `weighted_evaluate` decode
+groups of pairs of different sizes as two ragged decode states in lock-step (omr_weighted_decode_steps_varlen: per position
+both models' steps for all rows, then one mixing launch for all rows); every sequence equals `weighted_prediction` of that
+pair.  A sequence of alphas re-runs only the decode: encoders and cross-attention projections run once per pair.
 """
 from __future__ import annotations
 
-from typing import List
-
 import ctypes
+import itertools
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from ._lib import cur_stream, lib, ptr
+from .evaluation import WINDOW_BATCHES, plan_pair_groups
+from .metrics import compute_metrics
 from .synthetic import EOS_TOKEN, SOS_TOKEN
 
+_EXHAUSTED = "weighted_prediction beyond a model's max_seq_len (positional-encoding table exhausted)"
 
-@torch.no_grad()
-def weighted_prediction(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_model, alpha: float = 0.5, chunk: int = 16) -> List[str]:
-    """weighted_multimodal/test.py:21-70, same signature and return value (the predicted words, <eos> included when reached).
-    Like the reference, the loop runs for max(img_model.max_seq_len, audio_model.max_seq_len) steps and a model whose
-    positional table is shorter than that raises when the sequence outgrows it."""
-    assert xi.size(0) == 1, "Inference only supports batch_size = 1"
-    mem_i = img_model.encode(xi)                       # encoder -> 2-D PE -> flatten (test.py:28-37)
-    mem_a = audio_model.encode(xa)
-    st_i = img_model.decoder.init_decode(mem_i)
-    st_a = audio_model.decoder.init_decode(mem_a)
+
+def _decode_pair(st_i, st_a, img_model, audio_model, alpha: float, chunk: int) -> List[str]:
+    """The lock-step loop of one pair (test.py:39-68) over two batch-size-1 decode states at position 0."""
     assert st_i.V == st_a.V, "both models share the vocabulary (test.py:62)"
-    dev = mem_i.device
+    dev = st_i.tok.device
     tok = torch.full((1,), img_model.w2i[SOS_TOKEN], dtype=torch.int64, device=dev)
     yhat: List[str] = []
     left = max(img_model.max_seq_len, audio_model.max_seq_len)
     while left > 0:
         n = min(chunk, left, st_i.max_len - st_i.t, st_a.max_len - st_a.t)
         if n <= 0:
-            raise RuntimeError("weighted_prediction beyond a model's max_seq_len (positional-encoding table exhausted)")
+            raise RuntimeError(_EXHAUSTED)
         toks = torch.empty(n, dtype=torch.int64, device=dev)
         lib().call("omr_weighted_decode_steps", ctypes.byref(st_i.desc), ctypes.byref(st_a.desc), float(alpha), ptr(tok), st_i.t, n, ptr(toks), None,
                    ptr(st_i.logits), ptr(st_a.logits), cur_stream())
@@ -52,3 +53,128 @@ def weighted_prediction(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_mod
                 return yhat
         left -= n
     return yhat
+
+
+@torch.no_grad()
+def weighted_prediction(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_model, alpha: float = 0.5, chunk: int = 16) -> List[str]:
+    """weighted_multimodal/test.py:21-70, same signature and return value (the predicted words, <eos> included when reached).
+    Like the reference, the loop runs for max(img_model.max_seq_len, audio_model.max_seq_len) steps and a model whose
+    positional table is shorter than that raises when the sequence outgrows it."""
+    assert xi.size(0) == 1, "Inference only supports batch_size = 1"
+    mem_i = img_model.encode(xi)                       # encoder -> 2-D PE -> flatten (test.py:28-37)
+    mem_a = audio_model.encode(xa)
+    st_i = img_model.decoder.init_decode(mem_i)
+    st_a = audio_model.decoder.init_decode(mem_a)
+    return _decode_pair(st_i, st_a, img_model, audio_model, alpha, chunk)
+
+
+def _decode_rows(st_i, st_a, img_model, audio_model, alpha: float, sync_every: int) -> List[List[str]]:
+    """B pairs in lock-step over two ragged decode states at position 0: weighted_prediction's loop for every row, the host
+    reading the tokens back every `sync_every` positions and cutting each row after its <eos>."""
+    assert st_i.V == st_a.V and st_i.B == st_a.B
+    B, dev = st_i.B, st_i.tok.device
+    sos, eos = img_model.w2i[SOS_TOKEN], img_model.w2i[EOS_TOKEN]
+    tok = torch.full((B,), sos, dtype=torch.int64, device=dev)
+    done = [False] * B
+    out: List[List[int]] = [[] for _ in range(B)]
+    left = max(img_model.max_seq_len, audio_model.max_seq_len)
+    while left > 0 and not all(done):
+        n = min(sync_every, left, st_i.max_len - st_i.t, st_a.max_len - st_a.t)
+        if n <= 0:                                     # a live row outgrew the shorter positional table
+            raise RuntimeError(_EXHAUSTED)
+        toks = torch.empty((n, B), dtype=torch.int64, device=dev)
+        lib().call("omr_weighted_decode_steps_varlen", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
+                   float(alpha), ptr(tok), st_i.t, n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
+        st_i.t += n
+        st_a.t += n
+        for row in toks.cpu().tolist():                # one device sync per chunk
+            for b, t in enumerate(row):
+                if not done[b]:
+                    out[b].append(t)
+                    done[b] = t == eos
+        left -= n
+    return [[img_model._i2w(t) for t in seq] for seq in out]
+
+
+def _check_models(img_model, audio_model) -> None:
+    if img_model.w2i != audio_model.w2i:
+        raise ValueError("Vocabularies do not match (weighted_multimodal/test.py:140)")
+
+
+def _alphas(alpha) -> Tuple[List[float], bool]:
+    if isinstance(alpha, (int, float)):
+        return [float(alpha)], False
+    return [float(a) for a in alpha], True
+
+
+@torch.no_grad()
+def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[float], batch_size: int, sync_every: int,
+                      chunk: int = 16) -> List[List[List[str]]]:
+    """-> one prediction list per alpha.  Every pair is encoded once per model and every group's (or single's) decode states
+    are built once; each alpha decodes from position 0 again (DecodeState.rewind)."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    if sync_every < 1:
+        raise ValueError(f"sync_every must be >= 1, got {sync_every}")
+    _check_models(img_model, audio_model)
+    it = iter(pairs)
+    preds: List[List[List[str]]] = [[] for _ in alphas]
+    while True:
+        window = list(itertools.islice(it, WINDOW_BATCHES * batch_size))
+        if not window:
+            return preds
+        for xi, xa in window:                          # refuse before anything of this window is launched
+            assert xi.size(0) == 1 and xa.size(0) == 1, "weighted_predict takes (image, audio) pairs of batch size 1; their sizes may differ"
+        mems_i = [img_model.encode(xi) for xi, _ in window]
+        mems_a = [audio_model.encode(xa) for _, xa in window]
+        out: List[List[Optional[List[str]]]] = [[None] * len(window) for _ in alphas]
+        singles, groups = plan_pair_groups([m.shape[1] for m in mems_i], [m.shape[1] for m in mems_a], batch_size)
+        for i in singles:
+            st_i = img_model.decoder.init_decode(mems_i[i])
+            st_a = audio_model.decoder.init_decode(mems_a[i])
+            for k, alpha in enumerate(alphas):
+                st_i.rewind()
+                st_a.rewind()
+                out[k][i] = _decode_pair(st_i, st_a, img_model, audio_model, alpha, chunk)
+        for g in groups:
+            st_i = img_model.decoder.init_decode([mems_i[i] for i in g])
+            st_a = audio_model.decoder.init_decode([mems_a[i] for i in g])
+            for k, alpha in enumerate(alphas):
+                st_i.rewind()
+                st_a.rewind()
+                for i, seq in zip(g, _decode_rows(st_i, st_a, img_model, audio_model, alpha, sync_every)):
+                    out[k][i] = seq
+            del st_i, st_a
+        for k in range(len(alphas)):
+            preds[k] += out[k]
+        del mems_i, mems_a
+
+
+def weighted_predict(pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], img_model, audio_model, alpha: Union[float, Sequence[float]] = 0.5,
+                     batch_size: int = 32, sync_every: int = 8):
+    """Weighted predictions of (image, audio) pairs ([1, C, H, W] each, sizes free), in input order: each equals
+    weighted_prediction(xi, xa, img_model, audio_model, alpha).  A window of WINDOW_BATCHES * batch_size pairs at a time is
+    encoded at batch size 1 by each model, grouped by evaluation.plan_pair_groups and decoded group by group, both models in
+    lock-step over ragged batches of up to batch_size rows.  `alpha` may be a sequence (the usual tuning sweep): the result
+    is then {alpha: predictions}, with the encoders and the cross-attention projections run once, not once per alpha."""
+    alphas, many = _alphas(alpha)
+    preds = _weighted_predict(pairs, img_model, audio_model, alphas, batch_size, sync_every)
+    return dict(zip(alphas, preds)) if many else preds[0]
+
+
+def weighted_evaluate(batches: Iterable, img_model, audio_model, alpha: Union[float, Sequence[float]] = 0.5, batch_size: int = 32):
+    """weighted_multimodal/test.py:154-172 over `batches` ((xi, xa, y) as the test loader yields them): compute_metrics of the
+    weighted predictions against the ytest_i2w-decoded targets (without <sos>); {alpha: metrics} for a sequence of alphas."""
+    _check_models(img_model, audio_model)
+    truth: List[List[str]] = []
+
+    def inputs():
+        for xi, xa, y in batches:
+            assert y.size(0) == 1, "weighted_evaluate takes the batches of the test loader (batch_size = 1)"
+            truth.append([img_model.ytest_i2w[i] for i in y[0][1:].tolist()])
+            yield xi, xa
+
+    alphas, many = _alphas(alpha)
+    preds = _weighted_predict(inputs(), img_model, audio_model, alphas, batch_size, 8)
+    metrics = [compute_metrics(y_true=truth, y_pred=p) for p in preds]
+    return dict(zip(alphas, metrics)) if many else metrics[0]
