@@ -367,6 +367,50 @@ int omr_weighted_decode_steps_varlen(const omr_decode_desc* desc_a, const int* m
                                      const int* mem_len_b, float alpha, long* tokens, int t0, int n_steps, long* out_tokens,
                                      float* out_prob, float* logits_a, float* logits_b, void* stream);
 
+/* ---- batched beam search on the device ------------------------------------------------------------------------------- */
+/* Beam search (BASELINE config 5 "beam-search decode"; an extension -- the reference only decodes greedily, model.py:182-193)
+ * for N inputs at once without a host round trip between positions.  The yardstick is the host loop of _Base.beam_search
+ * (model.py of this package): every input gets exactly its result.  Row r = n * beam + k of the decode descriptor
+ * (desc->B == N * beam) is hypothesis k of input n; the rows of an input share its cross-attention K|V (desc->cross_kv holds
+ * N slots, cross_bs apart) and its mem_len[n].  Row and parent indices below are LOCAL to the input (0 .. beam-1).
+ * State, all device memory, carved out of ONE block `state` of omr_beam_workspace_bytes bytes so that one copy brings the
+ * results to the host:
+ *   scores      fp64 [rows]   sum of log-probabilities of the hypothesis (-inf: dead row); before position 0: 0, -inf, ...
+ *   best_score  fp64 [N]      best finished hypothesis: its score (-inf: none yet), the row it extended (best_row) and the
+ *   best_row / best_pos [N]   position at which it took <eos>; its tokens are the history walked back from there, + <eos>
+ *   done [N]                  1: the input stopped (no survivor, or its best survivor cannot overtake best_score); frozen
+ *   exhausted [N]             1 until the input stops by that rule (it then did not run out of positions)
+ *   parents int32 [rows]      the row each row of the NEXT position continues (written by the selection, read by the reorder)
+ *   tokens int64 [rows]       the token each row feeds to the next position; before position 0: <sos>
+ *   hist_parent / hist_token int32 [max_len][rows]   (parent, token) of every row at every position run
+ * Scores are fp64 because the host route adds Python floats to the fp32 log-probabilities it reads back.
+ * self_kv2: a second self-attention cache, the size of desc->self_kv; position t lives in desc->self_kv for even t and in
+ * self_kv2 for odd t (a run starts at position 0).  last_logits (nullable): fp32 [rows][ldv] logits of the last position run. */
+#define OMR_MAX_BEAM 8
+typedef struct omr_beam_desc {
+    int beam, N, eos, max_len;
+    void* state; long state_bytes;
+    double* scores; double* best_score; long* tokens; int* best_row; int* best_pos; int* done; int* exhausted; int* parents;
+    int* hist_parent; int* hist_token;
+    void* self_kv2; float* last_logits;
+} omr_beam_desc;
+/* Bytes of the state block for desc->{beam, N, max_len}; also points the ten state fields into desc->state (NULL: offsets). */
+long omr_beam_workspace_bytes(omr_beam_desc* desc);
+/* The selection of ONE position `t` for all inputs in one launch (the loop body of _Base.beam_search, model.py of this package):
+ * per row the `beam` largest log_softmax values of logits [rows][ld] (omr_topk_logprob's arithmetic and tie rule); candidates
+ * scores[parent] + value in fp64 from live rows, ordered by (score descending, parent ascending, token ascending); walked in
+ * that order: the first `beam` non-<eos> candidates survive, an <eos> candidate before the beam-th survivor replaces the best
+ * finished record if its score is strictly greater; the input stops when nothing survives or its best survivor's score is
+ * <= the best finished one, else parents / tokens / scores / history row t are written (padded with dead copies of the first
+ * survivor).  Inputs already done are not touched. */
+int omr_beam_select(const float* logits, long ld, int V, const omr_beam_desc* beam_desc, int t, void* stream);
+/* Positions t0 .. t0+n_steps-1 for all rows from one host call: per position the decode step without a pick
+ * (omr_decode_steps' position, fp32 logits), omr_beam_select, and one launch that moves the still readable cache positions
+ * [max(0, t+1-window), t] of every layer and row from its parent's row into the other cache buffer.  mem_len (nullable): device
+ * int32 [N] as in omr_decode_steps_varlen.  Refused before the first launch: beam outside 1..OMR_MAX_BEAM, desc->B != N * beam,
+ * t0 + n_steps > max_len. */
+int omr_beam_decode_steps(const omr_decode_desc* desc, const omr_beam_desc* beam_desc, const int* mem_len, int t0, int n_steps, void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------------------------ */
 /* CrossEntropyLoss(ignore_index=pad) (model.py:109,166) on row-major logits [M][ldv]; acc2 = {sum, count} (fp64). */
 int omr_ce_fwd(int dtype, const void* logits, const long* target, float* lse, double* acc2, float* loss_out, long M, int V, long ldv,

@@ -33,6 +33,7 @@ struct AttnArgs {
                                                        // separate __restrict__ parameter so that its loads become scalar loads
     // single-query-block forward split over the keys (decode): blockIdx.x = split, partials [B][H][nsplit][T][HD + 2] floats
     int nsplit, split_len; float* part;
+    int kv_group;                                      // key-split forward: batch row b reads the K|V (and kv_len) of slot b / kv_group
     // backward only
     const void* dout; long lddo, bsdo;
     const float* delta;                                // [B][H][T]
@@ -264,10 +265,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint
     const int q = qw0 + (lane & 31);
     const int kboff = SPLITW ? wave * BKV : 0;                  // this wave's keys inside the staged block
     const T* Q = (const T*)a.q + (long)b * a.bsq + h * HD;
-    const T* K = (const T*)a.k + (long)b * a.bsk + h * HD;
-    const T* V = (const T*)a.v + (long)b * a.bsv + h * HD;
+    const int bk = SPLITW ? b / a.kv_group : b;                 // K|V slot of this row (beam search: the hypotheses of an input share one)
+    const T* K = (const T*)a.k + (long)bk * a.bsk + h * HD;
+    const T* V = (const T*)a.v + (long)bk * a.bsv + h * HD;
     int S = a.S;                                                // this row's key count (never past the padded S; <= 0: no keys)
-    if constexpr (SPLITW) { if (kv_len) S = min(kv_len[b], a.S); }
+    if constexpr (SPLITW) { if (kv_len) S = min(kv_len[bk], a.S); }
 
     const float sc2 = a.scale * LOG2E;
     F qf[NKS];                                                  // Q * scale * log2 e
@@ -1162,7 +1164,7 @@ static int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v,
                          long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim, int causal, int window,
                          const float* key_bias, const int* blk_lq, const int* blk_lkv, float dropout_p, unsigned long long seed,
                          const unsigned long long* drop_words, float* split_ws, long split_ws_floats, void* stream, int* nsplit_out = nullptr,
-                         const int* kv_len = nullptr);
+                         const int* kv_len = nullptr, int kv_group = 1);
 
 /* omr_attn_fwd with caller-provided scratch for the key split (omr_attn_workspace_floats(..., backward = 0) floats) */
 extern "C" int omr_attn_fwd_ws(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv, long ldo,
@@ -1202,7 +1204,7 @@ static int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v,
                          long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim, int causal, int window,
                          const float* key_bias, const int* blk_lq, const int* blk_lkv, float dropout_p, unsigned long long seed,
                          const unsigned long long* drop_words, float* split_ws, long split_ws_floats, void* stream, int* nsplit_out,
-                         const int* kv_len) {
+                         const int* kv_len, int kv_group) {
     AttnArgs a = {};
     int rc = fill_common(a, B, H, T, S, head_dim, dropout_p, seed, causal, window, key_bias, blk_lq, blk_lkv, drop_words, true);
     if (rc) return rc;
@@ -1210,7 +1212,8 @@ static int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v,
     if (ldq % vec || ldk % vec || ldv % vec || ldo % 4) return OMR_ERR_ARG;
     a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.bsq = bsq; a.bsk = bsk; a.bsv = bsv; a.bso = bso;
-    a.nsplit = 1; a.split_len = 0; a.part = nullptr;
+    a.nsplit = 1; a.split_len = 0; a.part = nullptr; a.kv_group = kv_group;
+    if (kv_group < 1 || B % kv_group) return OMR_ERR_ARG;
     if (split_ws) {
         int nsplit, len;
         choose_split(B, H, T, S, causal, &nsplit, &len);
@@ -1220,7 +1223,7 @@ static int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v,
         }
     }
     // per-row key counts exist only in the key-split decode kernel: a shape that would not take it is refused, not run unmasked
-    if (kv_len && !(T <= 32 && S > 64 && a.drop_thresh == 0 && !causal && !blk_lq)) return OMR_ERR_UNSUPPORTED;
+    if ((kv_len || kv_group != 1) && !(T <= 32 && S > 64 && a.drop_thresh == 0 && !causal && !blk_lq)) return OMR_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const bool merge = nsplit_out == nullptr;           // a caller that asks for the split count merges the partials itself
     if (nsplit_out) *nsplit_out = (T <= 32 && S > 64) ? a.nsplit : 1;
@@ -1251,13 +1254,14 @@ extern "C" int omr_attn_fwd_split_varlen(int dtype, const void* q, const void* k
                          nullptr, split_ws, split_ws_floats, stream, nullptr, kv_len);
 }
 
-/* omr_attn_fwd_split_partials with per-row key counts, for the ragged decode executor (decode.hip).  A C++ symbol, not part of the C ABI */
+/* omr_attn_fwd_split_partials with per-row key counts and shared K|V slots (omr_common.h), for the decode executors (decode.hip).
+ * A C++ symbol, not part of the C ABI */
 int attn_fwd_split_partials_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
                                    long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
-                                   const int* kv_len, float* split_ws, long split_ws_floats, int* nsplit, void* stream) {
-    if (T > 32 || !nsplit) return OMR_ERR_ARG;
+                                   const int* kv_len, float* split_ws, long split_ws_floats, int* nsplit, void* stream, int kv_group) {
+    if (T > 32) return OMR_ERR_ARG;
     return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, nullptr, nullptr, nullptr, 0.f, 0,
-                         nullptr, split_ws, split_ws_floats, stream, nsplit, kv_len);
+                         nullptr, split_ws, split_ws_floats, stream, nsplit, kv_len, kv_group);
 }
 
 extern "C" int omr_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,

@@ -293,9 +293,12 @@ extern "C" long omr_decode_workspace_bytes(const omr_decode_desc* d) {
     return (long)carve(*d, nullptr, nullptr);
 }
 
-// mem_len (nullable, device int32 [B]): row b's cross-attention sees the first mem_len[b] of the d.S memory rows (ragged batch)
+// mem_len (nullable, device int32 [B / kv_group]): row b's cross-attention sees the first mem_len[b / kv_group] of the d.S memory
+// rows (ragged batch).  kv_group: that many consecutive rows share one cross-attention K|V slot (the hypotheses of one input of
+// a batched beam search); 1 everywhere else.  logits_at (nullable): where the last position's fp32 logits [B][ldv] lie in the
+// workspace, for a caller that consumes them in place.
 static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tokens, int t0, int n_steps, long* out_tokens, float* out_top1,
-                        float* last_logits, void* stream) {
+                        float* last_logits, void* stream, int kv_group = 1, float** logits_at = nullptr) {
     if (!dp || !tokens || n_steps < 1 || t0 < 0) return OMR_ERR_ARG;
     const omr_decode_desc& d = *dp;
     if (d.B <= 0 || d.L <= 0 || d.d <= 0 || d.d % d.nhead || d.V <= 0 || d.ldv < d.V || d.ldv % 8) return OMR_ERR_ARG;
@@ -366,7 +369,7 @@ static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tok
                 { char* tsw = xa; xa = xb; xb = tsw; }
                 const char* ck = (const char*)d.cross_kv + (size_t)l * 2 * dm * es;
                 TRY(attn_fwd_split_partials_varlen(dt, w.q, ck, ck + (size_t)dm * es, w.o, w.lse, dm, d.cross_ld, d.cross_ld, dm, dm, d.cross_bs, d.cross_bs,
-                                                   dm, B, d.nhead, 1, d.S, hd, mem_len, w.split, w.split_floats, &ns, stream));
+                                                   dm, B, d.nhead, 1, d.S, hd, mem_len, w.split, w.split_floats, &ns, stream, kv_group));
                 TRY(lin(ns > 1 ? 3 : 0, w.o, nullptr, nullptr, nullptr, nullptr, w.split, ns, Wl[8], (const float*)Wl[9], dm, dm, 0, w.proj, dm, dm, nullptr, 0, nullptr, nullptr, nullptr, W8l ? W8l[3] : nullptr, S8l ? S8l[3] : nullptr));
                 // feed-forward from norm2(x + cross-attention)
                 TRY(lin(1, w.proj, xa, (const float*)Wl[10], (const float*)Wl[11], xb, nullptr, 0, Wl[12], (const float*)Wl[13], d.ff, dm, 1, w.h, d.ff, d.ff, nullptr, 0, nullptr, nullptr, nullptr, W8l ? W8l[4] : nullptr, S8l ? S8l[4] : nullptr));
@@ -386,6 +389,7 @@ static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tok
             return OMR_ERR_LAUNCH;
         if (last_logits && hipMemcpyAsync(last_logits, w.logits32, (size_t)B * d.ldv * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
             return OMR_ERR_LAUNCH;
+        if (logits_at) *logits_at = w.logits32;
         return OMR_OK;
     }
     // ---- model widths the row kernel does not take: one GEMM / element-wise kernel per step of the layer (fp8 mode: activations
@@ -410,8 +414,12 @@ static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tok
             // cross-attention over the memory K|V projected once (init): layer l's block of the [B][S][L*2d] buffer
             TRY(gemm(w.x, dm, 6, (const float*)W[7], w.q, dm, dm, dm, 0, 2, 0));
             const char* ck = (const char*)d.cross_kv + (size_t)l * 2 * dm * es;
-            TRY(omr_attn_fwd_split_varlen(dt, w.q, ck, ck + (size_t)dm * es, w.o, w.lse, dm, d.cross_ld, d.cross_ld, dm, dm, d.cross_bs, d.cross_bs, dm,
-                                          B, d.nhead, 1, d.S, hd, nullptr, mem_len, w.split, w.split_floats, stream));
+            if (kv_group == 1)
+                TRY(omr_attn_fwd_split_varlen(dt, w.q, ck, ck + (size_t)dm * es, w.o, w.lse, dm, d.cross_ld, d.cross_ld, dm, dm, d.cross_bs, d.cross_bs, dm,
+                                              B, d.nhead, 1, d.S, hd, nullptr, mem_len, w.split, w.split_floats, stream));
+            else        // shared K|V slots exist in the key-split kernel only (S > 64); the partials are merged there
+                TRY(attn_fwd_split_partials_varlen(dt, w.q, ck, ck + (size_t)dm * es, w.o, w.lse, dm, d.cross_ld, d.cross_ld, dm, dm, d.cross_bs, d.cross_bs,
+                                                   dm, B, d.nhead, 1, d.S, hd, mem_len, w.split, w.split_floats, nullptr, stream, kv_group));
             TRY(gemm(w.o, dm, 8, (const float*)W[9], w.proj, dm, dm, dm, 0, 3, 0));
             TRY(omr_add_layernorm_fwd(dt, w.proj, w.x, (const float*)W[10], (const float*)W[11], w.x, w.mean, w.rstd, B, dm, 1e-5f, 0.f, 0, stream));
             // feed-forward
@@ -439,6 +447,7 @@ static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tok
             if (hipMemcpyAsync(last_logits, l32, (size_t)B * d.ldv * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
                 return OMR_ERR_LAUNCH;
         }
+        if (logits_at) *logits_at = l32;
     }
     return OMR_OK;
 }
@@ -482,4 +491,170 @@ extern "C" int omr_weighted_decode_steps(const omr_decode_desc* da, const omr_de
                                          long* out_tokens, float* out_prob, float* logits_a, float* logits_b, void* stream) {
     if (!da || !db || da->B != 1 || db->B != 1) return OMR_ERR_ARG;
     return omr_weighted_decode_steps_varlen(da, nullptr, db, nullptr, alpha, tokens, t0, n_steps, out_tokens, out_prob, logits_a, logits_b, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Batched beam search on the device (include/omr_hip.h "batched beam search").  The host loop it reproduces is
+// _Base.beam_search of this package's model.py; the three pieces per position are decode_steps without a pick, the selection
+// kernel and the cache reorder below.
+namespace {
+
+constexpr int BEAM_GROUPS = 4;         // rows of an input ranked side by side: one 256-thread group each
+
+// One workgroup per input.  Phase 1: the top `beam` log-probabilities of each of its rows (topk_logprob_row, the row body of
+// omr_topk_logprob).  Phase 2, wave 0, one candidate per lane (beam * beam <= 64): rank by all-pairs comparison, then the host
+// loop's walk over the sorted candidates as ballots.
+__global__ __launch_bounds__(256 * BEAM_GROUPS) void beam_select_kernel(const float* __restrict__ logits, long ld, int V, omr_beam_desc bd, int t) {
+    __shared__ float sv[BEAM_GROUPS][256];
+    __shared__ int si[BEAM_GROUPS][256];
+    __shared__ float c_val[64];
+    __shared__ int c_tok[64];
+    __shared__ double u_sc[64], o_sc[64];          // candidates as found / in order
+    __shared__ int u_live[64], o_tok[64], o_par[64], o_ok[64];
+    const int n = blockIdx.x, beam = bd.beam, row0 = n * beam;
+    if (bd.done[n]) return;                         // frozen (uniform over the workgroup)
+    const int g = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = threadIdx.x;
+    for (int k0 = 0; k0 < beam; k0 += BEAM_GROUPS) {
+        const int k = k0 + g;
+        const bool real = k < beam;                 // a group without a row walks an empty one: the barriers stay uniform
+        topk_logprob_row(logits + (long)(row0 + (real ? k : 0)) * ld, real ? V : 0, beam, tid, sv[g], si[g], [&](int j, int idx, float val) {
+            if (tid == 0 && real) { c_tok[k * beam + j] = idx; c_val[k * beam + j] = val; }
+        });
+    }
+    __syncthreads();
+    const int nc = beam * beam;
+    double sc = 0.0; int par = 0, tok = 0; bool live = false;
+    if (lane < 64) {
+        o_ok[lane] = 0;
+        if (lane < nc) {
+            par = lane / beam; tok = c_tok[lane];
+            const double ps = bd.scores[row0 + par];
+            live = ps > -INFINITY;                  // dead rows contribute no candidates
+            sc = ps + (double)c_val[lane];
+        }
+        u_sc[lane] = sc; u_live[lane] = live;
+    }
+    __syncthreads();
+    if (lane < 64 && live) {                        // (score descending, parent ascending, token ascending); lane = parent * beam + j
+        int rank = 0;
+        for (int c = 0; c < nc; ++c) {
+            if (!u_live[c] || c == lane) continue;
+            const double s2 = u_sc[c]; const int p2 = c / beam, t2 = c_tok[c];
+            if (s2 > sc || (s2 == sc && (p2 < par || (p2 == par && t2 < tok)))) ++rank;
+        }
+        o_sc[rank] = sc; o_tok[rank] = tok; o_par[rank] = par; o_ok[rank] = 1;
+    }
+    __syncthreads();
+    if (lane >= 64) return;
+    const bool ok = o_ok[lane] != 0;
+    sc = o_sc[lane]; tok = o_tok[lane]; par = o_par[lane];
+    const bool is_eos = ok && tok == bd.eos, alive = ok && !is_eos;
+    const unsigned long long live_mask = __ballot(alive);
+    const int before = __popcll(live_mask & ((1ull << lane) - 1ull));       // non-<eos> candidates ahead of this one
+    const bool surv = alive && before < beam;
+    const unsigned long long eos_mask = __ballot(is_eos && before < beam);    // the host loop breaks after the beam-th survivor
+    double best = bd.best_score[n];
+    if (eos_mask) {                                 // the first <eos> in the order has the largest score of them
+        const int fl = __ffsll(eos_mask) - 1;
+        const double es = o_sc[fl];
+        if (es > best) {
+            best = es;
+            if (lane == 0) { bd.best_score[n] = es; bd.best_row[n] = o_par[fl]; bd.best_pos[n] = t; }
+        }
+    }
+    const int first = live_mask ? __ffsll(live_mask) - 1 : 0;
+    if (!live_mask || o_sc[first] <= best) {        // nothing survives, or no survivor can overtake the best finished hypothesis
+        if (lane == 0) { bd.done[n] = 1; bd.exhausted[n] = 0; }
+        return;
+    }
+    const int nsurv = min(__popcll(live_mask), beam);
+    const long hrow = (long)t * bd.N * beam;
+    auto put = [&](int slot, int p_out, int t_out, double s_out) {
+        const int r = row0 + slot;
+        bd.parents[r] = p_out; bd.tokens[r] = t_out; bd.scores[r] = s_out;
+        bd.hist_parent[hrow + r] = p_out; bd.hist_token[hrow + r] = t_out;
+    };
+    if (surv) put(before, par, tok, sc);
+    if (lane >= nsurv && lane < beam) put(lane, o_par[first], o_tok[first], -INFINITY);      // dead padding rows: copies of the first survivor
+}
+
+// Cache reorder: new row i of an input continues row parents[i] of it.  Positions [lo, t] of every layer and row move from the
+// cache that holds position t to the one position t + 1 will be written into, 16 bytes per lane and access; nothing beyond t is
+// touched.  grid = (chunks of 1024 vectors, rows, L).  Inputs that are done are left where they are: their rows keep running on
+// stale cache contents, and nothing they produce is read.
+__global__ __launch_bounds__(256) void beam_reorder_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, const int* __restrict__ parents,
+                                                           const int* __restrict__ done, int beam, int rows, long row_vecs, long off_vecs, long nvec) {
+    const int r = blockIdx.y, n = r / beam;
+    if (done[n]) return;
+    const int p = min(max(parents[r], 0), beam - 1);
+    const uint4* s = src + ((long)blockIdx.z * rows + n * beam + p) * row_vecs + off_vecs;
+    uint4* d = dst + ((long)blockIdx.z * rows + r) * row_vecs + off_vecs;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const long i = (long)blockIdx.x * 1024 + u * 256 + threadIdx.x;
+        if (i < nvec) d[i] = s[i];
+    }
+}
+
+size_t beam_carve(omr_beam_desc* b) {
+    const size_t rows = (size_t)b->N * b->beam, N = (size_t)b->N, hist = (size_t)b->max_len * rows;
+    char* base = (char*)b->state;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base + off; off += align256(bytes); return p; };
+    b->scores = (double*)take(rows * 8); b->best_score = (double*)take(N * 8); b->tokens = (long*)take(rows * 8);
+    b->best_row = (int*)take(N * 4); b->best_pos = (int*)take(N * 4); b->done = (int*)take(N * 4); b->exhausted = (int*)take(N * 4);
+    b->parents = (int*)take(rows * 4); b->hist_parent = (int*)take(hist * 4); b->hist_token = (int*)take(hist * 4);
+    return off;
+}
+
+bool beam_desc_ok(const omr_beam_desc& b) {
+    if (b.beam < 1 || b.beam > OMR_MAX_BEAM || b.N < 1 || b.max_len < 1 || !b.state) return false;
+    omr_beam_desc c = b;
+    if ((long)beam_carve(&c) > b.state_bytes) return false;
+    return c.scores == b.scores && c.best_score == b.best_score && c.tokens == b.tokens && c.best_row == b.best_row && c.best_pos == b.best_pos &&
+           c.done == b.done && c.exhausted == b.exhausted && c.parents == b.parents && c.hist_parent == b.hist_parent && c.hist_token == b.hist_token;
+}
+
+}  // namespace
+
+extern "C" long omr_beam_workspace_bytes(omr_beam_desc* b) {
+    if (!b || b->beam < 1 || b->beam > OMR_MAX_BEAM || b->N < 1 || b->max_len < 1) return OMR_ERR_ARG;
+    return (long)beam_carve(b);
+}
+
+extern "C" int omr_beam_select(const float* logits, long ld, int V, const omr_beam_desc* bp, int t, void* stream) {
+    if (!logits || !bp || !beam_desc_ok(*bp)) return OMR_ERR_ARG;
+    if (V < bp->beam || ld < V || t < 0 || t >= bp->max_len || bp->eos < 0 || bp->eos >= V) return OMR_ERR_ARG;
+    hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)bp->N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, logits, ld, V, *bp, t);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+extern "C" int omr_beam_decode_steps(const omr_decode_desc* dp, const omr_beam_desc* bp, const int* mem_len, int t0, int n_steps, void* stream) {
+    if (!dp || !bp || n_steps < 1 || t0 < 0) return OMR_ERR_ARG;
+    if (bp->beam < 1 || bp->beam > OMR_MAX_BEAM || bp->N < 1 || (long)dp->B != (long)bp->N * bp->beam) return OMR_ERR_ARG;
+    if (t0 + n_steps > dp->max_len || bp->max_len != dp->max_len) return OMR_ERR_ARG;      // refuse before the first launch
+    if (!beam_desc_ok(*bp) || !bp->self_kv2 || !dp->self_kv || dp->V < bp->beam || bp->eos < 0 || bp->eos >= dp->V) return OMR_ERR_ARG;
+    const size_t es = dp->dtype == OMR_BF16 ? 2 : 4;
+    const size_t pos_bytes = (size_t)2 * dp->d * es;                          // K|V of one (layer, row, position)
+    if (pos_bytes % 16 || ((uintptr_t)dp->self_kv & 15) || ((uintptr_t)bp->self_kv2 & 15)) return OMR_ERR_ARG;
+    omr_decode_desc d = *dp;                                                   // own copy: the cache pointer alternates per position
+    for (int s = 0; s < n_steps; ++s) {
+        const int t = t0 + s;
+        void* cur = (t & 1) ? bp->self_kv2 : dp->self_kv;
+        void* nxt = (t & 1) ? dp->self_kv : bp->self_kv2;
+        d.self_kv = cur;
+        float* l32 = nullptr;
+        TRY(decode_steps(&d, mem_len, bp->tokens, t, 1, nullptr, nullptr, s == n_steps - 1 ? bp->last_logits : nullptr, stream, bp->beam, &l32));
+        hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)bp->N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, l32, (long)d.ldv, d.V, *bp, t);
+        if (t + 1 < d.max_len) {                                               // position t + 1 reads keys [lo, t + 1] (decode_steps' band)
+            const int lo = (d.window > 0 && t + 1 - d.window > 0) ? t + 1 - d.window : 0;
+            const long nvec = (long)(t + 1 - lo) * (long)(pos_bytes / 16);
+            const dim3 grid((unsigned)cdiv(nvec, 1024), (unsigned)d.B, (unsigned)d.L);
+            hipLaunchKernelGGL(beam_reorder_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)cur, (uint4*)nxt, bp->parents, bp->done,
+                               bp->beam, d.B, (long)d.max_len * (long)(pos_bytes / 16), (long)lo * (long)(pos_bytes / 16), nvec);
+        }
+        OMR_CHECK_LAUNCH();
+    }
+    return OMR_OK;
 }

@@ -255,43 +255,12 @@ __global__ void weighted_argmax_kernel(const float* __restrict__ la0, long lda, 
 __global__ void topk_logprob_kernel(const float* __restrict__ x0, int n, long ld, int k, long* __restrict__ idx_out, float* __restrict__ val_out) {
     __shared__ float sv[256];
     __shared__ int si[256];
-    const float* x = x0 + (long)blockIdx.x * ld;
     const int tid = threadIdx.x;
-    float mx = -INFINITY;
-    for (int i = tid; i < n; i += 256) mx = fmaxf(mx, x[i]);
-    sv[tid] = mx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) sv[tid] = fmaxf(sv[tid], sv[tid + o]); __syncthreads(); }
-    mx = sv[0];
-    __syncthreads();
-    float se = 0.f;
-    for (int i = tid; i < n; i += 256) se += expf(x[i] - mx);
-    sv[tid] = se;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) sv[tid] += sv[tid + o]; __syncthreads(); }
-    const float lse = mx + logf(sv[0]);
-    __syncthreads();
-    float last_v = INFINITY; int last_i = -1;
-    for (int j = 0; j < k; ++j) {
-        float best = -INFINITY; int bi = 0x7fffffff;
-        for (int i = tid; i < n; i += 256) {
-            const float v = x[i];
-            const bool cand = v < last_v || (v == last_v && i > last_i);
-            if (cand && (v > best || (v == best && i < bi))) { best = v; bi = i; }
-        }
-        sv[tid] = best; si[tid] = bi;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) {
-                const float v2 = sv[tid + o]; const int i2 = si[tid + o];
-                if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
-            }
-            __syncthreads();
-        }
-        last_v = sv[0]; last_i = si[0];
-        if (tid == 0) { idx_out[(long)blockIdx.x * k + j] = last_i; val_out[(long)blockIdx.x * k + j] = last_v - lse; }
-        __syncthreads();
-    }
+    long* io = idx_out + (long)blockIdx.x * k;
+    float* vo = val_out + (long)blockIdx.x * k;
+    topk_logprob_row(x0 + (long)blockIdx.x * ld, n, k, tid, sv, si, [&](int j, int idx, float val) {
+        if (tid == 0) { io[j] = idx; vo[j] = val; }
+    });
 }
 
 // ---------------------------------------------------------------- log-STFT post-processing (audio front end)

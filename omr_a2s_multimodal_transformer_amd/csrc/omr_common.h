@@ -134,7 +134,54 @@ __device__ __forceinline__ bool drop_keep(uint64_t seed, uint64_t idx, uint32_t 
 
 __host__ __device__ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-// attention.hip -> decode.hip: omr_attn_fwd_split_partials with per-row key counts kv_len[B] (omr_attn_fwd_split_varlen's rule)
+// attention.hip -> decode.hip: omr_attn_fwd_split_partials with per-row key counts (omr_attn_fwd_split_varlen's rule).  nsplit == NULL:
+// the partials are merged here (omr_attn_fwd_split_varlen).  kv_group (>= 1): batch row b reads the K|V of slot b / kv_group and
+// kv_len[b / kv_group] -- the `beam` hypotheses of one input share that input's memory K|V (beam search over a batch).
 int attn_fwd_split_partials_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
                                    long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
-                                   const int* kv_len, float* split_ws, long split_ws_floats, int* nsplit, void* stream);
+                                   const int* kv_len, float* split_ws, long split_ws_floats, int* nsplit, void* stream, int kv_group = 1);
+
+// Top-k log-probabilities of ONE row by a group of 256 threads (tid 0..255; every thread of the WORKGROUP must call it: it
+// synchronises with __syncthreads): emit(j, index, log_softmax(x)[index]) for the j-th largest, j < k, ties towards the smaller
+// index, with the same values in every thread.  A max / sum-exp pass, then k selection passes over the candidates that come
+// after the previous pick in (value descending, index ascending) order.  sv / si: 256 entries of LDS each, the group's own.
+// One definition for topk_logprob_kernel (elementwise.hip) and the beam selection (decode.hip): the on-device beam search has
+// to rank the very floats the host route reads back.
+template <typename Emit>
+__device__ __forceinline__ void topk_logprob_row(const float* __restrict__ x, int n, int k, int tid, float* sv, int* si, Emit emit) {
+    float mx = -INFINITY;
+    for (int i = tid; i < n; i += 256) mx = fmaxf(mx, x[i]);
+    sv[tid] = mx;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if (tid < o) sv[tid] = fmaxf(sv[tid], sv[tid + o]); __syncthreads(); }
+    mx = sv[0];
+    __syncthreads();
+    float se = 0.f;
+    for (int i = tid; i < n; i += 256) se += expf(x[i] - mx);
+    sv[tid] = se;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if (tid < o) sv[tid] += sv[tid + o]; __syncthreads(); }
+    const float lse = mx + logf(sv[0]);
+    __syncthreads();
+    float last_v = INFINITY; int last_i = -1;
+    for (int j = 0; j < k; ++j) {
+        float best = -INFINITY; int bi = 0x7fffffff;
+        for (int i = tid; i < n; i += 256) {
+            const float v = x[i];
+            const bool cand = v < last_v || (v == last_v && i > last_i);
+            if (cand && (v > best || (v == best && i < bi))) { best = v; bi = i; }
+        }
+        sv[tid] = best; si[tid] = bi;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (tid < o) {
+                const float v2 = sv[tid + o]; const int i2 = si[tid + o];
+                if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
+            }
+            __syncthreads();
+        }
+        last_v = sv[0]; last_i = si[0];
+        emit(j, last_i, last_v - lse);
+        __syncthreads();
+    }
+}

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -281,6 +281,23 @@ class Decoder(nn.Module):
         return DecodeState(self, as_dt(memory), dt)
 
     @torch.no_grad()
+    def init_beam_decode(self, memory, beam: int, sos: int = 2, eos: int = 1) -> "BeamDecodeState":
+        """The state of a beam search over N inputs at once, `beam` hypotheses each (omr_beam_decode_steps).  memory: [1, S, d],
+        or a list of memories [S_b, d] / [1, S_b, d] of different lengths; each is projected by the GEMM a batch-size-1 state
+        of it runs, and its hypotheses share that K|V.  sos / eos: the token ids (defaults: the id layout of the reference's
+        vocabularies with 3 special tokens, synthetic.make_vocab).  The limits of a ragged state apply (check_ragged_memories)."""
+        if not 1 <= beam <= MAX_BEAM:
+            raise ValueError(f"beam must be in 1..{MAX_BEAM}, got {beam}")
+        if beam > self.output_size or not (0 <= sos < self.output_size and 0 <= eos < self.output_size):
+            raise ValueError(f"beam decode: beam {beam}, sos {sos}, eos {eos} do not fit a vocabulary of {self.output_size}")
+        emb_w = self.embedding.weight
+        dt = torch.bfloat16 if getattr(emb_w, "omr_lowp", None) is not None else torch.float32
+        mems = list(memory) if isinstance(memory, (list, tuple)) else [memory]
+        mems = [m[0] if m.dim() == 3 else m for m in mems]
+        check_ragged_memories([m.shape for m in mems], emb_w.shape[1])
+        return BeamDecodeState(self, [K.cast(m.contiguous(), dt) if m.dtype != dt else m.contiguous() for m in mems], dt, beam, sos, eos)
+
+    @torch.no_grad()
     def decode_step(self, token: torch.Tensor, st: "DecodeState") -> torch.Tensor:
         """token int64 [B,1] -> fp32 logits of the next position ([V] for B = 1, else [B,V]); advances the cache.  Every
         sample of the batch is at the same position t; rows are computed independently (same per-row arithmetic as bs = 1)."""
@@ -333,6 +350,7 @@ class Decoder(nn.Module):
 # 64 keys per row (a shorter memory alone takes the query-per-wave kernel).  Python routes the short rows to batch size 1.
 MAX_RAGGED_MEMORY = 64 * 256
 MIN_RAGGED_MEMORY = 64
+MAX_BEAM = 8                 # OMR_MAX_BEAM: beam * beam candidates of an input are one wavefront of the selection kernel
 
 
 def check_ragged_memories(shapes, d: int) -> None:
@@ -500,3 +518,97 @@ class DecodeState:
         self._steps(self.t, n_steps, toks, top1, None)
         self.t += n_steps
         return toks, top1
+
+
+class _BeamDesc(ctypes.Structure):
+    """omr_beam_desc of include/omr_hip.h."""
+    STATE_FIELDS = ("scores", "best_score", "tokens", "best_row", "best_pos", "done", "exhausted", "parents", "hist_parent", "hist_token")
+    _fields_ = [(n, ctypes.c_int) for n in ("beam", "N", "eos", "max_len")] + [("state", ctypes.c_void_p), ("state_bytes", ctypes.c_long)] + [
+        (n, ctypes.c_void_p) for n in STATE_FIELDS + ("self_kv2", "last_logits")]
+
+
+class BeamDecodeState(DecodeState):
+    """Device state of a beam search over N inputs at once (csrc/decode.hip, omr_beam_decode_steps): a ragged decode state of
+    N memories whose B = N * beam rows are the hypotheses (row n * beam + k: hypothesis k of input n; the rows of an input read
+    its one cross-attention K|V slot), two self-attention caches that alternate per position, and the search state
+    (include/omr_hip.h) in one device block.  run(n) issues n positions from one host call; results() reads the block back
+    once and walks the history tables on the host (evaluation.beam_results)."""
+
+    def __init__(self, dec: "Decoder", mems, dt: torch.dtype, beam: int, sos: int, eos: int):
+        self.beam, self.sos, self.eos = beam, sos, eos     # before the base constructor: _bind sizes the rows by the beam
+        super().__init__(dec, mems, dt)
+
+    def _bind(self) -> None:
+        if not hasattr(self, "N"):                         # first call, from DecodeState.__init__: B is still the number of memories
+            self.N, self.B = self.B, self.B * self.beam
+            dev = self.cross_kv.device
+            self.self_kv = torch.empty((self.L, self.B, self.max_len, 2 * self.d), dtype=self.dtype, device=dev)
+            self.self_kv2 = torch.empty_like(self.self_kv)
+        super()._bind()
+        import numpy as np
+        bd = self.bdesc = _BeamDesc()
+        bd.beam, bd.N, bd.max_len = self.beam, self.N, self.max_len
+        bd.eos, sos = self.eos, self.sos
+        bd.state = None
+        nbytes = lib().query("omr_beam_workspace_bytes", ctypes.byref(bd))
+        if nbytes <= 0:
+            raise RuntimeError("libomr_hip: omr_beam_workspace_bytes rejected the beam descriptor")
+        self._off = {n: int(getattr(bd, n) or 0) for n in _BeamDesc.STATE_FIELDS}      # state == NULL: the fields are offsets
+        host = np.zeros(nbytes, dtype=np.uint8)
+        rows = self.B
+        self._view(host, "scores", np.float64, rows)[:] = ([0.0] + [float("-inf")] * (self.beam - 1)) * self.N
+        self._view(host, "best_score", np.float64, self.N)[:] = float("-inf")
+        self._view(host, "tokens", np.int64, rows)[:] = sos
+        self._view(host, "exhausted", np.int32, self.N)[:] = 1
+        self.state = torch.from_numpy(host).to(self.self_kv.device)
+        bd.state, bd.state_bytes = self.state.data_ptr(), nbytes
+        if lib().query("omr_beam_workspace_bytes", ctypes.byref(bd)) != nbytes:
+            raise RuntimeError("libomr_hip: omr_beam_workspace_bytes changed its answer")
+        bd.self_kv2, bd.last_logits = self.self_kv2.data_ptr(), self.logits.data_ptr()
+
+    def _view(self, host, name: str, dtype, count: int):
+        import numpy as np
+        off = self._off[name]
+        return host[off:off + count * np.dtype(dtype).itemsize].view(dtype)
+
+    def share_memory_between(self, rows: int) -> None:
+        raise RuntimeError("share_memory_between: a beam decode state already shares each memory between its hypotheses")
+
+    def run(self, n_steps: int) -> None:                   # noqa: D401 -- positions t .. t + n_steps - 1, nothing returned
+        """Run n_steps positions of every input (decode step, selection, cache reorder) without a host round trip."""
+        if n_steps < 1 or self.t + n_steps > self.max_len:
+            raise RuntimeError("beam decode beyond max_seq_len (positional-encoding table exhausted)")
+        lib().call("omr_beam_decode_steps", ctypes.byref(self.desc), ctypes.byref(self.bdesc), ptr(self.mem_len), self.t, n_steps, cur_stream())
+        self.t += n_steps
+
+    def _device_ints(self, name: str, count: int) -> torch.Tensor:
+        off = self._off[name]
+        return self.state[off:off + 4 * count].view(torch.int32)
+
+    def done(self) -> List[bool]:
+        """The `done` flag of every input (one small device-to-host copy)."""
+        return [bool(v) for v in self._device_ints("done", self.N).cpu().tolist()]
+
+    def parents(self) -> torch.Tensor:
+        """int32 [N, beam], on the device: the LOCAL row each row of the next position continues (of the last position run)."""
+        return self._device_ints("parents", self.B).view(self.N, self.beam)
+
+    def snapshot(self) -> dict:
+        """One device-to-host copy of the whole search state -> {field: numpy array} (history tables [max_len, rows])."""
+        import numpy as np
+        host = self.state.cpu().numpy()
+        rows, N = self.B, self.N
+        out = {"scores": self._view(host, "scores", np.float64, rows), "best_score": self._view(host, "best_score", np.float64, N),
+               "tokens": self._view(host, "tokens", np.int64, rows), "parents": self._view(host, "parents", np.int32, rows)}
+        for n in ("best_row", "best_pos", "done", "exhausted"):
+            out[n] = self._view(host, n, np.int32, N)
+        for n in ("hist_parent", "hist_token"):
+            out[n] = self._view(host, n, np.int32, self.max_len * rows).reshape(self.max_len, rows)
+        return out
+
+    def results(self):
+        """-> [(token ids, score)] per input, what _Base.beam_search finds for that input alone (evaluation.beam_results)."""
+        from .evaluation import beam_results
+        s = self.snapshot()
+        return beam_results(self.beam, self.t, int(self.bdesc.eos), s["scores"], s["best_score"], s["best_row"], s["best_pos"], s["done"],
+                            s["hist_parent"], s["hist_token"])

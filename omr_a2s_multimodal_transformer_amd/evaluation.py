@@ -56,3 +56,37 @@ def plan_pair_groups(len_a: Sequence[int], len_b: Sequence[int], batch_size: int
         rest = sorted((i for i in idx if ragged(i)), key=lambda i: (-(len_a[i] + len_b[i]), i))
         groups += [rest[g:g + batch_size] for g in range(0, len(rest), batch_size)]
     return singles, groups
+
+
+def beam_backtrack(hist_parent, hist_token, row: int, position: int) -> List[int]:
+    """The tokens of the hypothesis that sat in row `row` of ONE input after `position` positions of a beam search, from that
+    input's history tables: hist_parent[p][r] is the row (of position p - 1) that row r of position p continued, hist_token[p][r]
+    the token it took.  position 0: the empty prefix."""
+    out: List[int] = []
+    for p in range(position - 1, -1, -1):
+        out.append(int(hist_token[p][row]))
+        row = int(hist_parent[p][row])
+    return out[::-1]
+
+
+def beam_results(beam: int, positions: int, eos: int, scores, best_score, best_row, best_pos, done, hist_parent,
+                 hist_token) -> List[Tuple[List[int], float]]:
+    """(token ids, score) of every input of a batched beam search from its device state read back (BeamDecodeState.snapshot;
+    rows n * beam .. n * beam + beam - 1 belong to input n), after `positions` positions.  The finished hypothesis
+    (best_score, best_row, best_pos) is the prefix of row best_row before position best_pos, plus <eos>.  An input that is not
+    done ran out of positions: its best unfinished hypothesis (row 0) wins iff its score is greater than the best finished
+    one -- the last two lines of _Base.beam_search."""
+    out: List[Tuple[List[int], float]] = []
+    for n in range(len(best_score)):
+        r0 = n * beam
+        hp = [row[r0:r0 + beam] for row in hist_parent[:positions]]
+        ht = [row[r0:r0 + beam] for row in hist_token[:positions]]
+        score, seq = float(best_score[n]), None
+        if score > float("-inf"):
+            seq = beam_backtrack(hp, ht, int(best_row[n]), int(best_pos[n])) + [eos]
+        if not done[n] and float(scores[r0]) > score:
+            score, seq = float(scores[r0]), beam_backtrack(hp, ht, 0, positions)
+        if seq is None:
+            raise RuntimeError(f"beam search: input {n} has neither a finished nor a live hypothesis")
+        out.append((seq, score))
+    return out

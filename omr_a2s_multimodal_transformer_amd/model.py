@@ -5,6 +5,7 @@ for the parameterised builds BASELINE.json names.  The three reference quirks (S
 from __future__ import annotations
 
 import ctypes
+import functools
 import itertools
 import math
 import random
@@ -17,7 +18,7 @@ from . import functional as Fn
 from . import kernels as K
 from ._lib import lib
 from .config import ModelConfig
-from .decoder import MIN_RAGGED_MEMORY, Decoder, MultiheadAttention, check_ragged_memories
+from .decoder import MAX_BEAM, MAX_RAGGED_MEMORY, MIN_RAGGED_MEMORY, Decoder, MultiheadAttention, check_ragged_memories
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
 from .evaluation import WINDOW_BATCHES, plan_groups
 from .lightning_shim import LightningModule
@@ -91,7 +92,28 @@ class CrossEntropyLoss(nn.Module):
         return Fn.cross_entropy(logits_bvt, target, self.ignore_index)
 
 
+def _beam_option(fn):
+    """Gives a `predict` / `evaluate` method the keyword `beam` (1 .. 8, default 1).  The method's own parameter list -- part
+    of the public surface the late-fusion code and its tests build on -- stays as it is; beam = 1 calls it as before, a
+    wider beam is checked here, before anything is encoded, and makes `_predict` decode every input with `beam_search` /
+    `beam_search_batch` for the duration of the call."""
+    @functools.wraps(fn)
+    def call(self, *args, beam: int = 1, **kwargs):
+        if not isinstance(beam, int) or not 1 <= beam <= MAX_BEAM:
+            raise ValueError(f"beam must be an integer in 1..{MAX_BEAM}, got {beam}")
+        if beam == 1:
+            return fn(self, *args, **kwargs)
+        before, self._decode_beam = self._decode_beam, beam
+        try:
+            return fn(self, *args, **kwargs)
+        finally:
+            self._decode_beam = before
+    return call
+
+
 class _Base(FlatModuleMixin, LightningModule):
+    _decode_beam = 1          # beam width `_predict` decodes with (set by _beam_option for the duration of a call)
+
     def _common_init(self, w2i, i2w, ytest_i2w, max_seq_len, attn_window, teacher_forcing_prob, config: Optional[ModelConfig]):
         if isinstance(config, dict):
             config = ModelConfig.from_dict(config)
@@ -251,9 +273,12 @@ class _Base(FlatModuleMixin, LightningModule):
         """Greedy predictions of inputs of any size, in input order, each equal to `_greedy` of that input alone.  A window
         of WINDOW_BATCHES * batch_size inputs at a time is encoded at batch size 1 (like validation_step), grouped by memory
         length (evaluation.plan_groups) and decoded group by group as ragged batches of up to batch_size rows.
-        want_probs: -> (predictions, the top-1 logits of their positions) like `_greedy(..., want_probs=True)`."""
+        want_probs: -> (predictions, the top-1 logits of their positions) like `_greedy(..., want_probs=True)`.
+        Called with a beam (`_beam_option`): the words of `beam_search` of every input instead, decoded
+        batch_size // beam inputs at a time (`beam_search_batch`: a group has at most batch_size rows)."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        beam = 1 if want_probs else self._decode_beam          # predict_with_probs takes no beam
         it = iter(items)
         preds: List[List[str]] = []
         probs: List[List[float]] = []
@@ -264,11 +289,17 @@ class _Base(FlatModuleMixin, LightningModule):
             mems = [encode(x) for x in window]
             out: List[Optional[List[str]]] = [None] * len(mems)
             outp: List[Optional[List[float]]] = [None] * len(mems)
-            singles, groups = plan_groups([m.shape[1] for m in mems], batch_size)
+            singles, groups = plan_groups([m.shape[1] for m in mems], batch_size if beam == 1 else max(1, batch_size // beam))
             for i in singles:
-                out[i], outp[i] = self._greedy(mems[i], want_probs=want_probs)
+                if beam > 1:
+                    out[i] = self.beam_search(mems[i], beam)[0]
+                else:
+                    out[i], outp[i] = self._greedy(mems[i], want_probs=want_probs)
             for g in groups:
-                if want_probs:
+                if beam > 1:
+                    for i, (seq, _) in zip(g, self.beam_search_batch([mems[i] for i in g], beam)):
+                        out[i] = seq
+                elif want_probs:
                     state = self.decoder.init_decode([mems[i] for i in g])
                     seqs, top1 = self._greedy_rows(state, len(g), mems[g[0]].device, 8, want_probs=True)
                     for i, seq, pr in zip(g, seqs, top1):
@@ -339,6 +370,41 @@ class _Base(FlatModuleMixin, LightningModule):
         if exhausted and scores[0] > best_done[0]:
             best_done = (scores[0], seqs[0])                          # ran out of length: the best unfinished hypothesis wins
         return [self._i2w(t) for t in best_done[1]], best_done[0]
+
+    @torch.no_grad()
+    def beam_search_batch(self, memories, beam: int = 4, sync_every: int = 8) -> List[Tuple[List[str], float]]:
+        """`beam_search` of N inputs at once, on the device (Decoder.init_beam_decode; csrc/decode.hip omr_beam_decode_steps):
+        -> [(words, score)] in input order, each exactly what `beam_search(memory, beam)` returns for that input alone
+        (tests/test_beam_batch_gpu.py).  memories: a list of [1, S_b, d] / [S_b, d] of different lengths.  The selection, the
+        scores and the cache reorder stay on the device; the host reads the `done` flags every `sync_every` positions only
+        and the whole state once at the end.  Memories of at most 64 or more than 16 384 tokens go through `beam_search`."""
+        if not 1 <= beam <= MAX_BEAM:
+            raise ValueError(f"beam must be in 1..{MAX_BEAM}, got {beam}")
+        if sync_every < 1:
+            raise ValueError(f"sync_every must be >= 1, got {sync_every}")
+        mems = [m[0] if m.dim() == 3 else m for m in memories]
+        alone = [len(m.shape) == 2 and m.shape[0] > MAX_RAGGED_MEMORY for m in mems]
+        if not mems or not all(alone):
+            check_ragged_memories([m.shape for m, a in zip(mems, alone) if not a], self.decoder.embedding.weight.shape[1])
+        out: List[Optional[Tuple[List[str], float]]] = [None] * len(mems)
+        batched = []
+        for i, m in enumerate(mems):
+            if alone[i] or m.shape[0] <= MIN_RAGGED_MEMORY:      # alone, such a memory takes another attention kernel: search it alone
+                out[i] = self.beam_search(m.unsqueeze(0), beam)
+            else:
+                batched.append(i)
+        if batched:
+            state = self.decoder.init_beam_decode([mems[i] for i in batched], beam, sos=self.w2i[SOS_TOKEN], eos=self.w2i[EOS_TOKEN])
+            left = self.max_seq_len
+            while left > 0:
+                n = min(sync_every, left)
+                state.run(n)
+                left -= n
+                if left > 0 and all(state.done()):                # one small device sync per chunk
+                    break
+            for i, (seq, score) in zip(batched, state.results()):
+                out[i] = ([self._i2w(t) for t in seq], score)
+        return out
 
     @torch.no_grad()
     def test_step(self, batch, batch_idx) -> None:
@@ -434,10 +500,12 @@ class Transformer(_Base):
         assert x.size(0) == 1, "predict takes inputs of batch size 1 ([1, C, H, W]); their sizes may differ"
         return self.encode(x)
 
+    @_beam_option
     @torch.no_grad()
     def predict(self, xs: Iterable[torch.Tensor], batch_size: int = 32) -> List[List[str]]:
         """Greedy predictions of inputs [1, C, H_b, W_b] of any size, in input order: each equals validation_step's decode
-        of that input, decoded batch_size memories at a time."""
+        of that input, decoded batch_size memories at a time.  Keyword `beam` (2 .. 8, `_beam_option`): the words of
+        `beam_search` of each input, batch_size // beam inputs at a time."""
         return self._predict(xs, self._encode_input, batch_size)
 
     @torch.no_grad()
@@ -446,9 +514,11 @@ class Transformer(_Base):
         memories at a time: (words, top-1 logits) per input, in input order, each equal to the batch-size-1 call's."""
         return self._predict(xs, self._encode_input, batch_size, want_probs=True)
 
+    @_beam_option
     @torch.no_grad()
     def evaluate(self, batches: Iterable, batch_size: int = 32) -> Dict[str, float]:
-        """The metrics of validation_step over `batches` ((x, y) each) followed by on_validation_epoch_end, decoded in batches."""
+        """The metrics of validation_step over `batches` ((x, y) each) followed by on_validation_epoch_end, decoded in batches.
+        Keyword `beam` (2 .. 8, `_beam_option`): the predictions are those of `beam_search`."""
         return self._evaluate(batches, lambda batch: batch[0], batch_size)
 
 
@@ -583,16 +653,19 @@ class MultimodalTransformer(_Base):
         x, _ = self.encoder_forward(xi=xi, xa=xa, xli=None, xla=None, apply_teacher_forcing_modality=False)
         return x
 
+    @_beam_option
     @torch.no_grad()
     def predict(self, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], batch_size: int = 32) -> List[List[str]]:
         """Greedy predictions of (image, audio) pairs of any size, in input order: each equals validation_step's decode of
-        that pair, decoded batch_size memories at a time."""
+        that pair, decoded batch_size memories at a time.  Keyword `beam` (2 .. 8, `_beam_option`): the words of `beam_search`
+        of each pair's memory, batch_size // beam pairs at a time."""
         return self._predict(pairs, self._encode_input, batch_size)
 
+    @_beam_option
     @torch.no_grad()
     def evaluate(self, batches: Iterable, batch_size: int = 32) -> Dict[str, float]:
         """The metrics of validation_step over `batches` ((xi, xa, y) each) followed by on_validation_epoch_end, decoded in
-        batches."""
+        batches.  Keyword `beam` (2 .. 8, `_beam_option`): the predictions are those of `beam_search`."""
         return self._evaluate(batches, lambda batch: (batch[0], batch[1]), batch_size)
 
     ##### MODALITY MIXERS (model.py:644-726)
