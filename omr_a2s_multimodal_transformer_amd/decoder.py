@@ -27,7 +27,9 @@ def sinusoid_1d(max_len: int, emb_dim: int) -> torch.Tensor:
 
 
 def _to_dev(t: torch.Tensor, device) -> torch.Tensor:
-    """Host -> device without blocking the host (pinned staging + non-blocking copy); device tensors pass through."""
+    """Host -> device without blocking the host (pinned staging + non-blocking copy); device tensors pass through.  A blocking
+    copy would wait for the whole previous step (it drains the stream) and stop the host from issuing the next step's
+    launches while the GPU is still busy."""
     if t.device == device:
         return t
     if not t.is_cuda and not t.is_pinned() and torch.cuda.is_available():
@@ -259,6 +261,21 @@ class Decoder(nn.Module):
             return None
         return dict(L=L, d=d, w=w, gw=gw, b=b, gb=gb)
 
+    def _compute_dtype(self) -> torch.dtype:
+        """bf16 when the flat parameter buffer keeps a low-precision copy of the matrices, else fp32."""
+        return torch.bfloat16 if getattr(self.embedding.weight, "omr_lowp", None) is not None else torch.float32
+
+    def _in_compute_dtype(self, memory: torch.Tensor) -> torch.Tensor:
+        dt = self._compute_dtype()
+        return K.cast(memory.contiguous(), dt) if memory.dtype != dt else memory.contiguous()
+
+    def memory_list(self, memories, refuse_long: bool = True) -> List[torch.Tensor]:
+        """Memories [1, S_b, d] or [S_b, d] -> the list of [S_b, d] in the compute dtype, checked (check_ragged_memories)
+        before anything is launched."""
+        mems = [m[0] if m.dim() == 3 else m for m in memories]
+        check_ragged_memories([m.shape for m in mems], self.embedding.weight.shape[1], refuse_long)
+        return [self._in_compute_dtype(m) for m in mems]
+
     # ---- KV-cached greedy decoding (SURVEY.md section 8b `decode_step`, section 8f rank 1).  The reference re-runs the whole
     #      prefix every step (model.py:184-193, O(T^3)) and reads the argmax back per token.  Here the native executor
     #      omr_decode_steps (csrc/decode.hip) runs whole tokens from ONE host call each: it projects the new token, appends
@@ -268,17 +285,9 @@ class Decoder(nn.Module):
     def init_decode(self, memory) -> "DecodeState":
         """memory [B, S, d] -> the decode state of B same-sized inputs.  A LIST of memories ([1, S_b, d] or [S_b, d] each) gives
         one ragged state: padded to S = max S_b, row b's cross-attention sees its own S_b keys (omr_decode_steps_varlen)."""
-        emb_w = self.embedding.weight
-        dt = torch.bfloat16 if getattr(emb_w, "omr_lowp", None) is not None else torch.float32
-
-        def as_dt(m):
-            return K.cast(m.contiguous(), dt) if m.dtype != dt else m.contiguous()
-
         if isinstance(memory, (list, tuple)):
-            mems = [m[0] if m.dim() == 3 else m for m in memory]
-            check_ragged_memories([m.shape for m in mems], self.embedding.weight.shape[1])
-            return DecodeState(self, [as_dt(m) for m in mems], dt)
-        return DecodeState(self, as_dt(memory), dt)
+            return DecodeState(self, self.memory_list(memory), self._compute_dtype())
+        return DecodeState(self, self._in_compute_dtype(memory), self._compute_dtype())
 
     @torch.no_grad()
     def init_beam_decode(self, memory, beam: int, sos: int = 2, eos: int = 1) -> "BeamDecodeState":
@@ -290,12 +299,8 @@ class Decoder(nn.Module):
             raise ValueError(f"beam must be in 1..{MAX_BEAM}, got {beam}")
         if beam > self.output_size or not (0 <= sos < self.output_size and 0 <= eos < self.output_size):
             raise ValueError(f"beam decode: beam {beam}, sos {sos}, eos {eos} do not fit a vocabulary of {self.output_size}")
-        emb_w = self.embedding.weight
-        dt = torch.bfloat16 if getattr(emb_w, "omr_lowp", None) is not None else torch.float32
-        mems = list(memory) if isinstance(memory, (list, tuple)) else [memory]
-        mems = [m[0] if m.dim() == 3 else m for m in mems]
-        check_ragged_memories([m.shape for m in mems], emb_w.shape[1])
-        return BeamDecodeState(self, [K.cast(m.contiguous(), dt) if m.dtype != dt else m.contiguous() for m in mems], dt, beam, sos, eos)
+        mems = self.memory_list(memory if isinstance(memory, (list, tuple)) else [memory])
+        return BeamDecodeState(self, mems, self._compute_dtype(), beam, sos, eos)
 
     @torch.no_grad()
     def decode_step(self, token: torch.Tensor, st: "DecodeState") -> torch.Tensor:
@@ -311,11 +316,8 @@ class Decoder(nn.Module):
         return st.run(token, n_steps)
 
     def forward(self, tgt: torch.Tensor, memory: torch.Tensor, memory_len: Optional[torch.Tensor]) -> torch.Tensor:
-        emb_w = self.embedding.weight
-        dt = torch.bfloat16 if getattr(emb_w, "omr_lowp", None) is not None else torch.float32
-        if memory.dtype != dt:
-            memory = K.cast(memory.contiguous(), dt)
-        memory = memory.contiguous()
+        emb_w, dt = self.embedding.weight, self._compute_dtype()
+        memory = self._in_compute_dtype(memory)
         B, T = tgt.shape
         # Host copies of the token ids / integer lengths (the Trainer keeps integer tensors on the host) tell, without a device
         # round trip, when a mask is all zeros: adding 0.0 to every score is the identity, so such a mask is not built and the
@@ -353,8 +355,15 @@ MIN_RAGGED_MEMORY = 64
 MAX_BEAM = 8                 # OMR_MAX_BEAM: beam * beam candidates of an input are one wavefront of the selection kernel
 
 
-def check_ragged_memories(shapes, d: int) -> None:
-    """Refuse, before anything is launched, memories a ragged decode state cannot take."""
+def takes_ragged_state(length: int) -> bool:
+    """Whether a memory of `length` tokens may be a row of a ragged decode state; any other is decoded alone, at batch size 1.
+    THE routing rule of evaluation.plan_pair_groups, _Base.greedy_batch and _Base.beam_search_batch."""
+    return MIN_RAGGED_MEMORY < length <= MAX_RAGGED_MEMORY
+
+
+def check_ragged_memories(shapes, d: int, refuse_long: bool = True) -> None:
+    """Refuse, before anything is launched, memories a ragged decode state cannot take.  refuse_long = False lets a memory of
+    more than MAX_RAGGED_MEMORY rows pass: the caller decodes it alone (_Base.beam_search_batch)."""
     if not shapes:
         raise ValueError("ragged decode: no memories given")
     for i, shp in enumerate(shapes):
@@ -362,7 +371,7 @@ def check_ragged_memories(shapes, d: int) -> None:
             raise ValueError(f"ragged decode: memory {i} has shape {tuple(shp)}, expected [S, {d}] or [1, S, {d}]")
         if shp[0] < 1:
             raise ValueError(f"ragged decode: memory {i} is empty (0 rows)")
-        if shp[0] > MAX_RAGGED_MEMORY:
+        if refuse_long and shp[0] > MAX_RAGGED_MEMORY:
             raise ValueError(f"ragged decode: memory {i} has {shp[0]} rows, more than the {MAX_RAGGED_MEMORY} a ragged batch takes "
                              "(64 key splits of 256); decode it alone")
 
@@ -377,9 +386,10 @@ class _DecodeDesc(ctypes.Structure):
 
 
 class DecodeState:
-    """Device state of one KV-cached decode: the cross-attention K|V of every layer projected ONCE into one [B, S, L*2d]
+    """Device state of one KV-cached decode: the cross-attention K|V of every layer projected ONCE into one [memories, S, L*2d]
     buffer, the self-attention K|V cache [L, B, max_len, 2d], the position t, and the descriptor omr_decode_steps reads.
-    Rows are independent: B same-sized inputs decode in lock-step (batched greedy), or B hypotheses share one memory (beam)."""
+    Rows are independent: B same-sized inputs decode in lock-step (batched greedy), or B hypotheses share one memory (beam).
+    rows_per_memory > 1 (BeamDecodeState): B = memories * rows_per_memory rows, those of a memory reading its one K|V slot."""
 
     LAYER_PARAMS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
                     "norm1.weight", "norm1.bias", "multihead_attn.in_proj_weight", "multihead_attn.in_proj_bias",
@@ -388,13 +398,14 @@ class DecodeState:
     FP8_PARAMS = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "multihead_attn.in_proj_weight",
                   "multihead_attn.out_proj.weight", "linear1.weight", "linear2.weight")          # OMR_DECODE_LAYER_FP8 order
 
-    def __init__(self, dec: "Decoder", memory, dt: torch.dtype):
+    def __init__(self, dec: "Decoder", memory, dt: torch.dtype, rows_per_memory: int = 1):
         layers = dec.transformer_decoder.layers
         self.dec, self.dtype, self.t = dec, dt, 0
         self.L, self.d = len(layers), dec.embedding.weight.shape[1]
         ragged = isinstance(memory, list)              # [S_b, d] memories of different lengths (Decoder.init_decode)
         mems = memory if ragged else [memory.reshape(-1, self.d)]
-        self.B = len(memory) if ragged else memory.shape[0]
+        n_mem = len(memory) if ragged else memory.shape[0]
+        self.B = n_mem * rows_per_memory
         self.S = max(m.shape[0] for m in memory) if ragged else memory.shape[1]
         self.max_len = dec.pos_1d.pe.shape[1]
         self.V, self.ldv = dec.output_size, K.round_up(dec.output_size, 8)
@@ -402,7 +413,7 @@ class DecodeState:
         # cross-attention K|V rows [d, 3d) of every layer's packed in_proj over the memory: one GEMM where the flat buffer
         # holds the layers back to back (Decoder._cross_kv_pack), else one GEMM per layer into its column block.  Ragged: one
         # GEMM per memory into the first S_b rows of its slot -- the very GEMM a batch-size-1 state of that memory runs
-        self.cross_kv = torch.empty((self.B, self.S, L * 2 * d), dtype=dt, device=dev)
+        self.cross_kv = torch.empty((n_mem, self.S, L * 2 * d), dtype=dt, device=dev)
         pack = dec._cross_kv_pack(dt)
         for b, mem2 in enumerate(mems):
             kv2 = self.cross_kv[b, :mem2.shape[0]] if ragged else self.cross_kv.view(-1, L * 2 * d)
@@ -414,7 +425,7 @@ class DecodeState:
                     w = Fn.wt(mha.in_proj_weight, dt)
                     K.gemm(mem2, w[d:], bias=mha.in_proj_bias.omr_phys[d:], out=kv2[:, li * 2 * d:(li + 1) * 2 * d])
         self.cross_bs = self.S * L * 2 * d
-        # row b's memory length (device int32), or None: every row sees all S rows
+        # memory b's length (device int32), or None: every row sees all S rows
         self.mem_len = torch.tensor([m.shape[0] for m in mems], dtype=torch.int32).to(dev) if ragged else None
         self.self_kv = torch.empty((L, self.B, self.max_len, 2 * d), dtype=dt, device=dev)
 
@@ -535,20 +546,12 @@ class BeamDecodeState(DecodeState):
     once and walks the history tables on the host (evaluation.beam_results)."""
 
     def __init__(self, dec: "Decoder", mems, dt: torch.dtype, beam: int, sos: int, eos: int):
-        self.beam, self.sos, self.eos = beam, sos, eos     # before the base constructor: _bind sizes the rows by the beam
-        super().__init__(dec, mems, dt)
-
-    def _bind(self) -> None:
-        if not hasattr(self, "N"):                         # first call, from DecodeState.__init__: B is still the number of memories
-            self.N, self.B = self.B, self.B * self.beam
-            dev = self.cross_kv.device
-            self.self_kv = torch.empty((self.L, self.B, self.max_len, 2 * self.d), dtype=self.dtype, device=dev)
-            self.self_kv2 = torch.empty_like(self.self_kv)
-        super()._bind()
+        super().__init__(dec, mems, dt, rows_per_memory=beam)
         import numpy as np
+        self.beam, self.sos, self.eos, self.N = beam, sos, eos, len(mems)
+        self.self_kv2 = torch.empty_like(self.self_kv)
         bd = self.bdesc = _BeamDesc()
-        bd.beam, bd.N, bd.max_len = self.beam, self.N, self.max_len
-        bd.eos, sos = self.eos, self.sos
+        bd.beam, bd.N, bd.eos, bd.max_len = beam, self.N, eos, self.max_len
         bd.state = None
         nbytes = lib().query("omr_beam_workspace_bytes", ctypes.byref(bd))
         if nbytes <= 0:
@@ -556,7 +559,7 @@ class BeamDecodeState(DecodeState):
         self._off = {n: int(getattr(bd, n) or 0) for n in _BeamDesc.STATE_FIELDS}      # state == NULL: the fields are offsets
         host = np.zeros(nbytes, dtype=np.uint8)
         rows = self.B
-        self._view(host, "scores", np.float64, rows)[:] = ([0.0] + [float("-inf")] * (self.beam - 1)) * self.N
+        self._view(host, "scores", np.float64, rows)[:] = ([0.0] + [float("-inf")] * (beam - 1)) * self.N
         self._view(host, "best_score", np.float64, self.N)[:] = float("-inf")
         self._view(host, "tokens", np.int64, rows)[:] = sos
         self._view(host, "exhausted", np.int32, self.N)[:] = 1

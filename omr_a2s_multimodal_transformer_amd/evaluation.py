@@ -1,12 +1,13 @@
 """Batched evaluation over inputs of different sizes.  The reference validates one input at a time (src/train.py:34,
 src/transformer/model.py:171-199, "Inference only supports batch_size = 1"); `predict` / `evaluate` of both model classes
 decode groups of memories of different lengths as ONE ragged decode state (Decoder.init_decode on a list), and every
-sequence equals the batch-size-1 loop's (`_greedy`) for that input.  This module holds the host-side grouping."""
+sequence equals the batch-size-1 loop's (`_greedy`) for that input.  This module holds the host side of that: the grouping,
+the read-back loop of the greedy decodes and the backtrack of the batched beam search."""
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import Callable, List, Sequence, Tuple
 
-from .decoder import MAX_RAGGED_MEMORY, MIN_RAGGED_MEMORY
+from .decoder import takes_ragged_state
 
 WINDOW_BATCHES = 8          # inputs are encoded and sorted by memory length a window of 8 * batch_size at a time
 
@@ -14,21 +15,11 @@ WINDOW_BATCHES = 8          # inputs are encoded and sorted by memory length a w
 def plan_groups(lengths: Sequence[int], batch_size: int, window: int = 0) -> Tuple[List[int], List[List[int]]]:
     """-> (singles, groups) over the indices of `lengths` (memory lengths in tokens).  singles: memories decoded alone at batch
     size 1 -- at most MIN_RAGGED_MEMORY tokens (such a row alone takes another attention kernel than the ragged batch) or
-    more than MAX_RAGGED_MEMORY.  groups: the other indices, sorted by decreasing length (ties: input order) within
-    consecutive windows of `window` inputs (0: one window) and cut into groups of at most batch_size, so that the rows of a
-    group have similar lengths.  Every index appears exactly once."""
-    if batch_size < 1:
-        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
-    n = len(lengths)
-    window = window if window > 0 else max(n, 1)
-    singles: List[int] = []
-    groups: List[List[int]] = []
-    for w0 in range(0, n, window):
-        idx = range(w0, min(n, w0 + window))
-        singles += [i for i in idx if not MIN_RAGGED_MEMORY < lengths[i] <= MAX_RAGGED_MEMORY]
-        rest = sorted((i for i in idx if MIN_RAGGED_MEMORY < lengths[i] <= MAX_RAGGED_MEMORY), key=lambda i: (-lengths[i], i))
-        groups += [rest[g:g + batch_size] for g in range(0, len(rest), batch_size)]
-    return singles, groups
+    more than MAX_RAGGED_MEMORY (decoder.takes_ragged_state).  groups: the other indices, sorted by decreasing length (ties:
+    input order) within consecutive windows of `window` inputs (0: one window) and cut into groups of at most batch_size, so
+    that the rows of a group have similar lengths.  Every index appears exactly once.  This is plan_pair_groups of pairs
+    whose two memories are the same one: 2 * length orders like length."""
+    return plan_pair_groups(lengths, lengths, batch_size, window)
 
 
 def plan_pair_groups(len_a: Sequence[int], len_b: Sequence[int], batch_size: int,
@@ -44,7 +35,7 @@ def plan_pair_groups(len_a: Sequence[int], len_b: Sequence[int], batch_size: int
         raise ValueError(f"plan_pair_groups: {len(len_a)} lengths for one model, {len(len_b)} for the other")
 
     def ragged(i: int) -> bool:
-        return MIN_RAGGED_MEMORY < len_a[i] <= MAX_RAGGED_MEMORY and MIN_RAGGED_MEMORY < len_b[i] <= MAX_RAGGED_MEMORY
+        return takes_ragged_state(len_a[i]) and takes_ragged_state(len_b[i])
 
     n = len(len_a)
     window = window if window > 0 else max(n, 1)
@@ -56,6 +47,32 @@ def plan_pair_groups(len_a: Sequence[int], len_b: Sequence[int], batch_size: int
         rest = sorted((i for i in idx if ragged(i)), key=lambda i: (-(len_a[i] + len_b[i]), i))
         groups += [rest[g:g + batch_size] for g in range(0, len(rest), batch_size)]
     return singles, groups
+
+
+def decode_rows(step: Callable, rows: int, eos: int, budget: int, sync_every: int,
+                want_probs: bool = False) -> Tuple[List[List[int]], List[List[float]]]:
+    """THE chunked read-back loop of every greedy decode (one model or two in lock-step, one row or a ragged batch): ->
+    (token ids, top-1 values) per row, each row cut after its <eos> (`eos`, kept) or after `budget` positions.
+    step(n) runs up to n further positions of all rows and returns (tokens, values) as host lists [m][rows], 1 <= m <= n
+    -- values only with want_probs, else None; it raises when it cannot advance.  The chosen tokens reach the next position
+    on the device, so the loop handles host lists only: the caller's `step` does the one read-back (two with values) per
+    chunk.  What a finished row computed after its <eos> is dropped (at most sync_every - 1 positions in vain); `step` is
+    not asked again once every row is done.  Without want_probs the value lists stay empty."""
+    out: List[List[int]] = [[] for _ in range(rows)]
+    values: List[List[float]] = [[] for _ in range(rows)]
+    done = [False] * rows
+    left = budget
+    while left > 0 and not all(done):
+        toks, top1 = step(min(sync_every, left))
+        for s, row in enumerate(toks):
+            for b, t in enumerate(row):
+                if not done[b]:
+                    out[b].append(t)
+                    if want_probs:
+                        values[b].append(float(top1[s][b]))
+                    done[b] = t == eos
+        left -= len(toks)
+    return out, values
 
 
 def beam_backtrack(hist_parent, hist_token, row: int, position: int) -> List[int]:

@@ -18,9 +18,9 @@ from . import functional as Fn
 from . import kernels as K
 from ._lib import lib
 from .config import ModelConfig
-from .decoder import MAX_BEAM, MAX_RAGGED_MEMORY, MIN_RAGGED_MEMORY, Decoder, MultiheadAttention, check_ragged_memories
+from .decoder import MAX_BEAM, Decoder, MultiheadAttention, _to_dev, takes_ragged_state
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
-from .evaluation import WINDOW_BATCHES, plan_groups
+from .evaluation import WINDOW_BATCHES, decode_rows, plan_groups
 from .lightning_shim import LightningModule
 from .metrics import compute_metrics, compute_metrics_sharded
 from .runtime import FlatModuleMixin
@@ -64,16 +64,6 @@ class PositionalEncoding2D(nn.Module):
             from .runtime import next_seed
             y = Fn.DropoutFn.apply(y, self.dropout_p, next_seed("nhwc", self.dropout_p), False, False)
         return y.permute(0, 3, 1, 2)
-
-
-def _h2d(t: torch.Tensor, device) -> torch.Tensor:
-    """Host -> device without blocking the host: a blocking copy would wait for the whole previous step (it drains the
-    stream) and stop the host from issuing the next step's launches while the GPU is still busy."""
-    if t.device == device:
-        return t
-    if not t.is_cuda and not t.is_pinned() and torch.cuda.is_available():
-        t = t.pin_memory()
-    return t.to(device, non_blocking=True)
 
 
 def _flatten_memory(x: torch.Tensor) -> torch.Tensor:
@@ -177,28 +167,12 @@ class _Base(FlatModuleMixin, LightningModule):
         token chained to the next position on the device; the host reads a chunk back at a time and cuts the sequence after
         <eos>, so at most chunk - 1 positions are computed in vain); use_cache=False re-runs the whole prefix each step
         exactly like the reference.  Both give the same tokens (tests/test_model_gpu.py)."""
-        sos = self.w2i[SOS_TOKEN]
-        tok = torch.full((1, 1), sos, dtype=torch.int64, device=memory.device)
+        if use_cache:
+            ids, top1 = self._greedy_state(self.decoder.init_decode(memory), chunk, want_probs)
+            return [self._i2w(t) for t in ids[0]], top1[0]
+        y_in = torch.full((1, 1), self.w2i[SOS_TOKEN], dtype=torch.int64, device=memory.device)
         yhat: List[str] = []
         probs: List[float] = []
-        if use_cache:
-            state = self.decoder.init_decode(memory)
-            left = self.max_seq_len
-            while left > 0:
-                n = min(chunk, left)
-                toks, top1 = self.decoder.decode_tokens(tok, state, n)
-                toks_h, top1_h = toks[:, 0].cpu().tolist(), (top1[:, 0].cpu().tolist() if want_probs else None)      # one sync per chunk
-                for i, token in enumerate(toks_h):
-                    word = self._i2w(token)
-                    yhat.append(word)
-                    if want_probs:
-                        probs.append(float(top1_h[i]))
-                    if word == EOS_TOKEN:
-                        return yhat, probs
-                tok = toks[-1].view(1, 1)
-                left -= n
-            return yhat, probs
-        y_in = tok
         for _ in range(self.max_seq_len):
             logits = self.decoder(tgt=y_in, memory=memory, memory_len=None)   # [1, V, t]
             last = logits[0, :, -1]
@@ -222,51 +196,39 @@ class _Base(FlatModuleMixin, LightningModule):
         of different lengths -- padding would change the encoder features, so the reference pads nothing at inference -- is
         decoded as one ragged state (tests/test_ragged_decode_gpu.py); memories of at most 64 tokens go through `_greedy`.
         Returns one word list per memory, in input order.  The host reads the chosen tokens back every `sync_every` steps only."""
-        if isinstance(memory, (list, tuple)):
-            return self._greedy_ragged(list(memory), sync_every)
-        B = memory.shape[0]
-        state = self.decoder.init_decode(memory)
-        return [[self._i2w(t) for t in seq] for seq in self._greedy_rows(state, B, memory.device, sync_every)]
-
-    def _greedy_ragged(self, memories: List[torch.Tensor], sync_every: int) -> List[List[str]]:
-        mems = [m[0] if m.dim() == 3 else m for m in memories]
-        check_ragged_memories([m.shape for m in mems], self.decoder.embedding.weight.shape[1])
+        if not isinstance(memory, (list, tuple)):
+            return self._words(self._greedy_state(self.decoder.init_decode(memory), sync_every)[0])
+        mems = self.decoder.memory_list(memory)
         out: List[Optional[List[str]]] = [None] * len(mems)
         batched = []
         for i, m in enumerate(mems):
-            if m.shape[0] <= MIN_RAGGED_MEMORY:          # alone, such a memory takes another attention kernel: decode it alone
-                out[i] = self._greedy(m.unsqueeze(0))[0]
-            else:
+            if takes_ragged_state(m.shape[0]):
                 batched.append(i)
+            else:                                        # alone, such a memory takes another attention kernel: decode it alone
+                out[i] = self._greedy(m.unsqueeze(0))[0]
         if batched:
             state = self.decoder.init_decode([mems[i] for i in batched])
-            for i, seq in zip(batched, self._greedy_rows(state, len(batched), mems[batched[0]].device, sync_every)):
-                out[i] = [self._i2w(t) for t in seq]
+            for i, seq in zip(batched, self._words(self._greedy_state(state, sync_every)[0])):
+                out[i] = seq
         return out
 
-    def _greedy_rows(self, state, B: int, device, sync_every: int, want_probs: bool = False):
-        """Token ids of B rows of a decode state, each cut after its <eos> or max_seq_len tokens.  want_probs: -> (ids, the
-        top-1 logit of every kept position), the floats get_pred_seq_and_pred_prob_seq returns for that row alone."""
-        sos, eos = self.w2i[SOS_TOKEN], self.w2i[EOS_TOKEN]
-        tok = torch.full((B, 1), sos, dtype=torch.int64, device=device)
-        done = [False] * B
-        out: List[List[int]] = [[] for _ in range(B)]
-        probs: List[List[float]] = [[] for _ in range(B)]
-        left = self.max_seq_len
-        while left > 0 and not all(done):
-            n = min(sync_every, left)
+    def _words(self, seqs: List[List[int]]) -> List[List[str]]:
+        return [[self._i2w(t) for t in seq] for seq in seqs]
+
+    def _greedy_state(self, state, sync_every: int, want_probs: bool = False):
+        """Greedy decode of every row of a decode state at position 0 (evaluation.decode_rows): -> (token ids, top-1 logits)
+        per row, each cut after its <eos> or max_seq_len tokens.  The logits (want_probs; else empty lists) are the floats
+        get_pred_seq_and_pred_prob_seq returns for that row alone."""
+        tok = torch.full((state.B, 1), self.w2i[SOS_TOKEN], dtype=torch.int64, device=state.tok.device)
+
+        def step(n: int):
+            nonlocal tok
             toks, top1 = self.decoder.decode_tokens(tok, state, n)   # n positions, tokens chained on the device
+            tok = toks[-1].view(-1, 1)
             top1_h = top1.cpu().tolist() if want_probs else None
-            for s, row in enumerate(toks.cpu().tolist()):             # one device sync for the whole chunk
-                for b, t in enumerate(row):
-                    if not done[b]:
-                        out[b].append(t)
-                        if want_probs:
-                            probs[b].append(float(top1_h[s][b]))
-                        done[b] = t == eos
-            tok = toks[-1].view(B, 1)
-            left -= n
-        return (out, probs) if want_probs else out
+            return toks.cpu().tolist(), top1_h                        # one device sync for the whole chunk
+
+        return decode_rows(step, state.B, self.w2i[EOS_TOKEN], self.max_seq_len, sync_every, want_probs)
 
     @torch.no_grad()
     def _predict(self, items: Iterable, encode: Callable[[object], torch.Tensor], batch_size: int, want_probs: bool = False):
@@ -279,6 +241,24 @@ class _Base(FlatModuleMixin, LightningModule):
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         beam = 1 if want_probs else self._decode_beam          # predict_with_probs takes no beam
+        if beam > 1:
+            rows = max(1, batch_size // beam)
+
+            def decode_single(mem):
+                return self.beam_search(mem, beam)[0], None
+
+            def decode_group(group):
+                return [(seq, None) for seq, _ in self._beam_state(group, beam, 8)]
+        else:
+            rows = batch_size
+
+            def decode_single(mem):
+                return self._greedy(mem, want_probs=want_probs)
+
+            def decode_group(group):
+                ids, top1 = self._greedy_state(self.decoder.init_decode(group), 8, want_probs)
+                return zip(self._words(ids), top1)
+
         it = iter(items)
         preds: List[List[str]] = []
         probs: List[List[float]] = []
@@ -289,24 +269,12 @@ class _Base(FlatModuleMixin, LightningModule):
             mems = [encode(x) for x in window]
             out: List[Optional[List[str]]] = [None] * len(mems)
             outp: List[Optional[List[float]]] = [None] * len(mems)
-            singles, groups = plan_groups([m.shape[1] for m in mems], batch_size if beam == 1 else max(1, batch_size // beam))
+            singles, groups = plan_groups([m.shape[1] for m in mems], rows)
             for i in singles:
-                if beam > 1:
-                    out[i] = self.beam_search(mems[i], beam)[0]
-                else:
-                    out[i], outp[i] = self._greedy(mems[i], want_probs=want_probs)
-            for g in groups:
-                if beam > 1:
-                    for i, (seq, _) in zip(g, self.beam_search_batch([mems[i] for i in g], beam)):
-                        out[i] = seq
-                elif want_probs:
-                    state = self.decoder.init_decode([mems[i] for i in g])
-                    seqs, top1 = self._greedy_rows(state, len(g), mems[g[0]].device, 8, want_probs=True)
-                    for i, seq, pr in zip(g, seqs, top1):
-                        out[i], outp[i] = [self._i2w(t) for t in seq], pr
-                else:
-                    for i, seq in zip(g, self.greedy_batch([mems[i] for i in g])):
-                        out[i] = seq
+                out[i], outp[i] = decode_single(mems[i])
+            for g in groups:                                   # planned: every memory of a group takes a ragged state
+                for i, (seq, top1) in zip(g, decode_group([mems[i] for i in g])):
+                    out[i], outp[i] = seq, top1
             preds += out
             probs += outp
             del mems
@@ -382,29 +350,30 @@ class _Base(FlatModuleMixin, LightningModule):
             raise ValueError(f"beam must be in 1..{MAX_BEAM}, got {beam}")
         if sync_every < 1:
             raise ValueError(f"sync_every must be >= 1, got {sync_every}")
-        mems = [m[0] if m.dim() == 3 else m for m in memories]
-        alone = [len(m.shape) == 2 and m.shape[0] > MAX_RAGGED_MEMORY for m in mems]
-        if not mems or not all(alone):
-            check_ragged_memories([m.shape for m, a in zip(mems, alone) if not a], self.decoder.embedding.weight.shape[1])
+        mems = self.decoder.memory_list(memories, refuse_long=False)
         out: List[Optional[Tuple[List[str], float]]] = [None] * len(mems)
         batched = []
         for i, m in enumerate(mems):
-            if alone[i] or m.shape[0] <= MIN_RAGGED_MEMORY:      # alone, such a memory takes another attention kernel: search it alone
-                out[i] = self.beam_search(m.unsqueeze(0), beam)
-            else:
+            if takes_ragged_state(m.shape[0]):
                 batched.append(i)
+            else:                                        # alone, such a memory takes another attention kernel: search it alone
+                out[i] = self.beam_search(m.unsqueeze(0), beam)
         if batched:
-            state = self.decoder.init_beam_decode([mems[i] for i in batched], beam, sos=self.w2i[SOS_TOKEN], eos=self.w2i[EOS_TOKEN])
-            left = self.max_seq_len
-            while left > 0:
-                n = min(sync_every, left)
-                state.run(n)
-                left -= n
-                if left > 0 and all(state.done()):                # one small device sync per chunk
-                    break
-            for i, (seq, score) in zip(batched, state.results()):
-                out[i] = ([self._i2w(t) for t in seq], score)
+            for i, result in zip(batched, self._beam_state([mems[i] for i in batched], beam, sync_every)):
+                out[i] = result
         return out
+
+    def _beam_state(self, mems, beam: int, sync_every: int) -> List[Tuple[List[str], float]]:
+        """The search of `beam_search_batch` over memories that all take a ragged state: one BeamDecodeState, run to the end."""
+        state = self.decoder.init_beam_decode(mems, beam, sos=self.w2i[SOS_TOKEN], eos=self.w2i[EOS_TOKEN])
+        left = self.max_seq_len
+        while left > 0:
+            n = min(sync_every, left)
+            state.run(n)
+            left -= n
+            if left > 0 and all(state.done()):                # one small device sync per chunk
+                break
+        return [([self._i2w(t) for t in seq], score) for seq, score in state.results()]
 
     @torch.no_grad()
     def test_step(self, batch, batch_idx) -> None:
@@ -478,7 +447,7 @@ class Transformer(_Base):
         x, xl, y_in, y_out = batch
         y_in = self.apply_teacher_forcing(y_in)
         yhat = self.forward(x=x, xl=xl, y_in=y_in)
-        loss = self.compute_loss(yhat, _h2d(y_out, yhat.device))
+        loss = self.compute_loss(yhat, _to_dev(y_out, yhat.device))
         self.log("train_loss", loss, prog_bar=True, logger=True, on_epoch=True)
         return loss
 
@@ -577,7 +546,7 @@ class MultimodalTransformer(_Base):
 
     def _encode(self, enc: Encoder, pos: PositionalEncoding2D, x: torch.Tensor) -> torch.Tensor:
         flat = self.ensure_flat()
-        f = enc.forward_nhwc(_h2d(x, flat.device), flat.compute_dtype).permute(0, 3, 1, 2)
+        f = enc.forward_nhwc(_to_dev(x, flat.device), flat.compute_dtype).permute(0, 3, 1, 2)
         return _flatten_memory(pos(f))
 
     def encoder_forward(self, xi, xa, xli=None, xla=None, apply_teacher_forcing_modality: bool = False):
@@ -634,7 +603,7 @@ class MultimodalTransformer(_Base):
         xi, xli, xa, xla, y_in, y_out = batch
         y_in = self.apply_teacher_forcing(y_in)
         yhat = self.forward(xi=xi, xli=xli, xa=xa, xla=xla, y_in=y_in, apply_teacher_forcing_modality=True)
-        loss = self.compute_loss(yhat, _h2d(y_out, yhat.device))
+        loss = self.compute_loss(yhat, _to_dev(y_out, yhat.device))
         self.log("train_loss", loss, prog_bar=True, logger=True, on_epoch=True)
         return loss
 

@@ -5,9 +5,9 @@ is fed back to BOTH decoders.
 
 The reference re-runs both decoders over the whole prefix per token and reads every token back; here each model keeps its KV
 cache (Decoder.init_decode: cross-attention K|V projected once, self-attention K|V appended per step), the mixing + argmax of
-a step is one kernel (omr_weighted_argmax) and a CHUNK of positions is one host call (omr_weighted_decode_steps: the picked
-token reaches both models' next position through device memory; the host reads a chunk of tokens back at a time and cuts
-the sequence after <eos>).  Same tokens as the reference (tests/golden/f15_weighted.npz).
+a step is one kernel (omr_weighted_argmax_rows) and a CHUNK of positions is one host call (omr_weighted_decode_steps_varlen:
+the picked token reaches both models' next position through device memory; the host reads a chunk of tokens back at a time
+and cuts the sequence after <eos>).  Same tokens as the reference (tests/golden/f15_weighted.npz).
 
 The reference evaluates a test set one pair at a time (test.py:154-172).  `weighted_predict` / `weighted_evaluate` decode
 groups of pairs of different sizes as two ragged decode states in lock-step (omr_weighted_decode_steps_varlen: per position
@@ -23,36 +23,35 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 import torch
 
 from ._lib import cur_stream, lib, ptr
-from .evaluation import WINDOW_BATCHES, plan_pair_groups
+from .evaluation import WINDOW_BATCHES, decode_rows, plan_pair_groups
 from .metrics import compute_metrics
 from .synthetic import EOS_TOKEN, SOS_TOKEN
 
 _EXHAUSTED = "weighted_prediction beyond a model's max_seq_len (positional-encoding table exhausted)"
 
 
-def _decode_pair(st_i, st_a, img_model, audio_model, alpha: float, chunk: int) -> List[str]:
-    """The lock-step loop of one pair (test.py:39-68) over two batch-size-1 decode states at position 0."""
-    assert st_i.V == st_a.V, "both models share the vocabulary (test.py:62)"
-    dev = st_i.tok.device
-    tok = torch.full((1,), img_model.w2i[SOS_TOKEN], dtype=torch.int64, device=dev)
-    yhat: List[str] = []
-    left = max(img_model.max_seq_len, audio_model.max_seq_len)
-    while left > 0:
-        n = min(chunk, left, st_i.max_len - st_i.t, st_a.max_len - st_a.t)
-        if n <= 0:
+def _decode_lockstep(st_i, st_a, img_model, audio_model, alpha: float, sync_every: int) -> List[List[str]]:
+    """The lock-step loop (test.py:39-68) of every row of two decode states at position 0 -- one pair over two batch-size-1
+    states, or B pairs over two ragged ones: the host reads the tokens back every `sync_every` positions and cuts each row
+    after its <eos> (evaluation.decode_rows).  A dense state has no memory lengths: its pointer is NULL, which
+    omr_weighted_decode_steps_varlen takes for either model (one row: what omr_weighted_decode_steps runs)."""
+    assert st_i.V == st_a.V and st_i.B == st_a.B, "both models share the vocabulary (test.py:62) and decode the same rows"
+    B, dev = st_i.B, st_i.tok.device
+    tok = torch.full((B,), img_model.w2i[SOS_TOKEN], dtype=torch.int64, device=dev)      # the picked tokens stay here, on the device
+
+    def step(n: int):
+        n = min(n, st_i.max_len - st_i.t, st_a.max_len - st_a.t)
+        if n <= 0:                                     # a live row outgrew the shorter positional table
             raise RuntimeError(_EXHAUSTED)
-        toks = torch.empty(n, dtype=torch.int64, device=dev)
-        lib().call("omr_weighted_decode_steps", ctypes.byref(st_i.desc), ctypes.byref(st_a.desc), float(alpha), ptr(tok), st_i.t, n, ptr(toks), None,
-                   ptr(st_i.logits), ptr(st_a.logits), cur_stream())
+        toks = torch.empty((n, B), dtype=torch.int64, device=dev)
+        lib().call("omr_weighted_decode_steps_varlen", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
+                   float(alpha), ptr(tok), st_i.t, n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
         st_i.t += n
         st_a.t += n
-        for token in toks.cpu().tolist():              # one device sync per chunk
-            word = img_model._i2w(token)
-            yhat.append(word)
-            if word == EOS_TOKEN:
-                return yhat
-        left -= n
-    return yhat
+        return toks.cpu().tolist(), None               # one device sync per chunk
+
+    ids, _ = decode_rows(step, B, img_model.w2i[EOS_TOKEN], max(img_model.max_seq_len, audio_model.max_seq_len), sync_every)
+    return [[img_model._i2w(t) for t in seq] for seq in ids]
 
 
 @torch.no_grad()
@@ -65,35 +64,7 @@ def weighted_prediction(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_mod
     mem_a = audio_model.encode(xa)
     st_i = img_model.decoder.init_decode(mem_i)
     st_a = audio_model.decoder.init_decode(mem_a)
-    return _decode_pair(st_i, st_a, img_model, audio_model, alpha, chunk)
-
-
-def _decode_rows(st_i, st_a, img_model, audio_model, alpha: float, sync_every: int) -> List[List[str]]:
-    """B pairs in lock-step over two ragged decode states at position 0: weighted_prediction's loop for every row, the host
-    reading the tokens back every `sync_every` positions and cutting each row after its <eos>."""
-    assert st_i.V == st_a.V and st_i.B == st_a.B
-    B, dev = st_i.B, st_i.tok.device
-    sos, eos = img_model.w2i[SOS_TOKEN], img_model.w2i[EOS_TOKEN]
-    tok = torch.full((B,), sos, dtype=torch.int64, device=dev)
-    done = [False] * B
-    out: List[List[int]] = [[] for _ in range(B)]
-    left = max(img_model.max_seq_len, audio_model.max_seq_len)
-    while left > 0 and not all(done):
-        n = min(sync_every, left, st_i.max_len - st_i.t, st_a.max_len - st_a.t)
-        if n <= 0:                                     # a live row outgrew the shorter positional table
-            raise RuntimeError(_EXHAUSTED)
-        toks = torch.empty((n, B), dtype=torch.int64, device=dev)
-        lib().call("omr_weighted_decode_steps_varlen", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
-                   float(alpha), ptr(tok), st_i.t, n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
-        st_i.t += n
-        st_a.t += n
-        for row in toks.cpu().tolist():                # one device sync per chunk
-            for b, t in enumerate(row):
-                if not done[b]:
-                    out[b].append(t)
-                    done[b] = t == eos
-        left -= n
-    return [[img_model._i2w(t) for t in seq] for seq in out]
+    return _decode_lockstep(st_i, st_a, img_model, audio_model, alpha, chunk)[0]
 
 
 def _check_models(img_model, audio_model) -> None:
@@ -129,20 +100,16 @@ def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[floa
         mems_a = [audio_model.encode(xa) for _, xa in window]
         out: List[List[Optional[List[str]]]] = [[None] * len(window) for _ in alphas]
         singles, groups = plan_pair_groups([m.shape[1] for m in mems_i], [m.shape[1] for m in mems_a], batch_size)
-        for i in singles:
-            st_i = img_model.decoder.init_decode(mems_i[i])
-            st_a = audio_model.decoder.init_decode(mems_a[i])
+        # a single: the pair alone over two batch-size-1 states, `chunk` positions per read-back like weighted_prediction
+        plans = [([i], mems_i[i], mems_a[i], chunk) for i in singles]
+        plans += [(g, [mems_i[i] for i in g], [mems_a[i] for i in g], sync_every) for g in groups]
+        for idx, mi, ma, every in plans:
+            st_i = img_model.decoder.init_decode(mi)
+            st_a = audio_model.decoder.init_decode(ma)
             for k, alpha in enumerate(alphas):
                 st_i.rewind()
                 st_a.rewind()
-                out[k][i] = _decode_pair(st_i, st_a, img_model, audio_model, alpha, chunk)
-        for g in groups:
-            st_i = img_model.decoder.init_decode([mems_i[i] for i in g])
-            st_a = audio_model.decoder.init_decode([mems_a[i] for i in g])
-            for k, alpha in enumerate(alphas):
-                st_i.rewind()
-                st_a.rewind()
-                for i, seq in zip(g, _decode_rows(st_i, st_a, img_model, audio_model, alpha, sync_every)):
+                for i, seq in zip(idx, _decode_lockstep(st_i, st_a, img_model, audio_model, alpha, every)):
                     out[k][i] = seq
             del st_i, st_a
         for k in range(len(alphas)):
