@@ -1,10 +1,10 @@
 // conv3x3 implicit-GEMM kernel (forward and data gradient) -- shared by conv_bf16.hip / conv_f32.hip so the two dtypes
 // compile in parallel.  See conv.hip for the overview.
 #pragma once
-#include <atomic>
 #include <type_traits>
 
 #include "omr_common.h"
+#include "launch_setup.h"
 
 namespace omr_conv {
 
@@ -498,18 +498,11 @@ template <typename T, int NT, int RPW, int CK, int SH, int SW, int DH, int DW, b
     const long tiles_per_img = (long)a.tiles_w * a.tiles_h;
     // persistent grid = the block slots the chip really has for this kernel (256 CUs x resident blocks per CU), split
     // evenly over the images: every block is resident from the start, no tail of queued blocks.  The per-instantiation
-    // launch constants (dynamic-LDS opt-in, resident blocks per CU) are looked up once; the cache is an atomic whose only
-    // transition is 0 -> value, and racing first calls compute the same value (one process drives one GPU).
+    // launch constants (dynamic-LDS opt-in, resident blocks per CU) are looked up once (launch_setup.h).
     static std::atomic<int> occ_cache{0};
-    int occv = occ_cache.load(std::memory_order_acquire);
-    if (occv == 0) {
-        if (shm > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return OMR_ERR_LAUNCH;
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, shm) != hipSuccess || occ < 1) occ = 2;
-        occv = occ;
-        occ_cache.store(occ, std::memory_order_release);
-    }
-    long gx = (256L * occv + (long)ny * a.B - 1) / ((long)ny * a.B);
+    const int occv = omr_launch_setup(occ_cache, (const void*)kern, shm, shm > 48 * 1024, 256, 2);
+    if (occv == 0) return OMR_ERR_LAUNCH;
+    long gx = ((long)OMR_NUM_CU * occv + (long)ny * a.B - 1) / ((long)ny * a.B);
     if (gx > tiles_per_img) gx = tiles_per_img;
     if (a.stat_mode) {                       // one workspace slot per block of an image
         if (a.stat_slots < 1) return OMR_ERR_ARG;

@@ -31,11 +31,11 @@
 //   * XN (16 channels): the conv normalises its input on load (ConvBlock conv3): the X tile is normalised in LDS -- xhat is the weight
 //     gradient's operand -- and the data gradient dL/dxhat leaves with {sum dx, sum dx * xhat} reduced deterministically into the
 //     InstanceNorm-backward slots (what conv3x3_mfma.h's stat_mode 2 epilogue does for the separate data-gradient kernel).
-#include <atomic>
 #include <type_traits>
 #include "omr_common.h"
 #include "omr_hip.h"
 #include "dma_common.h"
+#include "launch_setup.h"
 
 namespace {
 
@@ -503,12 +503,9 @@ template <int CO, int CI, bool APPLY, bool XN, int NSLOT> int launch(FusedArgs a
     if ((long)(IH + 1) * a.W * 32 >= (1L << 30)) return OMR_ERR_UNSUPPORTED;          // 32-bit tile-relative offsets
     auto kern = conv_bwd_fused_kernel<CO, CI, APPLY, XN, NSLOT>;
     static std::atomic<int> ready{0};
-    if (ready.load(std::memory_order_acquire) == 0) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L::TOTAL) != hipSuccess) return OMR_ERR_LAUNCH;
-        ready.store(1, std::memory_order_release);
-    }
+    if (!omr_launch_setup(ready, (const void*)kern, L::TOTAL, true)) return OMR_ERR_LAUNCH;
     const long tiles_per_img = (long)a.tiles_w * a.tiles_h;
-    long gx = (256 + a.B - 1) / a.B;                  // one workgroup per CU, split evenly over the images
+    long gx = (OMR_NUM_CU + a.B - 1) / a.B;                  // one workgroup per CU, split evenly over the images
     if (gx > tiles_per_img) gx = tiles_per_img;
     if (XN && gx > a.stat_slots) gx = a.stat_slots;          // one workspace slot per block of an image
     if (gx < 1) gx = 1;
@@ -843,12 +840,9 @@ extern "C" int omr_conv3x3_bwd_fused_s2(const void* g, const void* x, const void
     a.B = B; a.H = H; a.W = W; a.xmean = x_mean; a.xrstd = x_rstd; a.stat_ws = (double*)stat_workspace; a.stat_slots = stat_slots;
     a.tiles_w = cdiv(W, TW); a.tiles_h = cdiv(H, TH);
     static std::atomic<int> ready{0};
-    if (ready.load(std::memory_order_acquire) == 0) {
-        if (hipFuncSetAttribute((const void*)conv_bwd_fused_s2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S2::TOTAL) != hipSuccess) return OMR_ERR_LAUNCH;
-        ready.store(1, std::memory_order_release);
-    }
+    if (!omr_launch_setup(ready, (const void*)conv_bwd_fused_s2_kernel, S2::TOTAL, true)) return OMR_ERR_LAUNCH;
     const long tiles_per_img = (long)a.tiles_w * a.tiles_h;
-    long gx = (256 + B - 1) / B;
+    long gx = (OMR_NUM_CU + B - 1) / B;
     if (gx > tiles_per_img) gx = tiles_per_img;
     if (gx > stat_slots) gx = stat_slots;
     if (gx < 1) gx = 1;

@@ -1,4 +1,5 @@
-// Arguments of the 3x3 weight-gradient kernels (conv.hip: generic staged kernel; conv_wgrad_dma.hip: bf16 LDS-DMA kernel).
+// Arguments of the dense 3x3 weight-gradient kernels (conv.hip: generic staged kernel; conv_wgrad_dma.hip: bf16 LDS-DMA kernel).
+// The first layer (Cin = 1) and the depthwise family have their own: conv1.hip (conv1.h), dwconv.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

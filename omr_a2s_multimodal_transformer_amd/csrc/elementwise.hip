@@ -294,11 +294,6 @@ __global__ void stft_db_kernel(const float* __restrict__ spec, long frames, int 
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL)                         \
-    if ((dtype) == OMR_F32) { typedef float T; CALL; }  \
-    else if ((dtype) == OMR_BF16) { typedef bf16 T; CALL; } \
-    else return OMR_ERR_UNSUPPORTED;
-
 extern "C" int omr_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n, void* stream) {
     if (n <= 0) return OMR_OK;
     hipStream_t s = (hipStream_t)stream;

@@ -19,6 +19,7 @@
 #include "omr_hip.h"
 
 #include "gemm_args.h"
+#include "launch_setup.h"
 
 namespace {
 
@@ -160,13 +161,13 @@ int omr_gemm_panel_bf16(const GemmArgs& g, hipStream_t s) {
     const dim3 grid((unsigned)cdiv(g.M, PM)), block(512);
     if (g.K == 256) {
         constexpr size_t shm = (2 * PN * (256 + 8) + 2 * PM * (PN + 8)) * sizeof(bf16) + 2 * PN * sizeof(float);
-        static bool attr = false;
-        if (!attr) { if (hipFuncSetAttribute((const void*)gemm_panel_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return OMR_ERR_LAUNCH; attr = true; }
+        static std::atomic<int> ready{0};
+        if (!omr_launch_setup(ready, (const void*)gemm_panel_kernel<16>, shm, true)) return OMR_ERR_LAUNCH;
         hipLaunchKernelGGL((gemm_panel_kernel<16>), grid, block, shm, s, g);
     } else {
         constexpr size_t shm = (2 * PN * (128 + 8) + 2 * PM * (PN + 8)) * sizeof(bf16) + 2 * PN * sizeof(float);
-        static bool attr = false;
-        if (!attr) { if (hipFuncSetAttribute((const void*)gemm_panel_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return OMR_ERR_LAUNCH; attr = true; }
+        static std::atomic<int> ready{0};
+        if (!omr_launch_setup(ready, (const void*)gemm_panel_kernel<8>, shm, true)) return OMR_ERR_LAUNCH;
         hipLaunchKernelGGL((gemm_panel_kernel<8>), grid, block, shm, s, g);
     }
     OMR_CHECK_LAUNCH();

@@ -19,11 +19,11 @@
 //     consecutive columns: the 256 x 256 tile is packed to bf16 into the (dead) stage memory and leaves as whole 512-byte rows.
 // Row groups on the reduction side (GemmArgs grp_operand 2: the K|V rows of the layers' packed in_proj matrices) are resolved
 // per k-tile (a tile never straddles a group: grp % 64 == 0, host-checked).
-#include <atomic>
 #include "omr_common.h"
 #include "omr_hip.h"
 #include "gemm_args.h"
 #include "dma_common.h"
+#include "launch_setup.h"
 
 namespace {
 
@@ -165,11 +165,8 @@ int omr_gemm_tall_bf16(const GemmArgs& g0, hipStream_t s) {
     g.mt = (g.M + TM - 1) / TM;
     if (g.mt < 192) return OMR_ERR_UNSUPPORTED;          // fewer row tiles than CUs: the tile kernel spreads better
     static std::atomic<int> ready{0};
-    if (!ready.load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)gemm_tall_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess) return OMR_ERR_LAUNCH;
-        ready.store(1, std::memory_order_release);
-    }
-    const int grid = g.mt < 256 ? g.mt : 256;
+    if (!omr_launch_setup(ready, (const void*)gemm_tall_kernel, SMEM, true)) return OMR_ERR_LAUNCH;
+    const int grid = g.mt < OMR_NUM_CU ? g.mt : OMR_NUM_CU;
     hipLaunchKernelGGL(gemm_tall_kernel, dim3(grid), dim3(1024), SMEM, s, g);
     OMR_CHECK_LAUNCH();
     return OMR_OK;

@@ -274,11 +274,6 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(const T* __restrict__ d
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL)                         \
-    if ((dtype) == OMR_F32) { typedef float T; CALL; }  \
-    else if ((dtype) == OMR_BF16) { typedef bf16 T; CALL; } \
-    else return OMR_ERR_UNSUPPORTED;
-
 // Pixels per workgroup of the statistics passes: 2048 on the big maps, fewer on the small DSC maps so that at least ~1000
 // workgroups are in flight (16 x 256 maps with 2048 pixels per workgroup left 3/4 of the CUs idle).
 static int stat_pixels_per_block(long HW, int B) {

@@ -29,6 +29,12 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
         if (e__ != hipSuccess) return OMR_ERR_LAUNCH;         \
     } while (0)
 
+// Run CALL with T = the element type of a C-ABI dtype code (inside a function that returns an OMR_* status).
+#define DISPATCH_T(dtype, CALL)                         \
+    if ((dtype) == OMR_F32) { typedef float T; CALL; }  \
+    else if ((dtype) == OMR_BF16) { typedef bf16 T; CALL; } \
+    else return OMR_ERR_UNSUPPORTED;
+
 template <typename T> struct Frag;
 template <> struct Frag<bf16> {
     typedef bf16x8 type;

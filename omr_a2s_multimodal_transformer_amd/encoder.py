@@ -1,6 +1,6 @@
 """Convolutional encoder on HIP kernels -- same classes, constructor signatures, attribute and state-dict
 names as the reference's src/transformer/encoder.py; activations are NHWC internally and every conv /
-norm / dropout is a hand-written gfx950 kernel (csrc/conv.hip, norm.hip, gemm.hip, elementwise.hip).
+norm / dropout is a hand-written gfx950 kernel (csrc/conv.hip, conv1.hip, dwconv.hip, norm.hip, gemm.hip, elementwise.hip).
 """
 from __future__ import annotations
 

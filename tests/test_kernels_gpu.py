@@ -324,6 +324,80 @@ def test_dwconv3x3(dtype, C):
     check(k.dwconv3x3(nhwc(x2).to(dev(), dtype), wg, bias.detach().to(dev()), in_stats=stats), nhwc(ref), dtype, scale=2, what="dw norm fwd")
 
 
+# Which depthwise kernel a shape reaches (dispatch rules of omr_dwconv3x3 / omr_dwconv3x3_wgrad, csrc/dwconv.hip).  With
+# cv = C / (8 for bf16, 4 for fp32) 16-byte channel groups, tc = 256 / cv tile columns and a halo tile of 10 x (tc + 2) x C elements:
+#   forward / data gradient
+#     dwconv3x3_tile_kernel         tc >= 2, H >= 4, tile <= 64 KB, w 16-byte aligned: all four cases of test_dwconv3x3
+#     dwconv3x3_walk_kernel         H >= 4 otherwise: DW_PATH_CASES[0] (tile too large) and [1] (w not aligned) below
+#     dwconv3x3_kernel              H < 4: DW_PATH_CASES[2] below
+#   weight gradient
+#     dwconv3x3_wgrad_tile_kernel   NLD = 12 (10 (tc + 2) cv <= 3072): bf16 C = 128 in test_dwconv3x3
+#                                   NLD = 16: bf16 C = 256 in test_dwconv3x3
+#                                   "wide" fold (cv >= 64): fp32 C = 256 in test_dwconv3x3
+#     dwconv3x3_wgrad_kernel        cv not in {16, 32, 64..256} or H < 4: bf16 C = 64 in test_fuzz_depthwise_walkers, DW_PATH_CASES[2] below
+#     unsupported                   no tile and cv > 64: DW_PATH_CASES[0] below
+DW_PATH_CASES = [  # dtype, C, H, weight offset in bytes, weight gradient supported
+    # dwconv3x3_walk_kernel: the tile is 10 x 4 x 512 x 4 B = 80 KB > 64 KB; weight gradient: cv = 128 fits neither the tile nor a wave -> unsupported
+    (torch.float32, 512, 6, 0, False),
+    # dwconv3x3_walk_kernel: the weight starts 8 bytes into its buffer, the tile kernel reads taps as aligned 16-byte fragments;
+    # weight gradient: dwconv3x3_wgrad_tile_kernel<bf16, 12> (it does not read w)
+    (torch.bfloat16, 128, 6, 8, True),
+    # dwconv3x3_kernel (per pixel): H = 3 < 4; weight gradient: dwconv3x3_wgrad_kernel (row walker, cv = 16)
+    (torch.bfloat16, 128, 3, 0, True),
+]
+
+
+@pytest.mark.parametrize("dtype,C,H,w_off,has_wgrad", DW_PATH_CASES)
+def test_dwconv3x3_every_kernel(dtype, C, H, w_off, has_wgrad):
+    """The depthwise kernels test_dwconv3x3's shapes do not reach, against F.conv2d with test_dwconv3x3's tolerances; each with the
+    fused InstanceNorm on the input and the producer's mask on the output.  mask_scale = 2 doubles the data gradient, hence scale=2."""
+    B, W = 2, 19
+    x = q(rnd((B, C, H, W), 37), dtype).requires_grad_(True)
+    w = q(rnd((C, 1, 3, 3), 38) / 3, dtype).requires_grad_(True)
+    bias = rnd((C,), 39).requires_grad_(True)
+    y = F.conv2d(x, w, bias, padding=1, groups=C)
+    k = K()
+    xg = nhwc(x.detach()).to(dev(), dtype)
+    off = w_off // xg.element_size()
+    wbuf = torch.zeros(C * 9 + off, device=dev(), dtype=dtype)
+    wg = wbuf[off:].view(C, 9)                                  # a view `w_off` bytes into a larger buffer
+    wg.copy_(w.detach().reshape(C, 9))
+    assert wbuf.data_ptr() % 16 == 0 and wg.data_ptr() % 16 == w_off and wg.is_contiguous()
+    check(k.dwconv3x3(xg, wg, bias.detach().to(dev())), nhwc(y), dtype, what="dw fwd")
+    g = q(rnd((B, C, H, W), 40), dtype)
+    y.backward(g)
+    gg = nhwc(g).to(dev(), dtype)
+    check(k.dwconv3x3(gg, wg, None, flip=True), nhwc(x.grad), dtype, what="dw dgrad")
+    m = q(F.relu(rnd((B, C, H, W), 42)), dtype)                 # the producer's ReLU output: about half of it is 0
+    check(k.dwconv3x3(gg, wg, None, flip=True, out_mask=nhwc(m).to(dev(), dtype), mask_scale=2.0), nhwc(x.grad * (m > 0) * 2.0), dtype, scale=2,
+          what="dw masked dgrad")
+    # fused InstanceNorm on the input
+    x2 = q(F.relu(rnd((B, C, H, W), 41)), dtype).requires_grad_(True)
+    x2g = nhwc(x2.detach()).to(dev(), dtype)
+    stats = k.instnorm_stats(x2g)
+    w2 = w.detach().clone().requires_grad_(True)
+    b2 = bias.detach().clone().requires_grad_(True)
+    ref = F.conv2d(R.instance_norm(x2), w2, b2, padding=1, groups=C)
+    check(k.dwconv3x3(x2g, wg, bias.detach().to(dev()), in_stats=stats), nhwc(ref), dtype, scale=2, what="dw norm fwd")
+    dw, db = torch.zeros((C, 9), device=dev()), torch.zeros(C, device=dev())
+    if not has_wgrad:
+        with pytest.raises(RuntimeError, match="unsupported configuration"):
+            k.dwconv3x3_wgrad(xg, gg, dw, db)
+        with pytest.raises(RuntimeError, match="unsupported configuration"):
+            k.dwconv3x3_wgrad(x2g, gg, dw, db, in_stats=stats)
+        return
+    k.dwconv3x3_wgrad(xg, gg, dw, db)
+    check(dw, w.grad.reshape(C, 9), dtype, scale=6, what="dw wgrad")
+    check(db, bias.grad, dtype, scale=6, what="dw bgrad")
+    ref.backward(g)
+    dw.zero_(), db.zero_()
+    k.dwconv3x3_wgrad(x2g, gg, dw, db, in_stats=stats)
+    # the kernel rounds the normalised input to the compute dtype and unit-variance values are sqrt(3) x the uniform ones above:
+    # twice the plain bound, the factor test_fuzz_depthwise_walkers uses for its normalised cases
+    check(dw, w2.grad.reshape(C, 9), dtype, scale=12, what="dw norm wgrad")
+    check(db, b2.grad, dtype, scale=6, what="dw norm bgrad")
+
+
 # ------------------------------------------------------------------------------------------------ attention
 
 def ref_attention(qh, kh, vh, nhead, bias):
