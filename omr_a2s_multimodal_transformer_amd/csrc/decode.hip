@@ -52,7 +52,7 @@ size_t carve(const omr_decode_desc& d, char* base, Ws* w) {
 // (row, column): chunks in ascending k, the 16 k-lanes combined by a fixed cross-lane tree.  blockIdx.y picks RM rows; nothing in a row's
 // arithmetic depends on M or on the other rows.
 constexpr int RM = 8, NOUT = 16, KL = 16, WCH = 8;      // rows per workgroup, columns per workgroup, k-lanes, prefetched weight chunks per thread
-constexpr int MAXSPLIT = 64, MAXHS = 512;                // key splits the merge prologue takes (attention.hip choose_split caps a decode
+constexpr int MAXSPLIT = 64, MAXHS = 512;                // key splits the merge prologue takes (attn_common.h choose_split caps a decode
                                                          // row at 64 splits of >= 256 keys: the reference's largest memory, 12 696 tokens,
                                                          // is 50); heads x splits
 

@@ -1,4 +1,4 @@
-"""Round-3 attention kernels (csrc/attention.hip): augmented k-step (bias / reference maximum / log-sum-exp inside the MFMA
+"""Round-3 attention kernels (csrc/attention.hip, csrc/attention_bwd.hip): augmented k-step (bias / reference maximum / log-sum-exp inside the MFMA
 chain), lagged reference maximum, dropout keep bits read from pre-generated words.  Reference math: torch's
 multi_head_attention_forward as nn.TransformerDecoderLayer / CrossAttention use it (decoder.py:86-95, model.py:289-355)."""
 import math
@@ -55,12 +55,16 @@ def _ref_attention(q, k, v, H, key_bias, causal, mask):
     return (p @ vh).transpose(1, 2).reshape(B, T, d)
 
 
-@pytest.mark.parametrize("T,S,causal,p", [(200, 333, False, 0.25), (192, 192, True, 0.1), (20, 200, False, 0.25), (130, 1000, False, 0.0)])
+@pytest.mark.parametrize("T,S,causal,p", [(200, 333, False, 0.25), (192, 192, True, 0.1), (20, 200, False, 0.25), (130, 1000, False, 0.0),
+                                          (40, 1100, False, 0.25)])      # forward and dQ split the keys (2 x 768), with dropout words
 def test_attention_fwd_bwd_with_dropout_vs_torch_fp32(T, S, causal, p):
     """fp32 forward / dQ / dK / dV over several 64-key tiles, ragged edges, +1.0 and -inf key biases, against autograd through
     the written-out attention with the SAME keep mask (materialised by omr_attn_dropout_mask)."""
     from omr_a2s_multimodal_transformer_amd import kernels as K
     B, H, d, seed = 2, 2, 128, 99
+    if S == 1100:  # the case must keep covering the key split
+        from omr_a2s_multimodal_transformer_amd._lib import lib
+        assert lib().query("omr_attn_workspace_floats", B, H, T, S, d // H, 0, 0) > 0
     q, k, v = rnd((B, T, d), 1), rnd((B, S, d), 2), rnd((B, S, d), 3)
     bias = torch.zeros(B, S)
     bias[0, S - 40:] = 1.0                     # float padding mask: ADDED (decoder.py:186-188)

@@ -424,6 +424,9 @@ ATTN_CASES = [  # name, T, S, d, nhead, causal, window, key_bias kind, blk
     ("decode_one_query", 1, 700, 256, 4, False, -1, "plus1", False),      # T <= 32: the forward splits the keys over the waves
     ("decode_few_queries", 20, 333, 128, 4, False, -1, "neginf", False),
     ("decode_blk_quirk", 8, 130, 256, 4, False, -1, None, True),
+    # T > 32 and S >= 1024: forward and dQ split the keys over workgroups (2 x 768).  Rows 1 and 2 have 733 and 366 valid keys, so
+    # their whole second split is -inf: the weight-0 path of the merge
+    ("cross_key_split", 40, 1100, 256, 4, False, -1, "neginf", False),
 ]
 
 
@@ -455,6 +458,9 @@ def test_attention_fwd_bwd(dtype, name, T, S, d, nhead, causal, window, kb, blk)
     g = q(rnd((B, T, d), 60), dtype)
     ref.backward(g)
     k = K()
+    if name == "cross_key_split":  # the case must keep covering the key split
+        from omr_a2s_multimodal_transformer_amd._lib import lib
+        assert lib().query("omr_attn_workspace_floats", B, nhead, T, S, d // nhead, 0, 0) > 0
     if packed:  # q|k|v packed [B,T,3d] views, as the decoder's self-attention uses them
         qkv = torch.cat([qv, kv, vv], dim=-1).detach().to(dev(), dtype)
         qg, kg, vg = qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:]
