@@ -274,6 +274,17 @@ int omr_attn_fwd_split_partials(int dtype, const void* q, const void* k, const v
 int omr_attn_fwd_split_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
                               long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
                               const float* key_bias, const int* kv_len, float* split_ws, long split_ws_floats, void* stream);
+/* omr_attn_fwd_split_varlen with a per-row first key as well (continuous batching of greedy evaluation: the reference decodes
+ * one input at a time, src/transformer/model.py:171-199; here the rows of a decode state each sit at their own position, so
+ * the banded self-attention window [lo_b, t_b] of decoder.py:213-214 differs per row).  Row b attends over rows
+ * [kv_start[b], kv_start[b] + kv_len[b]) of its K / V slot (kv_start: device int32 [B], in keys, NULL = 0; key_bias[b][j]
+ * belongs to key kv_start[b] + j); nothing outside that range is read.  S = the largest kv_len, any value >= 1: this entry
+ * always takes the key-split kernel, so output and lse of every row are bit-equal to omr_attn_fwd_split of that row alone
+ * (K / V advanced by kv_start[b], S = kv_len[b]) for every kv_len[b] >= 1, 64 keys and fewer included. */
+int omr_attn_fwd_split_rows(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                            long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                            const float* key_bias, const int* kv_len, const int* kv_start, float* split_ws, long split_ws_floats,
+                            void* stream);
 /* Test / debug entry: the attention-probability dropout keep-mask (1 = kept) for (seed, dropout_p) -- the function
  * omr_attn_dropout_words packs -- one byte per score, mask[B][H][T][S].  Lets a checker inject the very same mask into a CPU
  * restatement of nn.MultiheadAttention's dropout (tests/test_dropout_parity_gpu.py). */
@@ -349,6 +360,18 @@ int omr_decode_steps(const omr_decode_desc* desc, long* tokens, int t0, int n_st
  * S).  A row with mem_len[b] > 64 gets, token for token, what omr_decode_steps gives for that memory alone. */
 int omr_decode_steps_varlen(const omr_decode_desc* desc, const int* mem_len, long* tokens, int t0, int n_steps, long* out_tokens,
                             float* out_top1, float* last_logits, void* stream);
+/* omr_decode_steps_varlen for rows that each sit at their OWN position (continuous batching: a row that took <eos> hands its
+ * slot to the next input while its neighbours go on; the reference's loop, src/transformer/model.py:171-199, has one input).
+ * pos: device int32 [B], row b's position when the call starts; row b runs positions pos[b] .. pos[b] + n_steps - 1: it adds
+ * pe[pos[b] + s], writes its K|V into cache row pos[b] + s of its own slot, attends over cache rows [lo_b, pos[b] + s]
+ * (omr_attn_fwd_split_rows) and over its mem_len[b] memory keys (mem_len nullable).  Nothing beyond a row's own position or
+ * memory length is read: a slot may still hold its previous occupant's cache.  t_max: the largest entry of pos, given by the
+ * host; t_max + n_steps > max_len is refused before the first launch (and positions are clamped on the device to the cache).
+ * `pos` is read once per call and not advanced.  Everything else as in omr_decode_steps_varlen.  Only descriptors of the row
+ * kernel (d in {128, 256, 512}, ff <= 2048) are taken; any other returns OMR_ERR_UNSUPPORTED -- that answer comes before
+ * every other argument check, so a caller may ask with NULL pointers. */
+int omr_decode_steps_rows(const omr_decode_desc* desc, const int* mem_len, const int* pos, int t_max, long* tokens, int n_steps,
+                          long* out_tokens, float* out_top1, float* last_logits, void* stream);
 /* Weighted late fusion (src/multimodal/weighted_multimodal/test.py:21-70) without a host round trip per token: positions
  * t0 .. t0+n_steps-1 of TWO models (descriptors with B = 1 and the same vocabulary) in lock-step; per position
  * argmax(alpha * softmax(logits_a) + (1 - alpha) * softmax(logits_b)) (omr_weighted_argmax) is written to out_tokens[s]
@@ -366,6 +389,12 @@ int omr_weighted_decode_steps(const omr_decode_desc* desc_a, const omr_decode_de
 int omr_weighted_decode_steps_varlen(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b,
                                      const int* mem_len_b, float alpha, long* tokens, int t0, int n_steps, long* out_tokens,
                                      float* out_prob, float* logits_a, float* logits_b, void* stream);
+/* omr_weighted_decode_steps_varlen over rows at their own positions (src/multimodal/weighted_multimodal/test.py:21-70,154-172
+ * with continuous batching): ONE pos / t_max for both models -- the two models of a pair are always at the same position --
+ * as in omr_decode_steps_rows; `tokens` in = the token each row feeds to its position pos[b]. */
+int omr_weighted_decode_steps_rows(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b, const int* mem_len_b,
+                                   const int* pos, int t_max, float alpha, long* tokens, int n_steps, long* out_tokens, float* out_prob,
+                                   float* logits_a, float* logits_b, void* stream);
 
 /* ---- batched beam search on the device ------------------------------------------------------------------------------- */
 /* Beam search (BASELINE config 5 "beam-search decode"; an extension -- the reference only decodes greedily, model.py:182-193)

@@ -25,8 +25,12 @@ using namespace attn;
 // kv_len (SPLITW only, nullable): batch row b attends over keys [0, kv_len[b]) of its padded S (a ragged batch of decode
 // memories).  Every key bound below is that row's; a key split or wave past it walks nothing and leaves (O 0, max -inf,
 // sum 0), which both mergers weigh with 0.  The tile loads clamp to the row's last key, so nothing past it is ever read.
+// kv_start (SPLITW only, nullable): row b's keys begin at row kv_start[b] of its K / V slot (per-row positions of a decode state
+// with slots: the banded self-attention window [lo_b, t_b]); key j of the row, its key_bias entry included, is slot row
+// kv_start[b] + j, and nothing before the start is read either.
 template <typename T, int HD, bool SPLITW, bool DROP>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint64_t* __restrict__ dmask, const int* __restrict__ kv_len) {
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint64_t* __restrict__ dmask, const int* __restrict__ kv_len,
+                                                          const int* __restrict__ kv_start) {
     typedef typename Frag<T>::type F;
     constexpr int VEC = ACfg<T>::VEC, NFR = ACfg<T>::NFR, KS = KStep<T>::value;
     constexpr int NKS = HD / KS, NDB = HD / 32, BKV = 64;
@@ -57,7 +61,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint
     const T* K = (const T*)a.k + (long)bk * a.bsk + h * HD;
     const T* V = (const T*)a.v + (long)bk * a.bsv + h * HD;
     int S = a.S;                                                // this row's key count (never past the padded S; <= 0: no keys)
-    if constexpr (SPLITW) { if (kv_len) S = min(kv_len[bk], a.S); }
+    if constexpr (SPLITW) {
+        if (kv_len) S = min(kv_len[bk], a.S);
+        if (kv_start) { const long first = max(kv_start[bk], 0); K += first * a.ldk; V += first * a.ldv; }
+    }
 
     const float sc2 = a.scale * LOG2E;
     F qf[NKS];                                                  // Q * scale * log2 e
@@ -353,15 +360,16 @@ __global__ __launch_bounds__(256) void attn_dropout_words_kernel(uint64_t* __res
 // query-per-wave kernel.
 bool takes_decode_kernel(const AttnArgs& a) { return a.T <= 32 && a.S > 64 && !a.drop_thresh; }
 
-template <typename T, int HD> int run_fwd(const AttnArgs& a, hipStream_t s, bool merge, const int* kv_len) {
+// force_split: the key-split kernel whatever S is (omr_attn_fwd_split_rows: rows of at most 64 keys beside longer ones)
+template <typename T, int HD> int run_fwd(const AttnArgs& a, hipStream_t s, bool merge, const int* kv_len, const int* kv_start, bool force_split) {
     const int nsplit = a.nsplit > 1 ? a.nsplit : 1;
-    if (takes_decode_kernel(a)) {
-        hipLaunchKernelGGL((attn_fwd_kernel<T, HD, true, false>), dim3(nsplit, a.H, a.B), dim3(256), 0, s, a, a.dmask, kv_len);
+    if (force_split || takes_decode_kernel(a)) {
+        hipLaunchKernelGGL((attn_fwd_kernel<T, HD, true, false>), dim3(nsplit, a.H, a.B), dim3(256), 0, s, a, a.dmask, kv_len, kv_start);
     } else {
         if (kv_len) return OMR_ERR_UNSUPPORTED;                // per-row key counts: the key-split kernel above only
         const dim3 grid(cdiv(a.T, 128) * nsplit, a.H, a.B);
-        if (a.drop_thresh) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, false, true>), grid, dim3(256), 0, s, a, a.dmask, (const int*)nullptr);
-        else hipLaunchKernelGGL((attn_fwd_kernel<T, HD, false, false>), grid, dim3(256), 0, s, a, a.dmask, (const int*)nullptr);
+        if (a.drop_thresh) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, false, true>), grid, dim3(256), 0, s, a, a.dmask, (const int*)nullptr, (const int*)nullptr);
+        else hipLaunchKernelGGL((attn_fwd_kernel<T, HD, false, false>), grid, dim3(256), 0, s, a, a.dmask, (const int*)nullptr, (const int*)nullptr);
         merge = true;                                          // partials of this kernel are always merged here
     }
     if (a.nsplit > 1 && merge) hipLaunchKernelGGL((attn_split_merge_kernel<T, HD>), dim3(a.B * a.H * a.T), dim3(64), 0, s, a);
@@ -370,12 +378,13 @@ template <typename T, int HD> int run_fwd(const AttnArgs& a, hipStream_t s, bool
 }
 
 // Every forward entry point.  nsplit_out: the caller merges the key-split partials itself (decode.hip) and is told how many
-// there are; kv_len / kv_group: see attn_fwd_kernel.
+// there are; kv_len / kv_start / kv_group: see attn_fwd_kernel.  rows: the per-row-window form (omr_attn_fwd_split_rows), which takes
+// the key-split kernel for every S.
 int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv, long ldo,
                   long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim, int causal, int window,
                   const float* key_bias, const int* blk_lq, const int* blk_lkv, float dropout_p, unsigned long long seed,
                   const unsigned long long* drop_words, float* split_ws, long split_ws_floats, void* stream, int* nsplit_out = nullptr,
-                  const int* kv_len = nullptr, int kv_group = 1) {
+                  const int* kv_len = nullptr, int kv_group = 1, const int* kv_start = nullptr, bool rows = false) {
     AttnArgs a = {};
     int rc = fill_common(a, B, H, T, S, head_dim, dropout_p, seed, causal, window, key_bias, blk_lq, blk_lkv, drop_words, true);
     if (rc) return rc;
@@ -386,14 +395,16 @@ int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v, void* 
     rc = plan_split(a, head_dim, split_ws, split_ws_floats, fwd_split_floats);
     if (rc) return rc;
     // per-row key counts exist only in the key-split decode kernel: a shape that would not take it is refused, not run unmasked
-    if ((kv_len || kv_group != 1) && !(takes_decode_kernel(a) && !causal && !blk_lq)) return OMR_ERR_UNSUPPORTED;
+    if (rows && (T > 32 || a.drop_thresh || causal || blk_lq)) return OMR_ERR_ARG;
+    const bool split_kernel = rows || takes_decode_kernel(a);
+    if ((kv_len || kv_start || kv_group != 1) && !(split_kernel && !causal && !blk_lq)) return OMR_ERR_UNSUPPORTED;
     const bool merge = nsplit_out == nullptr;           // a caller that asks for the split count merges the partials itself
     // only that kernel leaves partials (its rule also asks for "no dropout", which is immaterial here: no entry point passes both
     // nsplit_out and dropout)
-    if (!merge && !takes_decode_kernel(a)) { a.nsplit = 1; a.split_len = 0; a.part = nullptr; }
+    if (!merge && !split_kernel) { a.nsplit = 1; a.split_len = 0; a.part = nullptr; }
     if (nsplit_out) *nsplit_out = a.nsplit;
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_T(dtype, DISPATCH_HD(head_dim, return (run_fwd<T, HD>(a, s, merge, kv_len))))
+    DISPATCH_T(dtype, DISPATCH_HD(head_dim, return (run_fwd<T, HD>(a, s, merge, kv_len, kv_start, rows))))
 }
 
 }  // namespace
@@ -499,4 +510,27 @@ int attn_fwd_split_partials_varlen(int dtype, const void* q, const void* k, cons
     if (T > 32) return OMR_ERR_ARG;
     return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, nullptr, nullptr, nullptr, 0.f, 0,
                          nullptr, split_ws, split_ws_floats, stream, nsplit, kv_len, kv_group);
+}
+
+/* omr_attn_fwd_split_varlen with a per-row key START as well: the self-attention of a decode state whose rows sit at their own
+ * positions (src/transformer/model.py:171-199 decodes one input at a time; here a finished row's slot goes to the next input).
+ * Row b attends over rows [kv_start[b], kv_start[b] + kv_len[b]) of its K / V slot; S is the largest kv_len (the split plan's).
+ * Always the key-split kernel, S <= 64 included. */
+extern "C" int omr_attn_fwd_split_rows(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                                       long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                                       const float* key_bias, const int* kv_len, const int* kv_start, float* split_ws, long split_ws_floats,
+                                       void* stream) {
+    if (T > 32) return OMR_ERR_ARG;
+    return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, key_bias, nullptr, nullptr, 0.f, 0,
+                         nullptr, split_ws, split_ws_floats, stream, nullptr, kv_len, 1, kv_start, true);
+}
+
+/* omr_attn_fwd_split_rows without the merge pass, for the per-row-position decode executor (decode.hip).  A C++ symbol, not part
+ * of the C ABI */
+int attn_fwd_split_partials_rows(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                                 long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                                 const int* kv_len, const int* kv_start, float* split_ws, long split_ws_floats, int* nsplit, void* stream) {
+    if (T > 32 || !nsplit) return OMR_ERR_ARG;
+    return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, nullptr, nullptr, nullptr, 0.f, 0,
+                         nullptr, split_ws, split_ws_floats, stream, nsplit, kv_len, 1, kv_start, true);
 }

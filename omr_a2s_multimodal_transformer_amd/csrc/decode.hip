@@ -18,6 +18,7 @@ struct Ws {          // activation scratch of one step, carved out of the caller
     char* x; char* x2; char* q; char* o; char* proj; char* h; char* logits; float* logits32; float* lse; float* mean; float* rstd;
     float* split; long split_floats; float* apart;
     unsigned char* a8; float* sa8;          // fp8 mode: the quantised input rows of the current GEMM and their scales
+    int* rows_tab;                          // per-row positions: [3][max_len][B] tables of position | first key | key count
 };
 
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -37,7 +38,8 @@ size_t carve(const omr_decode_desc& d, char* base, Ws* w) {
     const size_t kmax = (size_t)(d.d > d.ff ? d.d : d.ff);
     unsigned char* a8 = (unsigned char*)take(d.fp8 ? B * ((kmax + 15) / 16 * 16) : 0);
     float* sa8 = (float*)take(d.fp8 ? B * 4 : 0);
-    if (w) *w = Ws{x, x2, q, o, proj, h, logits, l32, lse, mean, rstd, split, sf, apart, a8, sa8};
+    int* rows_tab = (int*)take(3 * B * (size_t)(d.max_len > 0 ? d.max_len : 0) * 4);
+    if (w) *w = Ws{x, x2, q, o, proj, h, logits, l32, lse, mean, rstd, split, sf, apart, a8, sa8, rows_tab};
     return off;
 }
 
@@ -82,8 +84,14 @@ __device__ __forceinline__ void w_unpack(const f32x4& c, float (&f)[4]) {
     for (int e = 0; e < 4; ++e) f[e] = c[e];
 }
 
-template <typename T, bool W8>
-__global__ __launch_bounds__(256) void decode_linear_kernel(omr_decode_linear_args a) {
+// The kernel's argument block: the public omr_decode_linear_args (its layout is pinned) plus what a decode state with per-row
+// positions adds (ROWS): row m sits at position row_pos[m], so its positional row is pe_row + row_pos[m] * K and its out1 part
+// (the K|V projection's cache row) lands out1_pos_ld elements further per position.
+struct LinArgs { omr_decode_linear_args a; const int* row_pos; long out1_pos_ld; };
+
+template <typename T, bool W8, bool ROWS>
+__global__ __launch_bounds__(256) void decode_linear_kernel(LinArgs la) {
+    const omr_decode_linear_args& a = la.a;
     typedef typename Frag<T>::type F;
     constexpr int VEC = W8 ? 8 : Frag<T>::N;                            // weight elements per chunk (fp8: 8 codes = 8 bytes)
     typedef typename std::conditional<W8, W8Chunk, F>::type WF;
@@ -133,9 +141,10 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(omr_decode_linear_ar
             } else if (a.pro == 2) {        // embedding + positional row (embed_pe_kernel, elementwise.hip)
                 const long t = a.tokens[m];
                 const bool ok = t >= 0 && t < a.vocab;
+                const float* pe_row = ROWS ? a.pe_row + (long)la.row_pos[m] * K : a.pe_row;
                 for (int i = 0; i < per; ++i) {
                     const int k = lane * per + i;
-                    const T o = from_f32<T>((ok ? to_f32(((const T*)a.emb)[t * K + k]) : 0.f) + a.pe_row[k]);
+                    const T o = from_f32<T>((ok ? to_f32(((const T*)a.emb)[t * K + k]) : 0.f) + pe_row[k]);
                     xr[k] = to_f32(o);
                     if (blockIdx.x == 0) ((T*)a.xn_out)[m * K + k] = o;
                 }
@@ -215,7 +224,7 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(omr_decode_linear_ar
                 const T o = from_f32<T>(v);
                 const long m = r0 + r;
                 if (n < a.n0) ((T*)a.out0)[m * a.ld0 + n] = o;
-                else ((T*)a.out1)[m * a.ld1 + (n - a.n0)] = o;
+                else ((T*)a.out1)[m * a.ld1 + (ROWS ? (long)la.row_pos[m] * la.out1_pos_ld : 0) + (n - a.n0)] = o;
                 if (a.out32) a.out32[m * a.ld32 + n] = to_f32(o);
                 cand[r][nl] = to_f32(o);
             }
@@ -258,11 +267,21 @@ __global__ __launch_bounds__(64) void decode_pick_kernel(const float* __restrict
     if (lane == 0) { idx_out[blockIdx.x] = bi; if (val_out) val_out[blockIdx.x] = best; }
 }
 
-}  // namespace
+// Per-row positions (omr_decode_steps_rows): ONE launch per host call turns pos[B] into the tables every kernel of position s
+// indexes at [s][b] -- the position pos[b] + off + s, the first visible key lo_b (banded causal mask, decoder.py:213-214) and
+// the key count.  A position is clamped into [0, max_len - n_steps]: whatever `pos` holds, no kernel leaves the caches.
+__global__ __launch_bounds__(256) void decode_rows_tables_kernel(const int* __restrict__ pos, int off, int B, int n_steps, int max_len, int window,
+                                                                 int* __restrict__ tpos, int* __restrict__ tstart, int* __restrict__ tcount) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * n_steps) return;
+    const int b = i % B, s = i / B;
+    const int t = min(max(pos[b] + off, 0), max_len - n_steps) + s;
+    const int lo = (window > 0 && t - window > 0) ? t - window : 0;
+    tpos[i] = t; tstart[i] = lo; tcount[i] = t + 1 - lo;
+}
 
-extern "C" int omr_decode_linear(const omr_decode_linear_args* ap, void* stream) {
-    if (!ap) return OMR_ERR_ARG;
-    const omr_decode_linear_args& a = *ap;
+// row_pos != NULL: the per-row-position form (LinArgs)
+int decode_linear_impl(const omr_decode_linear_args& a, const int* row_pos, long out1_pos_ld, void* stream) {
     const int vec = (a.dtype == OMR_BF16 || a.w8) ? 8 : 4;
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.K % vec || a.K > 2048 || (!a.w && !a.w8) || !a.out0 || a.n0 < 0) return OMR_ERR_ARG;
     if (a.w8 ? (!a.w8_scale || ((uintptr_t)a.w8 & 7)) : (((uintptr_t)a.w & 15) != 0)) return OMR_ERR_ARG;
@@ -278,14 +297,34 @@ extern "C" int omr_decode_linear(const omr_decode_linear_args* ap, void* stream)
     if (a.pro == 3 && (!a.part || a.nsplit < 1 || a.nsplit > MAXSPLIT || a.H < 1 || a.hd < 1 || a.H * a.hd != a.K || a.H * a.nsplit > MAXHS || a.hd % (a.K / 64))) return OMR_ERR_ARG;
     const dim3 grid((unsigned)cdiv(a.N, NOUT), (unsigned)cdiv(a.M, RM)), block(256);
     const size_t shm = (size_t)RM * a.K * sizeof(float);
-    if (a.dtype == OMR_BF16 && a.w8) hipLaunchKernelGGL((decode_linear_kernel<bf16, true>), grid, block, shm, (hipStream_t)stream, a);
-    else if (a.dtype == OMR_F32 && a.w8) hipLaunchKernelGGL((decode_linear_kernel<float, true>), grid, block, shm, (hipStream_t)stream, a);
-    else if (a.dtype == OMR_BF16) hipLaunchKernelGGL((decode_linear_kernel<bf16, false>), grid, block, shm, (hipStream_t)stream, a);
-    else if (a.dtype == OMR_F32) hipLaunchKernelGGL((decode_linear_kernel<float, false>), grid, block, shm, (hipStream_t)stream, a);
-    else return OMR_ERR_UNSUPPORTED;
+    if (a.dtype != OMR_BF16 && a.dtype != OMR_F32) return OMR_ERR_UNSUPPORTED;
+    const LinArgs la = {a, row_pos, out1_pos_ld};
+    auto launch = [&](auto rows_c) {
+        constexpr bool ROWS = decltype(rows_c)::value;
+        if (a.dtype == OMR_BF16 && a.w8) hipLaunchKernelGGL((decode_linear_kernel<bf16, true, ROWS>), grid, block, shm, (hipStream_t)stream, la);
+        else if (a.dtype == OMR_F32 && a.w8) hipLaunchKernelGGL((decode_linear_kernel<float, true, ROWS>), grid, block, shm, (hipStream_t)stream, la);
+        else if (a.dtype == OMR_BF16) hipLaunchKernelGGL((decode_linear_kernel<bf16, false, ROWS>), grid, block, shm, (hipStream_t)stream, la);
+        else hipLaunchKernelGGL((decode_linear_kernel<float, false, ROWS>), grid, block, shm, (hipStream_t)stream, la);
+    };
+    if (row_pos) launch(std::true_type());
+    else launch(std::false_type());
     if (a.amax_idx) hipLaunchKernelGGL(decode_pick_kernel, dim3((unsigned)a.M), dim3(64), 0, (hipStream_t)stream, a.amax_part, (int)grid.x, a.amax_idx, a.amax_val);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
+}
+
+// the model widths the row kernel takes (8 launches per layer); any other takes one kernel per step of the layer
+bool takes_row_kernel(const omr_decode_desc& d) {
+    const int smax = d.S > d.max_len ? d.S : d.max_len, splits_max = (smax + 255) / 256 < MAXSPLIT ? (smax + 255) / 256 : MAXSPLIT;
+    return (d.d == 128 || d.d == 256 || d.d == 512) && d.ff <= 2048 && d.ff % (16 * ((d.dtype == OMR_BF16 || d.fp8) ? 8 : 4)) == 0 &&
+           d.nhead * splits_max <= MAXHS;
+}
+
+}  // namespace
+
+extern "C" int omr_decode_linear(const omr_decode_linear_args* ap, void* stream) {
+    if (!ap) return OMR_ERR_ARG;
+    return decode_linear_impl(*ap, nullptr, 0, stream);
 }
 
 extern "C" long omr_decode_workspace_bytes(const omr_decode_desc* d) {
@@ -296,9 +335,10 @@ extern "C" long omr_decode_workspace_bytes(const omr_decode_desc* d) {
 // mem_len (nullable, device int32 [B / kv_group]): row b's cross-attention sees the first mem_len[b / kv_group] of the d.S memory
 // rows (ragged batch).  kv_group: that many consecutive rows share one cross-attention K|V slot (the hypotheses of one input of
 // a batched beam search); 1 everywhere else.  logits_at (nullable): where the last position's fp32 logits [B][ldv] lie in the
-// workspace, for a caller that consumes them in place.
+// workspace, for a caller that consumes them in place.  pos (nullable, device int32 [B]): the per-row-position form
+// (omr_decode_steps_rows) -- row b runs positions pos[b] + pos_off + s, and t0 is the LARGEST of those first positions.
 static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tokens, int t0, int n_steps, long* out_tokens, float* out_top1,
-                        float* last_logits, void* stream, int kv_group = 1, float** logits_at = nullptr) {
+                        float* last_logits, void* stream, int kv_group = 1, float** logits_at = nullptr, const int* pos = nullptr, int pos_off = 0) {
     if (!dp || !tokens || n_steps < 1 || t0 < 0) return OMR_ERR_ARG;
     const omr_decode_desc& d = *dp;
     if (d.B <= 0 || d.L <= 0 || d.d <= 0 || d.d % d.nhead || d.V <= 0 || d.ldv < d.V || d.ldv % 8) return OMR_ERR_ARG;
@@ -327,24 +367,32 @@ static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tok
     // three add + LayerNorm, the merge of the key-split attention) is folded into the loading of the NEXT linear's input rows
     // (omr_decode_linear prologues); the residual stream alternates between two buffers because the workgroup that stores a
     // freshly normalised row runs beside workgroups still reading the previous one.
-    const int smax = d.S > d.max_len ? d.S : d.max_len, splits_max = (smax + 255) / 256 < MAXSPLIT ? (smax + 255) / 256 : MAXSPLIT;
-    if ((dm == 128 || dm == 256 || dm == 512) && d.ff <= 2048 && d.ff % (16 * ((dt == OMR_BF16 || d.fp8) ? 8 : 4)) == 0 && d.nhead * splits_max <= MAXHS) {
+    if (pos && (!takes_row_kernel(d) || kv_group != 1)) return OMR_ERR_UNSUPPORTED;
+    if (takes_row_kernel(d)) {
         const long* tok_in = tokens;
+        int *tpos = nullptr, *tstart = nullptr, *tcount = nullptr;
+        if (pos) {
+            tpos = w.rows_tab; tstart = tpos + (size_t)B * d.max_len; tcount = tstart + (size_t)B * d.max_len;
+            hipLaunchKernelGGL(decode_rows_tables_kernel, dim3((unsigned)cdiv((long)B * n_steps, 256)), dim3(256), 0, (hipStream_t)stream, pos, pos_off, B,
+                               n_steps, d.max_len, d.window, tpos, tstart, tcount);
+        }
         for (int s = 0; s < n_steps; ++s) {
-            const int t = t0 + s;
+            const int t = t0 + s;                                                   // per-row positions: the furthest row's
+            const int* rp = pos ? tpos + (size_t)s * B : nullptr;
             const int lo = (d.window > 0 && t - d.window > 0) ? t - d.window : 0;  // banded causal mask = a key range (decoder.py:213-214)
             char* xa = w.x; char* xb = w.x2;                                        // xa: residual stream entering the sub-layer
             auto lin = [&](int pro, const void* x, const void* res, const float* g, const float* bt, void* xn_out, const float* part, int nsplit,
                            const void* wmat, const float* bias, int N, int K, int relu, void* out0, long ld0, int n0, void* out1, long ld1,
                            float* out32, long* amax_idx = nullptr, float* amax_val = nullptr, const unsigned char* w8 = nullptr,
-                           const float* s8 = nullptr) -> int {
+                           const float* s8 = nullptr, const int* row_pos = nullptr) -> int {
                 omr_decode_linear_args a = {};
                 a.w8 = d.fp8 ? w8 : nullptr; a.w8_scale = d.fp8 ? s8 : nullptr;
                 a.amax_idx = amax_idx; a.amax_val = amax_val; a.amax_part = amax_idx ? w.apart : nullptr;
                 a.dtype = dt; a.pro = pro; a.M = B; a.N = N; a.K = K; a.relu = relu; a.n0 = n0; a.nsplit = nsplit; a.H = d.nhead; a.hd = hd; a.vocab = d.V;
                 a.eps = 1e-5f; a.x = x; a.ldx = K; a.res = res; a.ldres = K; a.gamma = g; a.beta = bt; a.xn_out = xn_out;
-                a.tokens = tok_in; a.emb = d.emb; a.pe_row = d.pe + (size_t)t * dm; a.part = part;
+                a.tokens = tok_in; a.emb = d.emb; a.pe_row = row_pos ? d.pe : d.pe + (size_t)t * dm; a.part = part;
                 a.w = wmat; a.bias = bias; a.out0 = out0; a.ld0 = ld0; a.out1 = out1; a.ld1 = ld1; a.out32 = out32; a.ld32 = d.ldv;
+                if (row_pos) return decode_linear_impl(a, row_pos, 2L * dm, stream);
                 return omr_decode_linear(&a, stream);
             };
             const float *pg = nullptr, *pb = nullptr;                               // norm3 of the previous layer, still to be applied
@@ -353,14 +401,19 @@ static int decode_steps(const omr_decode_desc* dp, const int* mem_len, long* tok
                 const unsigned char* const* W8l = d.fp8 ? d.layer_w8 + (size_t)l * OMR_DECODE_LAYER_FP8 : nullptr;     // e4m3 rows + row scales of the
                 const float* const* S8l = d.fp8 ? d.layer_s8 + (size_t)l * OMR_DECODE_LAYER_FP8 : nullptr;             // layer's six matrices
                 char* cache_l = (char*)d.self_kv + ((size_t)l * B * d.max_len) * 2 * dm * es;
-                char* kv_row = cache_l + (size_t)t * 2 * dm * es;
+                char* kv_row = pos ? cache_l : cache_l + (size_t)t * 2 * dm * es;      // per-row positions: the kernel adds each row's
                 // q | k|v projection of the position: q -> w.q, k|v straight into row t of the cache.  Its input is the
                 // embedding (layer 0) or norm3(x + ffn) of the previous layer; either way the rows land in xb
-                if (l == 0) TRY(lin(2, nullptr, nullptr, nullptr, nullptr, xb, nullptr, 0, Wl[0], (const float*)Wl[1], 3 * dm, dm, 0, w.q, dm, dm, kv_row, (long)d.max_len * 2 * dm, nullptr, nullptr, nullptr, W8l ? W8l[0] : nullptr, S8l ? S8l[0] : nullptr));
-                else TRY(lin(1, w.proj, xa, pg, pb, xb, nullptr, 0, Wl[0], (const float*)Wl[1], 3 * dm, dm, 0, w.q, dm, dm, kv_row, (long)d.max_len * 2 * dm, nullptr, nullptr, nullptr, W8l ? W8l[0] : nullptr, S8l ? S8l[0] : nullptr));
+                if (l == 0) TRY(lin(2, nullptr, nullptr, nullptr, nullptr, xb, nullptr, 0, Wl[0], (const float*)Wl[1], 3 * dm, dm, 0, w.q, dm, dm, kv_row, (long)d.max_len * 2 * dm, nullptr, nullptr, nullptr, W8l ? W8l[0] : nullptr, S8l ? S8l[0] : nullptr, rp));
+                else TRY(lin(1, w.proj, xa, pg, pb, xb, nullptr, 0, Wl[0], (const float*)Wl[1], 3 * dm, dm, 0, w.q, dm, dm, kv_row, (long)d.max_len * 2 * dm, nullptr, nullptr, nullptr, W8l ? W8l[0] : nullptr, S8l ? S8l[0] : nullptr, rp));
                 { char* tsw = xa; xa = xb; xb = tsw; }
                 const char* k0 = cache_l + (size_t)lo * 2 * dm * es;
                 int ns = 1;
+                if (pos)        // row b over its own keys [lo_b, t_b]; the split plan is that of the furthest row's count
+                    TRY(attn_fwd_split_partials_rows(dt, w.q, cache_l, cache_l + (size_t)dm * es, w.o, w.lse, dm, 2 * dm, 2 * dm, dm, dm,
+                                                     (long)d.max_len * 2 * dm, (long)d.max_len * 2 * dm, dm, B, d.nhead, 1, t + 1 - lo, hd,
+                                                     tcount + (size_t)s * B, tstart + (size_t)s * B, w.split, w.split_floats, &ns, stream));
+                else
                 TRY(omr_attn_fwd_split_partials(dt, w.q, k0, k0 + (size_t)dm * es, w.o, w.lse, dm, 2 * dm, 2 * dm, dm, dm, (long)d.max_len * 2 * dm,
                                                 (long)d.max_len * 2 * dm, dm, B, d.nhead, 1, t + 1 - lo, hd, w.split, w.split_floats, &ns, stream));
                 TRY(lin(ns > 1 ? 3 : 0, w.o, nullptr, nullptr, nullptr, nullptr, w.split, ns, Wl[2], (const float*)Wl[3], dm, dm, 0, w.proj, dm, dm, nullptr, 0, nullptr, nullptr, nullptr, W8l ? W8l[1] : nullptr, S8l ? S8l[1] : nullptr));
@@ -464,6 +517,17 @@ extern "C" int omr_decode_steps_varlen(const omr_decode_desc* dp, const int* mem
     return decode_steps(dp, mem_len, tokens, t0, n_steps, out_tokens, out_top1, last_logits, stream);
 }
 
+/* omr_decode_steps_varlen for a state whose rows each sit at their own position (continuous batching of the reference's greedy
+ * loop, src/transformer/model.py:171-199): row b runs positions pos[b] .. pos[b] + n_steps - 1.  Whether the descriptor takes
+ * this entry is answered first, so that a caller can ask with NULL pointers. */
+extern "C" int omr_decode_steps_rows(const omr_decode_desc* dp, const int* mem_len, const int* pos, int t_max, long* tokens, int n_steps,
+                                     long* out_tokens, float* out_top1, float* last_logits, void* stream) {
+    if (!dp) return OMR_ERR_ARG;
+    if (!takes_row_kernel(*dp)) return OMR_ERR_UNSUPPORTED;
+    if (!pos || t_max < 0) return OMR_ERR_ARG;
+    return decode_steps(dp, mem_len, tokens, t_max, n_steps, out_tokens, out_top1, last_logits, stream, 1, nullptr, pos);
+}
+
 /* Weighted late fusion (src/multimodal/weighted_multimodal/test.py:21-70) as ONE host call per run of tokens: two unimodal
  * models with their own KV caches decode the same prefixes in lock-step; per position both descriptors run their step for all
  * B rows (decode_steps without a pick: fp32 logits only), ONE omr_weighted_argmax_rows launch mixes the two softmaxes of every
@@ -480,6 +544,26 @@ extern "C" int omr_weighted_decode_steps_varlen(const omr_decode_desc* da, const
     for (int s = 0; s < n_steps; ++s) {
         TRY(decode_steps(da, mem_len_a, tokens, t0 + s, 1, nullptr, nullptr, logits_a, stream));
         TRY(decode_steps(db, mem_len_b, tokens, t0 + s, 1, nullptr, nullptr, logits_b, stream));
+        TRY(omr_weighted_argmax_rows(logits_a, da->ldv, logits_b, db->ldv, B, da->V, alpha, out_tokens + (size_t)s * B,
+                                     out_prob ? out_prob + (size_t)s * B : nullptr, tokens, stream));
+    }
+    return OMR_OK;
+}
+
+/* omr_weighted_decode_steps_varlen over rows at their own positions: one pos / t_max for both models (the two models of a pair
+ * are always at the same position), per position the per-row-position step of each model (omr_decode_steps_rows) */
+extern "C" int omr_weighted_decode_steps_rows(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
+                                              const int* pos, int t_max, float alpha, long* tokens, int n_steps, long* out_tokens,
+                                              float* out_prob, float* logits_a, float* logits_b, void* stream) {
+    if (!da || !db) return OMR_ERR_ARG;
+    if (!takes_row_kernel(*da) || !takes_row_kernel(*db)) return OMR_ERR_UNSUPPORTED;
+    if (!pos || !tokens || !out_tokens || !logits_a || !logits_b || n_steps < 1 || t_max < 0) return OMR_ERR_ARG;
+    if (da->B < 1 || da->B != db->B || da->V != db->V) return OMR_ERR_ARG;
+    if (t_max + n_steps > da->max_len || t_max + n_steps > db->max_len) return OMR_ERR_ARG;      // refuse before the first launch
+    const int B = da->B;
+    for (int s = 0; s < n_steps; ++s) {
+        TRY(decode_steps(da, mem_len_a, tokens, t_max + s, 1, nullptr, nullptr, logits_a, stream, 1, nullptr, pos, s));
+        TRY(decode_steps(db, mem_len_b, tokens, t_max + s, 1, nullptr, nullptr, logits_b, stream, 1, nullptr, pos, s));
         TRY(omr_weighted_argmax_rows(logits_a, da->ldv, logits_b, db->ldv, B, da->V, alpha, out_tokens + (size_t)s * B,
                                      out_prob ? out_prob + (size_t)s * B : nullptr, tokens, stream));
     }

@@ -147,6 +147,11 @@ int attn_fwd_split_partials_varlen(int dtype, const void* q, const void* k, cons
                                    long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
                                    const int* kv_len, float* split_ws, long split_ws_floats, int* nsplit, void* stream, int kv_group = 1);
 
+// The same with a per-row first key (omr_attn_fwd_split_rows' rule: the key-split kernel for every S).
+int attn_fwd_split_partials_rows(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                                 long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                                 const int* kv_len, const int* kv_start, float* split_ws, long split_ws_floats, int* nsplit, void* stream);
+
 // Top-k log-probabilities of ONE row by a group of 256 threads (tid 0..255; every thread of the WORKGROUP must call it: it
 // synchronises with __syncthreads): emit(j, index, log_softmax(x)[index]) for the j-th largest, j < k, ties towards the smaller
 // index, with the same values in every thread.  A max / sum-exp pass, then k selection passes over the candidates that come

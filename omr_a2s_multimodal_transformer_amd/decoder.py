@@ -289,6 +289,23 @@ class Decoder(nn.Module):
             return DecodeState(self, self.memory_list(memory), self._compute_dtype())
         return DecodeState(self, self._in_compute_dtype(memory), self._compute_dtype())
 
+    def takes_slot_state(self, capacity: int = 0) -> bool:
+        """Whether this decoder's widths take a decode state with slots (omr_decode_steps_rows: the row kernel of
+        csrc/decode.hip) for memories of up to `capacity` tokens (0: the longest a ragged state takes); the library is asked, with a
+        descriptor that carries the widths only."""
+        layer = self.transformer_decoder.layers[0]
+        ds = _DecodeDesc()
+        ds.dtype, ds.d, ds.nhead, ds.ff = dtype_code(self._compute_dtype()), self.embedding.weight.shape[1], layer.self_attn.num_heads, layer.linear1.weight.shape[0]
+        ds.fp8, ds.max_len, ds.S = int(bool(getattr(self, "fp8_weights", False))), self.pos_1d.pe.shape[1], capacity or MAX_RAGGED_MEMORY
+        return lib().query("omr_decode_steps_rows", ctypes.byref(ds), None, None, 0, None, 0, None, None, None, None) != -3
+
+    @torch.no_grad()
+    def init_slot_decode(self, rows: int, capacity: int, device, sos: int = 2) -> "SlotDecodeState":
+        """A decode state of `rows` slots for memories of up to `capacity` tokens each (continuous batching)."""
+        if not self.takes_slot_state(capacity):
+            raise RuntimeError("init_slot_decode: this decoder's widths do not take omr_decode_steps_rows")
+        return SlotDecodeState(self, rows, capacity, self._compute_dtype(), device, sos)
+
     @torch.no_grad()
     def init_beam_decode(self, memory, beam: int, sos: int = 2, eos: int = 1) -> "BeamDecodeState":
         """The state of a beam search over N inputs at once, `beam` hypotheses each (omr_beam_decode_steps).  memory: [1, S, d],
@@ -414,20 +431,32 @@ class DecodeState:
         # holds the layers back to back (Decoder._cross_kv_pack), else one GEMM per layer into its column block.  Ragged: one
         # GEMM per memory into the first S_b rows of its slot -- the very GEMM a batch-size-1 state of that memory runs
         self.cross_kv = torch.empty((n_mem, self.S, L * 2 * d), dtype=dt, device=dev)
-        pack = dec._cross_kv_pack(dt)
         for b, mem2 in enumerate(mems):
-            kv2 = self.cross_kv[b, :mem2.shape[0]] if ragged else self.cross_kv.view(-1, L * 2 * d)
-            if pack is not None:
-                K.gemm_row_groups(mem2, pack["w"], kv2, mem2.shape[0], L * 2 * d, d, bias=pack["b"], group=(2 * d, 3 * d, d, 1))
-            else:
-                for li, layer in enumerate(layers):
-                    mha = layer.multihead_attn
-                    w = Fn.wt(mha.in_proj_weight, dt)
-                    K.gemm(mem2, w[d:], bias=mha.in_proj_bias.omr_phys[d:], out=kv2[:, li * 2 * d:(li + 1) * 2 * d])
+            self._project(mem2, self.cross_kv[b, :mem2.shape[0]] if ragged else self.cross_kv.view(-1, L * 2 * d))
         self.cross_bs = self.S * L * 2 * d
         # memory b's length (device int32), or None: every row sees all S rows
         self.mem_len = torch.tensor([m.shape[0] for m in mems], dtype=torch.int32).to(dev) if ragged else None
         self.self_kv = torch.empty((L, self.B, self.max_len, 2 * d), dtype=dt, device=dev)
+        self._weights()
+        self.desc = _DecodeDesc()
+        self._bind()
+
+    def _project(self, mem2: torch.Tensor, kv2: torch.Tensor) -> None:
+        """The cross-attention K|V of every layer of memory rows mem2 [n, d] into kv2 [n, L*2d]."""
+        dec, dt, L, d = self.dec, self.dtype, self.L, self.d
+        pack = dec._cross_kv_pack(dt)
+        if pack is not None:
+            K.gemm_row_groups(mem2, pack["w"], kv2, mem2.shape[0], L * 2 * d, d, bias=pack["b"], group=(2 * d, 3 * d, d, 1))
+        else:
+            for li, layer in enumerate(dec.transformer_decoder.layers):
+                mha = layer.multihead_attn
+                w = Fn.wt(mha.in_proj_weight, dt)
+                K.gemm(mem2, w[d:], bias=mha.in_proj_bias.omr_phys[d:], out=kv2[:, li * 2 * d:(li + 1) * 2 * d])
+
+    def _weights(self) -> None:
+        """The host arrays of device pointers the descriptor carries (and the fp8 copies of the matrices)."""
+        dec, dt = self.dec, self.dtype
+        layers = dec.transformer_decoder.layers
 
         def pointer(p):            # matrices in the compute dtype, vectors (biases, LayerNorm) fp32
             return (Fn.wt(p, dt) if p.dim() >= 2 else p.omr_phys).data_ptr()
@@ -453,8 +482,6 @@ class DecodeState:
             self._layer_w8 = (ctypes.c_void_p * len(pairs))(*[a for a, _ in pairs])
             self._layer_s8 = (ctypes.c_void_p * len(pairs))(*[b for _, b in pairs])
             self._head8 = quantised(dec.out_layer.weight)
-        self.desc = _DecodeDesc()
-        self._bind()
 
     def _bind(self) -> None:
         """(Re)fill the descriptor after B / the buffers changed."""
@@ -529,6 +556,88 @@ class DecodeState:
         self._steps(self.t, n_steps, toks, top1, None)
         self.t += n_steps
         return toks, top1
+
+
+class SlotDecodeState(DecodeState):
+    """A decode state of `rows` SLOTS whose rows each sit at their own position (omr_decode_steps_rows): the state behind
+    continuous batching of greedy evaluation (evaluation.decode_stream).  A slot takes one input at a time: admit() projects that
+    memory's cross-attention K|V into the slot with the GEMM a batch-size-1 state of it runs and puts the row back to position
+    0 and <sos>; what the slot's previous occupant left in the caches is never read (a row sees its own positions and its own
+    memory length only).  capacity: the longest memory a slot will hold.  pos / mem_len live on the device and are uploaded
+    once per run_rows call, from the host lists this state keeps."""
+
+    def __init__(self, dec: "Decoder", rows: int, capacity: int, dt: torch.dtype, device, sos: int):
+        if rows < 1 or capacity < 1:
+            raise ValueError(f"slot decode state: rows {rows} and capacity {capacity} must be >= 1")
+        self.dec, self.dtype, self.t, self.sos = dec, dt, 0, sos
+        self.L, self.d = len(dec.transformer_decoder.layers), dec.embedding.weight.shape[1]
+        self.B, self.S = rows, capacity
+        self.max_len = dec.pos_1d.pe.shape[1]
+        self.V, self.ldv = dec.output_size, K.round_up(dec.output_size, 8)
+        L, d = self.L, self.d
+        self.cross_kv = torch.empty((rows, capacity, L * 2 * d), dtype=dt, device=device)
+        self.cross_bs = capacity * L * 2 * d
+        self.self_kv = torch.empty((L, rows, self.max_len, 2 * d), dtype=dt, device=device)
+        self._mem_len_h, self._pos_h, self._live = [1] * rows, [0] * rows, [False] * rows
+        self.mem_len = torch.ones(rows, dtype=torch.int32, device=device)
+        self.pos = torch.zeros(rows, dtype=torch.int32, device=device)
+        self.admitted = 0                      # inputs admitted so far (more than `rows`: slots were refilled)
+        self.positions = 0                     # positions run so far (each for all slots)
+        self._weights()
+        self.desc = _DecodeDesc()
+        self._bind()
+        self.tok.fill_(sos)
+
+    def admit(self, slot: int, memory: Optional[torch.Tensor]) -> None:
+        """Give `slot` to the input with this memory ([S_b, d] in the compute dtype), or to nobody (None): an idle slot runs
+        from position 0 at every call and its output is dropped."""
+        self._pos_h[slot] = 0
+        self._live[slot] = memory is not None
+        if memory is None:
+            return
+        n = memory.shape[0]
+        if memory.dim() != 2 or memory.shape[1] != self.d or not 1 <= n <= self.S or memory.dtype != self.dtype:
+            raise ValueError(f"slot decode state: a memory of shape {tuple(memory.shape)} {memory.dtype} does not fit a slot of [{self.S}, {self.d}] {self.dtype}")
+        self._project(memory, self.cross_kv[slot, :n])
+        self._mem_len_h[slot] = n
+        self.tok[slot:slot + 1].fill_(self.sos)
+        self.admitted += 1
+
+    def furthest(self) -> int:
+        """The largest position of a slot that holds an input (idle slots start over at every call)."""
+        return max((p for p, live in zip(self._pos_h, self._live) if live), default=0)
+
+    def begin(self, n_steps: int) -> int:
+        """Upload the rows' positions and memory lengths for a call of n_steps positions -> the largest position."""
+        for b in range(self.B):
+            if not self._live[b]:
+                self._pos_h[b] = 0
+        t_max = self.furthest()
+        if n_steps < 1 or t_max + n_steps > self.max_len:
+            raise RuntimeError("decode_step beyond max_seq_len (positional-encoding table exhausted)")
+        self.pos.copy_(torch.tensor(self._pos_h, dtype=torch.int32))
+        self.mem_len.copy_(torch.tensor(self._mem_len_h, dtype=torch.int32))
+        return t_max
+
+    def advance(self, n_steps: int) -> None:
+        self.positions += n_steps
+        self._pos_h = [p + n_steps for p in self._pos_h]
+
+    def run_rows(self, n_steps: int):
+        """n_steps further positions of every slot -> (tokens int64 [n_steps, rows], their fp32 top-1 logits [n_steps, rows]),
+        on the device; the chosen tokens reach the next position there."""
+        t_max = self.begin(n_steps)
+        toks = torch.empty((n_steps, self.B), dtype=torch.int64, device=self.tok.device)
+        top1 = torch.empty((n_steps, self.B), dtype=torch.float32, device=self.tok.device)
+        lib().call("omr_decode_steps_rows", ctypes.byref(self.desc), ptr(self.mem_len), ptr(self.pos), t_max, ptr(self.tok), n_steps, ptr(toks),
+                   ptr(top1), None, cur_stream())
+        self.advance(n_steps)
+        return toks, top1
+
+    def _no_lockstep(self, *_a, **_k):
+        raise RuntimeError("a slot decode state has no common position: use admit / run_rows")
+
+    run = step_logits = rewind = share_memory_between = reorder_rows = _no_lockstep
 
 
 class _BeamDesc(ctypes.Structure):

@@ -5,11 +5,37 @@ sequence equals the batch-size-1 loop's (`_greedy`) for that input.  This module
 the read-back loop of the greedy decodes and the backtrack of the batched beam search."""
 from __future__ import annotations
 
+import contextvars
+import functools
 from typing import Callable, List, Sequence, Tuple
 
 from .decoder import takes_ragged_state
 
 WINDOW_BATCHES = 8          # inputs are encoded and sorted by memory length a window of 8 * batch_size at a time
+
+
+_REFILL = contextvars.ContextVar("omr_refill", default=False)
+
+
+def refill_enabled() -> bool:
+    """Whether the evaluation call under way asked for continuous batching (`refill_option`)."""
+    return _REFILL.get()
+
+
+def refill_option(fn):
+    """Gives an evaluation entry point (`predict` / `predict_with_probs` / `evaluate` of both model classes, weighted_predict /
+    weighted_evaluate, sw_predict / sw_evaluate) the keyword `refill: bool = False`.  The function's own parameter list -- part
+    of the public surface the tests pin -- stays as it is, like `beam` (model._beam_option); the flag holds for the duration
+    of the call and the decode loops ask `refill_enabled()`.  An evaluation call made inside another one (sw_predict calls
+    predict_with_probs) without the keyword keeps the outer call's choice."""
+    @functools.wraps(fn)
+    def call(*args, refill=None, **kwargs):
+        token = _REFILL.set(_REFILL.get() if refill is None else bool(refill))
+        try:
+            return fn(*args, **kwargs)
+        finally:
+            _REFILL.reset(token)
+    return call
 
 
 def plan_groups(lengths: Sequence[int], batch_size: int, window: int = 0) -> Tuple[List[int], List[List[int]]]:
@@ -72,6 +98,58 @@ def decode_rows(step: Callable, rows: int, eos: int, budget: int, sync_every: in
                         values[b].append(float(top1[s][b]))
                     done[b] = t == eos
         left -= len(toks)
+    return out, values
+
+
+def stream_order(lengths: Sequence[int]) -> List[int]:
+    """Admission order of decode_stream: the indices of `lengths` by decreasing length (ties: input order), so that the rows
+    running side by side have similar memories.  The order affects speed only, never results."""
+    return sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
+
+
+def decode_stream(step: Callable, admit: Callable, order: Sequence[int], rows: int, eos: int, budget: int, sync_every: int,
+                  want_probs: bool = False) -> Tuple[List[List[int]], List[List[float]]]:
+    """decode_rows with a QUEUE (continuous batching): `rows` slots decode the inputs `order` (a permutation of
+    0 .. len(order) - 1, admitted in that order) -> (token ids, top-1 values) per INPUT index, each cut after its <eos> (kept)
+    or after `budget` positions of that input.  After every chunk the finished rows are cut, and each freed slot goes to the
+    next waiting input; the loop ends when the queue is empty and every slot is done.
+    admit(slot, index) hands `slot` to input `index`, which starts at position 0; admit(slot, None) leaves it idle (nothing
+    waits; whatever it computes is dropped).  step(n) runs n further positions of all slots and returns (tokens, values) as host
+    lists [m][rows], 1 <= m <= n -- values only with want_probs, else None; it raises when it cannot advance.  n never takes a
+    live row past its budget.  Like decode_rows this touches host lists and the two callbacks only."""
+    n_in = len(order)
+    if sorted(order) != list(range(n_in)):
+        raise ValueError("decode_stream: `order` must be a permutation of the input indices")
+    if rows < 1 or sync_every < 1:
+        raise ValueError(f"decode_stream: rows {rows} and sync_every {sync_every} must be >= 1")
+    out: List[List[int]] = [[] for _ in range(n_in)]
+    values: List[List[float]] = [[] for _ in range(n_in)]
+    if budget <= 0:
+        return out, values
+    waiting = list(order)[::-1]
+    holds: List = [None] * rows                       # the input each slot decodes
+    used = [0] * rows                                  # positions of that input so far
+
+    def refill(b: int) -> None:
+        holds[b] = waiting.pop() if waiting else None
+        used[b] = 0
+        admit(b, holds[b])
+
+    for b in range(rows):
+        refill(b)
+    while any(i is not None for i in holds):
+        live = [b for b in range(rows) if holds[b] is not None]
+        toks, top1 = step(min(sync_every, min(budget - used[b] for b in live)))
+        for b in live:
+            i = holds[b]
+            for s, row in enumerate(toks):
+                out[i].append(row[b])
+                if want_probs:
+                    values[i].append(float(top1[s][b]))
+                used[b] += 1
+                if row[b] == eos or used[b] >= budget:
+                    refill(b)
+                    break
     return out, values
 
 

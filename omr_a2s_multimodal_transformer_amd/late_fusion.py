@@ -19,6 +19,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import lib
+from .evaluation import refill_option
 
 START, END, GAP = "¡", "!", "-"          # the reference's sentinel / gap symbols (smith_waterman.py:5,31-32)
 
@@ -106,17 +107,20 @@ def fuse(r: List[str], r_prob: List[float], q: List[str], q_prob: List[float], m
     return [t for t in fused if t not in (START, END)]          # undo_swalign_preprocess (smith_waterman.py:162-173)
 
 
+@refill_option
 def sw_predict(pairs: Iterable, img_model, audio_model, batch_size: int = 32, match: int = 2, mismatch: int = -1,
                gap_penalty: int = -1) -> List[List[str]]:
     """test.py:113-157 over (image, audio) pairs ([1, C, H, W] each, sizes free): the fused prediction of every pair, in input
     order.  Each model decodes all of its inputs batch_size memories at a time (grouping its own memory lengths); every fused
-    sequence equals fuse() of the two get_pred_seq_and_pred_prob_seq results of that pair."""
+    sequence equals fuse() of the two get_pred_seq_and_pred_prob_seq results of that pair.  Keyword `refill` (default False,
+    evaluation.refill_option): both models' predict_with_probs decode with continuous batching; same values."""
     pairs = list(pairs)
     r, r_prob = img_model.predict_with_probs((xi for xi, _ in pairs), batch_size)
     q, q_prob = audio_model.predict_with_probs((xa for _, xa in pairs), batch_size)
     return [fuse(ri, rpi, qi, qpi, match, mismatch, gap_penalty) for ri, rpi, qi, qpi in zip(r, r_prob, q, q_prob)]
 
 
+@refill_option
 def sw_evaluate(batches: Iterable, img_model, audio_model, batch_size: int = 32, match: int = 2, mismatch: int = -1,
                 gap_penalty: int = -1) -> Dict[str, float]:
     """test.py:113-161 over `batches` ((xi, xa, y) as the test loader yields them): compute_metrics of sw_predict against the

@@ -20,7 +20,7 @@ from ._lib import lib
 from .config import ModelConfig
 from .decoder import MAX_BEAM, Decoder, MultiheadAttention, _to_dev, takes_ragged_state
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
-from .evaluation import WINDOW_BATCHES, decode_rows, plan_groups
+from .evaluation import WINDOW_BATCHES, decode_rows, decode_stream, plan_groups, refill_enabled, refill_option, stream_order
 from .lightning_shim import LightningModule
 from .metrics import compute_metrics, compute_metrics_sharded
 from .runtime import FlatModuleMixin
@@ -103,6 +103,8 @@ def _beam_option(fn):
 
 class _Base(FlatModuleMixin, LightningModule):
     _decode_beam = 1          # beam width `_predict` decodes with (set by _beam_option for the duration of a call)
+    _refill_sync_every = 8    # positions per read-back of a refilled decode (evaluation.decode_stream); results do not depend on it
+    _refill_state_hook = None  # called with every SlotDecodeState `_greedy_stream` creates, before its first admission (tests)
 
     def _common_init(self, w2i, i2w, ytest_i2w, max_seq_len, attn_window, teacher_forcing_prob, config: Optional[ModelConfig]):
         if isinstance(config, dict):
@@ -230,6 +232,26 @@ class _Base(FlatModuleMixin, LightningModule):
 
         return decode_rows(step, state.B, self.w2i[EOS_TOKEN], self.max_seq_len, sync_every, want_probs)
 
+    def _greedy_stream(self, mems: List[torch.Tensor], rows: int, want_probs: bool = False):
+        """Greedy decode of memories that all take a ragged state through ONE decode state of `rows` slots, a finished row's
+        slot going to the next memory (Decoder.init_slot_decode, evaluation.decode_stream): -> (token ids, top-1 logits) per
+        memory, in the order given, each what `_greedy_state` of that memory alone returns."""
+        mems = self.decoder.memory_list(mems)
+        lens = [m.shape[0] for m in mems]
+        state = self.decoder.init_slot_decode(min(rows, len(mems)), max(lens), mems[0].device, self.w2i[SOS_TOKEN])
+        if self._refill_state_hook is not None:
+            self._refill_state_hook(state)
+
+        def admit(slot: int, i: Optional[int]) -> None:
+            state.admit(slot, None if i is None else mems[i])
+
+        def step(n: int):
+            toks, top1 = state.run_rows(n)
+            top1_h = top1.cpu().tolist() if want_probs else None
+            return toks.cpu().tolist(), top1_h                        # one device sync for the whole chunk
+
+        return decode_stream(step, admit, stream_order(lens), state.B, self.w2i[EOS_TOKEN], self.max_seq_len, self._refill_sync_every, want_probs)
+
     @torch.no_grad()
     def _predict(self, items: Iterable, encode: Callable[[object], torch.Tensor], batch_size: int, want_probs: bool = False):
         """Greedy predictions of inputs of any size, in input order, each equal to `_greedy` of that input alone.  A window
@@ -237,10 +259,16 @@ class _Base(FlatModuleMixin, LightningModule):
         length (evaluation.plan_groups) and decoded group by group as ragged batches of up to batch_size rows.
         want_probs: -> (predictions, the top-1 logits of their positions) like `_greedy(..., want_probs=True)`.
         Called with a beam (`_beam_option`): the words of `beam_search` of every input instead, decoded
-        batch_size // beam inputs at a time (`beam_search_batch`: a group has at most batch_size rows)."""
+        batch_size // beam inputs at a time (`beam_search_batch`: a group has at most batch_size rows).
+        Called with refill=True (evaluation.refill_option; greedy only): the memories of a window that take a ragged state stream through ONE decode state of
+        min(batch_size, count) slots (`_greedy_stream`) instead of running group by group until each group's longest row ends;
+        a decoder whose widths omr_decode_steps_rows does not take decodes in groups as without the flag."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         beam = 1 if want_probs else self._decode_beam          # predict_with_probs takes no beam
+        refill = refill_enabled()
+        if refill and beam > 1:
+            raise ValueError("refill=True decodes greedily: the beam state (two caches, a history table) has no slots to refill")
         if beam > 1:
             rows = max(1, batch_size // beam)
 
@@ -272,6 +300,12 @@ class _Base(FlatModuleMixin, LightningModule):
             singles, groups = plan_groups([m.shape[1] for m in mems], rows)
             for i in singles:
                 out[i], outp[i] = decode_single(mems[i])
+            if refill and groups and self.decoder.takes_slot_state(max(mems[i].shape[1] for g in groups for i in g)):
+                rest = [i for g in groups for i in g]
+                ids, top1 = self._greedy_stream([mems[i] for i in rest], rows, want_probs)
+                for i, seq, t1 in zip(rest, self._words(ids), top1):
+                    out[i], outp[i] = seq, t1
+                groups = []
             for g in groups:                                   # planned: every memory of a group takes a ragged state
                 for i, (seq, top1) in zip(g, decode_group([mems[i] for i in g])):
                     out[i], outp[i] = seq, top1
@@ -469,25 +503,31 @@ class Transformer(_Base):
         assert x.size(0) == 1, "predict takes inputs of batch size 1 ([1, C, H, W]); their sizes may differ"
         return self.encode(x)
 
+    @refill_option
     @_beam_option
     @torch.no_grad()
     def predict(self, xs: Iterable[torch.Tensor], batch_size: int = 32) -> List[List[str]]:
         """Greedy predictions of inputs [1, C, H_b, W_b] of any size, in input order: each equals validation_step's decode
         of that input, decoded batch_size memories at a time.  Keyword `beam` (2 .. 8, `_beam_option`): the words of
-        `beam_search` of each input, batch_size // beam inputs at a time."""
+        `beam_search` of each input, batch_size // beam inputs at a time.  Keyword `refill` (default False, `refill_option`;
+        greedy only): continuous batching, a finished row's slot goes to the next input (`_predict`); same predictions."""
         return self._predict(xs, self._encode_input, batch_size)
 
+    @refill_option
     @torch.no_grad()
     def predict_with_probs(self, xs: Iterable[torch.Tensor], batch_size: int = 32) -> Tuple[List[List[str]], List[List[float]]]:
         """get_pred_seq_and_pred_prob_seq (model.py:226-262) of inputs [1, C, H_b, W_b] of any size, decoded batch_size
-        memories at a time: (words, top-1 logits) per input, in input order, each equal to the batch-size-1 call's."""
+        memories at a time: (words, top-1 logits) per input, in input order, each equal to the batch-size-1 call's.
+        Keyword `refill` (default False, `refill_option`): continuous batching (`_predict`), same values."""
         return self._predict(xs, self._encode_input, batch_size, want_probs=True)
 
+    @refill_option
     @_beam_option
     @torch.no_grad()
     def evaluate(self, batches: Iterable, batch_size: int = 32) -> Dict[str, float]:
         """The metrics of validation_step over `batches` ((x, y) each) followed by on_validation_epoch_end, decoded in batches.
-        Keyword `beam` (2 .. 8, `_beam_option`): the predictions are those of `beam_search`."""
+        Keyword `beam` (2 .. 8, `_beam_option`): the predictions are those of `beam_search`.  Keyword `refill` (default False,
+        `refill_option`; greedy only): continuous batching (`_predict`), same metrics."""
         return self._evaluate(batches, lambda batch: batch[0], batch_size)
 
 
@@ -622,19 +662,23 @@ class MultimodalTransformer(_Base):
         x, _ = self.encoder_forward(xi=xi, xa=xa, xli=None, xla=None, apply_teacher_forcing_modality=False)
         return x
 
+    @refill_option
     @_beam_option
     @torch.no_grad()
     def predict(self, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], batch_size: int = 32) -> List[List[str]]:
         """Greedy predictions of (image, audio) pairs of any size, in input order: each equals validation_step's decode of
         that pair, decoded batch_size memories at a time.  Keyword `beam` (2 .. 8, `_beam_option`): the words of `beam_search`
-        of each pair's memory, batch_size // beam pairs at a time."""
+        of each pair's memory, batch_size // beam pairs at a time.  Keyword `refill` (default False, `refill_option`; greedy
+        only): continuous batching (`_predict`), same predictions."""
         return self._predict(pairs, self._encode_input, batch_size)
 
+    @refill_option
     @_beam_option
     @torch.no_grad()
     def evaluate(self, batches: Iterable, batch_size: int = 32) -> Dict[str, float]:
         """The metrics of validation_step over `batches` ((xi, xa, y) each) followed by on_validation_epoch_end, decoded in
-        batches.  Keyword `beam` (2 .. 8, `_beam_option`): the predictions are those of `beam_search`."""
+        batches.  Keyword `beam` (2 .. 8, `_beam_option`): the predictions are those of `beam_search`.  Keyword `refill` (default
+        False, `refill_option`; greedy only): continuous batching (`_predict`), same metrics."""
         return self._evaluate(batches, lambda batch: (batch[0], batch[1]), batch_size)
 
     ##### MODALITY MIXERS (model.py:644-726)

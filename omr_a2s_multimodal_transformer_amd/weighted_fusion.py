@@ -23,7 +23,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 import torch
 
 from ._lib import cur_stream, lib, ptr
-from .evaluation import WINDOW_BATCHES, decode_rows, plan_pair_groups
+from .evaluation import WINDOW_BATCHES, decode_rows, decode_stream, plan_pair_groups, refill_enabled, refill_option, stream_order
 from .metrics import compute_metrics
 from .synthetic import EOS_TOKEN, SOS_TOKEN
 
@@ -51,6 +51,41 @@ def _decode_lockstep(st_i, st_a, img_model, audio_model, alpha: float, sync_ever
         return toks.cpu().tolist(), None               # one device sync per chunk
 
     ids, _ = decode_rows(step, B, img_model.w2i[EOS_TOKEN], max(img_model.max_seq_len, audio_model.max_seq_len), sync_every)
+    return [[img_model._i2w(t) for t in seq] for seq in ids]
+
+
+def _decode_lockstep_stream(mems_i, mems_a, img_model, audio_model, alpha: float, rows: int, sync_every: int) -> List[List[str]]:
+    """_decode_lockstep with continuous batching: the pairs (mems_i[k], mems_a[k]), all of which take a ragged state, stream
+    through ONE slot decode state per model (Decoder.init_slot_decode); both states hold the same rows at the same positions,
+    so one `pos` serves both (omr_weighted_decode_steps_rows), and a finished pair's slot goes to the next pair
+    (evaluation.decode_stream).  Each sequence equals _decode_lockstep of that pair alone."""
+    sos, dev = img_model.w2i[SOS_TOKEN], mems_i[0].device
+    rows = min(rows, len(mems_i))
+    st_i = img_model.decoder.init_slot_decode(rows, max(m.shape[0] for m in mems_i), dev, sos)
+    st_a = audio_model.decoder.init_slot_decode(rows, max(m.shape[0] for m in mems_a), dev, sos)
+    assert st_i.V == st_a.V, "both models share the vocabulary (test.py:62)"
+    tok = torch.full((rows,), sos, dtype=torch.int64, device=dev)      # the picked tokens stay here, on the device
+
+    def admit(slot: int, k: Optional[int]) -> None:
+        st_i.admit(slot, None if k is None else mems_i[k])
+        st_a.admit(slot, None if k is None else mems_a[k])
+        tok[slot:slot + 1].fill_(sos)
+
+    def step(n: int):
+        n = min(n, st_i.max_len - st_i.furthest(), st_a.max_len - st_a.furthest())
+        if n <= 0:                                     # a live row outgrew the shorter positional table
+            raise RuntimeError(_EXHAUSTED)
+        t_max = st_i.begin(n)
+        st_a.begin(n)
+        toks = torch.empty((n, rows), dtype=torch.int64, device=dev)
+        lib().call("omr_weighted_decode_steps_rows", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
+                   ptr(st_i.pos), t_max, float(alpha), ptr(tok), n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
+        st_i.advance(n)
+        st_a.advance(n)
+        return toks.cpu().tolist(), None               # one device sync per chunk
+
+    order = stream_order([mi.shape[0] + ma.shape[0] for mi, ma in zip(mems_i, mems_a)])
+    ids, _ = decode_stream(step, admit, order, rows, img_model.w2i[EOS_TOKEN], max(img_model.max_seq_len, audio_model.max_seq_len), sync_every)
     return [[img_model._i2w(t) for t in seq] for seq in ids]
 
 
@@ -82,12 +117,15 @@ def _alphas(alpha) -> Tuple[List[float], bool]:
 def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[float], batch_size: int, sync_every: int,
                       chunk: int = 16) -> List[List[List[str]]]:
     """-> one prediction list per alpha.  Every pair is encoded once per model and every group's (or single's) decode states
-    are built once; each alpha decodes from position 0 again (DecodeState.rewind)."""
+    are built once; each alpha decodes from position 0 again (DecodeState.rewind).  Called with refill=True (evaluation.refill_option): the pairs of a window that take a
+    ragged state stream through one slot state per model instead (_decode_lockstep_stream), once per alpha over the kept
+    memories -- the cross-attention K|V of a pair are projected again on every admission."""
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     if sync_every < 1:
         raise ValueError(f"sync_every must be >= 1, got {sync_every}")
     _check_models(img_model, audio_model)
+    refill = refill_enabled()
     it = iter(pairs)
     preds: List[List[List[str]]] = [[] for _ in alphas]
     while True:
@@ -102,6 +140,15 @@ def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[floa
         singles, groups = plan_pair_groups([m.shape[1] for m in mems_i], [m.shape[1] for m in mems_a], batch_size)
         # a single: the pair alone over two batch-size-1 states, `chunk` positions per read-back like weighted_prediction
         plans = [([i], mems_i[i], mems_a[i], chunk) for i in singles]
+        rest = [i for g in groups for i in g]
+        if refill and rest and img_model.decoder.takes_slot_state(max(mems_i[i].shape[1] for i in rest)) and \
+                audio_model.decoder.takes_slot_state(max(mems_a[i].shape[1] for i in rest)):
+            mi = img_model.decoder.memory_list([mems_i[i] for i in rest])
+            ma = audio_model.decoder.memory_list([mems_a[i] for i in rest])
+            for k, alpha in enumerate(alphas):
+                for i, seq in zip(rest, _decode_lockstep_stream(mi, ma, img_model, audio_model, alpha, batch_size, sync_every)):
+                    out[k][i] = seq
+            groups = []
         plans += [(g, [mems_i[i] for i in g], [mems_a[i] for i in g], sync_every) for g in groups]
         for idx, mi, ma, every in plans:
             st_i = img_model.decoder.init_decode(mi)
@@ -117,21 +164,26 @@ def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[floa
         del mems_i, mems_a
 
 
+@refill_option
 def weighted_predict(pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], img_model, audio_model, alpha: Union[float, Sequence[float]] = 0.5,
                      batch_size: int = 32, sync_every: int = 8):
     """Weighted predictions of (image, audio) pairs ([1, C, H, W] each, sizes free), in input order: each equals
     weighted_prediction(xi, xa, img_model, audio_model, alpha).  A window of WINDOW_BATCHES * batch_size pairs at a time is
     encoded at batch size 1 by each model, grouped by evaluation.plan_pair_groups and decoded group by group, both models in
     lock-step over ragged batches of up to batch_size rows.  `alpha` may be a sequence (the usual tuning sweep): the result
-    is then {alpha: predictions}, with the encoders and the cross-attention projections run once, not once per alpha."""
+    is then {alpha: predictions}, with the encoders and the cross-attention projections run once, not once per alpha.
+    Keyword `refill` (default False, `refill_option`): continuous batching -- a finished pair's slot goes to the next pair of the window (_decode_lockstep_stream);
+    same predictions."""
     alphas, many = _alphas(alpha)
     preds = _weighted_predict(pairs, img_model, audio_model, alphas, batch_size, sync_every)
     return dict(zip(alphas, preds)) if many else preds[0]
 
 
+@refill_option
 def weighted_evaluate(batches: Iterable, img_model, audio_model, alpha: Union[float, Sequence[float]] = 0.5, batch_size: int = 32):
     """weighted_multimodal/test.py:154-172 over `batches` ((xi, xa, y) as the test loader yields them): compute_metrics of the
-    weighted predictions against the ytest_i2w-decoded targets (without <sos>); {alpha: metrics} for a sequence of alphas."""
+    weighted predictions against the ytest_i2w-decoded targets (without <sos>); {alpha: metrics} for a sequence of alphas.
+    Keyword `refill`: as in weighted_predict."""
     _check_models(img_model, audio_model)
     truth: List[List[str]] = []
 

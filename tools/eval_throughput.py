@@ -9,7 +9,10 @@ batched decode (Transformer.greedy_batch on a list of memories, Transformer.eval
                             wall-clock of evaluate(batch_size=32) and of validation_step x 64 + on_validation_epoch_end on the
                             same 64 samples, the head bias of <eos> raised so that the sequences end at different lengths;
                             encode_s: the 64 batch-size-1 encoder passes both of them include
-Usage: python tools/eval_throughput.py [--n 64] [--batch 32] [--bs1-samples 8]"""
+  --refill                  also times evaluate(batch_size, refill=True) (continuous batching) three times, alternated with the
+                            grouped evaluate, and counts the positions each plan runs (grouped: every group until its longest
+                            row ends; stream: the positions of the slot state)
+Usage: python tools/eval_throughput.py [--n 64] [--batch 32] [--bs1-samples 8] [--refill]"""
 import argparse
 import json
 import os
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--bs1-samples", type=int, default=8, help="memories timed through the batch-size-1 loop")
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--refill", action="store_true", help="also measure evaluate(refill=True)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -118,8 +122,31 @@ def main():
     out["evaluate_speedup"] = round(t_loop / t_eval, 2)
     out["evaluate_equals_validation_loop"] = metrics_b == metrics_1
     out["metrics"] = metrics_b
+    ok = metrics_b == metrics_1
+    if args.refill:
+        from omr_a2s_multimodal_transformer_amd.evaluation import plan_groups
+        states = []
+        model._refill_state_hook = states.append
+        model.evaluate(batches[:args.batch // 2], batch_size=args.batch, refill=True)      # warm-up
+        del states[:]
+        grouped_s, refill_s = [], []
+        for _ in range(3):
+            metrics_r, t = timed(lambda: model.evaluate(batches, batch_size=args.batch, refill=True))
+            ok = ok and metrics_r == metrics_1
+            refill_s.append(round(t, 3))
+            grouped_s.append(round(timed(lambda: model.evaluate(batches, batch_size=args.batch))[1], 3))
+        with torch.no_grad():
+            mem_lens = [model.encode(x).shape[1] for x in xs]
+        singles, groups = plan_groups(mem_lens, args.batch)
+        out["evaluate_refill_s"] = refill_s
+        out["evaluate_grouped_s"] = grouped_s
+        out["refill_speedup_vs_grouped"] = round(min(grouped_s) / min(refill_s), 2)
+        out["refill_speedup_vs_validation_loop"] = round(t_loop / min(refill_s), 2)
+        out["positions_grouped"] = sum(max(lengths[i] for i in g) for g in groups)
+        out["positions_refill"] = sum(s.positions for s in states) // 3
+        out["evaluate_refill_equals_validation_loop"] = ok
     print(json.dumps(out), flush=True)
-    return 0 if metrics_b == metrics_1 else 1
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":

@@ -15,7 +15,8 @@ raised in both models so that the sequences end at different lengths.  Prints on
   equal                     every batched output equals the loop's (exit status 1 otherwise)
   batched_faster / sweep_below_5x
                             batched_s < min(loop_s); sweep_batched_s < 5 * batched_s
-Usage: python tools/late_fusion_throughput.py [--n 64] [--batch 32]"""
+  --refill: also weighted_predict(refill=True) (continuous batching), three runs alternated with the grouped call
+Usage: python tools/late_fusion_throughput.py [--n 64] [--batch 32] [--refill]"""
 import argparse
 import json
 import os
@@ -53,6 +54,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--alpha", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--refill", action="store_true", help="also time weighted_predict(refill=True), alternated with the grouped call")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -131,6 +133,18 @@ def main():
         out["probs_batched_tokens_per_s"] = round(ntok_probs / t_probs, 1)
         out["probs_speedup"] = round(t_probs_loop / t_probs, 2)
         equal["predict_with_probs"] = probs_got == ([w for w, _ in probs_want], [p for _, p in probs_want])
+        if args.refill:
+            weighted_predict(pairs[:args.batch // 2], img, aud, args.alpha, args.batch, refill=True)      # warm-up
+            grouped_s, refill_s = [], []
+            for _ in range(3):
+                got_r, t = timed(lambda: weighted_predict(pairs, img, aud, args.alpha, args.batch, refill=True))
+                equal["weighted_refill"] = equal.get("weighted_refill", True) and got_r == want
+                refill_s.append(round(t, 3))
+                grouped_s.append(round(timed(lambda: weighted_predict(pairs, img, aud, args.alpha, args.batch))[1], 3))
+            out["refill_s"] = refill_s
+            out["grouped_s"] = grouped_s
+            out["refill_speedup_vs_grouped"] = round(min(grouped_s) / min(refill_s), 2)
+            out["refill_speedup_vs_faster_loop"] = round(min(t_loop1, t_loop2) / min(refill_s), 2)
     out["equal"] = equal
     out["batched_faster"] = t_batched < min(t_loop1, t_loop2)
     out["sweep_below_5x"] = t_sweep < 5 * t_batched
