@@ -440,6 +440,35 @@ int omr_beam_select(const float* logits, long ld, int V, const omr_beam_desc* be
  * t0 + n_steps > max_len. */
 int omr_beam_decode_steps(const omr_decode_desc* desc, const omr_beam_desc* beam_desc, const int* mem_len, int t0, int n_steps, void* stream);
 
+/* ---- beam search over the weighted late fusion ------------------------------------------------------------------------ */
+/* The k best tokens of one decoding step of the weighted late fusion (src/multimodal/weighted_multimodal/test.py:50-61; an
+ * extension: the reference decodes greedily, k = 1).  Per row pair r of logits_a [rows][lda] / logits_b [rows][ldb] (fp32, n
+ * entries read): p[i] = alpha * softmax(a)[i] + (1 - alpha) * softmax(b)[i] in omr_weighted_argmax_rows' arithmetic (the
+ * same maxima, sums and weight roundings; two rounded products and one add); idx_out [rows][k] are the indices of the k
+ * largest p, ordered by p descending, then index ascending; val_out [rows][k] = logf(p) in fp32 (-inf where p underflowed to
+ * 0).  k = 1 gives omr_weighted_argmax_rows' index, ties included.  One workgroup per row; a row's result does not depend on
+ * `rows`.  Refused: rows < 1, k outside 1..OMR_MAX_BEAM, n < k, lda < n, ldb < n. */
+int omr_weighted_topk_logprob(const float* logits_a, long lda, const float* logits_b, long ldb, int rows, int n, float alpha, int k,
+                              long* idx_out, float* val_out, void* stream);
+/* omr_beam_select for the weighted late fusion (weighted_multimodal/test.py:50-61; an extension: the reference decodes
+ * greedily): the candidates of row r are omr_weighted_topk_logprob's `beam` (index, logf(p)) of rows r of logits_a / logits_b
+ * [N * beam][ld] -- ranked by p descending, then index ascending -- and everything after that (fp64 scores, order, finished
+ * record, stop rule, padding) is omr_beam_select's, by the same code.  A candidate of value -inf gets no special case. */
+int omr_weighted_beam_select(const float* logits_a, long lda, const float* logits_b, long ldb, int V, float alpha,
+                             const omr_beam_desc* beam_desc, int t, void* stream);
+/* omr_beam_decode_steps for the weighted late fusion (weighted_multimodal/test.py:21-70; an extension: the reference decodes
+ * greedily): ONE search state drives two models.  Per position: model A's step, model B's step (no pick; both read
+ * beam_desc->tokens, the hypotheses of an input share its cross-attention K|V slot in either model), one
+ * omr_weighted_beam_select launch over the two models' fp32 logits (candidates: the `beam` largest
+ * alpha * softmax(a) + (1 - alpha) * softmax(b) per row, p descending then index ascending, value logf(p)), then the cache
+ * reorder once per model with that model's own L, d, dtype and window.  beam_desc->self_kv2 is model A's second cache,
+ * self_kv2_b model B's; both models' caches alternate by the parity of the position.  beam_desc->last_logits (nullable) gets
+ * model A's logits of the last position.  mem_len_a / mem_len_b: device int32 [N] of that model.  Refused before the first
+ * launch: desc_a->V != desc_b->V, desc_x->B != N * beam, beam outside 1..OMR_MAX_BEAM, t0 + n_steps greater than either
+ * model's max_len or beam_desc->max_len, a cache that is not 16-byte aligned. */
+int omr_weighted_beam_decode_steps(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b, const int* mem_len_b,
+                                   const omr_beam_desc* beam_desc, void* self_kv2_b, float alpha, int t0, int n_steps, void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------------------------ */
 /* CrossEntropyLoss(ignore_index=pad) (model.py:109,166) on row-major logits [M][ldv]; acc2 = {sum, count} (fp64). */
 int omr_ce_fwd(int dtype, const void* logits, const long* target, float* lse, double* acc2, float* loss_out, long M, int V, long ldv,

@@ -585,26 +585,14 @@ namespace {
 
 constexpr int BEAM_GROUPS = 4;         // rows of an input ranked side by side: one 256-thread group each
 
-// One workgroup per input.  Phase 1: the top `beam` log-probabilities of each of its rows (topk_logprob_row, the row body of
-// omr_topk_logprob).  Phase 2, wave 0, one candidate per lane (beam * beam <= 64): rank by all-pairs comparison, then the host
-// loop's walk over the sorted candidates as ballots.
-__global__ __launch_bounds__(256 * BEAM_GROUPS) void beam_select_kernel(const float* __restrict__ logits, long ld, int V, omr_beam_desc bd, int t) {
-    __shared__ float sv[BEAM_GROUPS][256];
-    __shared__ int si[BEAM_GROUPS][256];
-    __shared__ float c_val[64];
-    __shared__ int c_tok[64];
+// Phase 2 of a selection kernel, one workgroup per input n (every thread calls it): the beam * beam (<= 64) candidates
+// (c_tok, c_val)[parent * beam + j] that phase 1 left in LDS get fp64 scores from the live rows, wave 0 ranks them by all-pairs
+// comparison, one candidate per lane, and walks them in order as ballots -- the host loop's walk (_Base.beam_search): finished
+// record, stop rule, survivors and dead padding (`put`).  One definition for both selection kernels.
+__device__ __forceinline__ void beam_rank_and_put(const omr_beam_desc& bd, int n, int t, const float* c_val, const int* c_tok) {
     __shared__ double u_sc[64], o_sc[64];          // candidates as found / in order
     __shared__ int u_live[64], o_tok[64], o_par[64], o_ok[64];
-    const int n = blockIdx.x, beam = bd.beam, row0 = n * beam;
-    if (bd.done[n]) return;                         // frozen (uniform over the workgroup)
-    const int g = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = threadIdx.x;
-    for (int k0 = 0; k0 < beam; k0 += BEAM_GROUPS) {
-        const int k = k0 + g;
-        const bool real = k < beam;                 // a group without a row walks an empty one: the barriers stay uniform
-        topk_logprob_row(logits + (long)(row0 + (real ? k : 0)) * ld, real ? V : 0, beam, tid, sv[g], si[g], [&](int j, int idx, float val) {
-            if (tid == 0 && real) { c_tok[k * beam + j] = idx; c_val[k * beam + j] = val; }
-        });
-    }
+    const int beam = bd.beam, row0 = n * beam, lane = threadIdx.x;
     __syncthreads();
     const int nc = beam * beam;
     double sc = 0.0; int par = 0, tok = 0; bool live = false;
@@ -662,6 +650,49 @@ __global__ __launch_bounds__(256 * BEAM_GROUPS) void beam_select_kernel(const fl
     if (lane >= nsurv && lane < beam) put(lane, o_par[first], o_tok[first], -INFINITY);      // dead padding rows: copies of the first survivor
 }
 
+// One workgroup per input.  Phase 1: the top `beam` log-probabilities of each of its rows (topk_logprob_row, the row body of
+// omr_topk_logprob), BEAM_GROUPS rows side by side.  Phase 2: beam_rank_and_put.
+__global__ __launch_bounds__(256 * BEAM_GROUPS) void beam_select_kernel(const float* __restrict__ logits, long ld, int V, omr_beam_desc bd, int t) {
+    __shared__ float sv[BEAM_GROUPS][256];
+    __shared__ int si[BEAM_GROUPS][256];
+    __shared__ float c_val[64];
+    __shared__ int c_tok[64];
+    const int n = blockIdx.x, beam = bd.beam, row0 = n * beam;
+    if (bd.done[n]) return;                         // frozen (uniform over the workgroup)
+    const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
+    for (int k0 = 0; k0 < beam; k0 += BEAM_GROUPS) {
+        const int k = k0 + g;
+        const bool real = k < beam;                 // a group without a row walks an empty one: the barriers stay uniform
+        topk_logprob_row(logits + (long)(row0 + (real ? k : 0)) * ld, real ? V : 0, beam, tid, sv[g], si[g], [&](int j, int idx, float val) {
+            if (tid == 0 && real) { c_tok[k * beam + j] = idx; c_val[k * beam + j] = val; }
+        });
+    }
+    beam_rank_and_put(bd, n, t, c_val, c_tok);
+}
+
+// beam_select_kernel over the weighted late fusion of two models (an extension: the reference decodes greedily,
+// weighted_multimodal/test.py:50-61): phase 1 ranks wa * softmax(la) + wb * softmax(lb) of each row pair
+// (weighted_topk_logprob_row, the row body of omr_weighted_topk_logprob); phase 2 is the same.
+__global__ __launch_bounds__(256 * BEAM_GROUPS) void weighted_beam_select_kernel(const float* __restrict__ la, long lda, const float* __restrict__ lb, long ldb,
+                                                                                 int V, float wa, float wb, omr_beam_desc bd, int t) {
+    __shared__ float sa[BEAM_GROUPS][256], sb[BEAM_GROUPS][256];
+    __shared__ int si[BEAM_GROUPS][256];
+    __shared__ float c_val[64];
+    __shared__ int c_tok[64];
+    const int n = blockIdx.x, beam = bd.beam, row0 = n * beam;
+    if (bd.done[n]) return;                         // frozen (uniform over the workgroup)
+    const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
+    for (int k0 = 0; k0 < beam; k0 += BEAM_GROUPS) {
+        const int k = k0 + g;
+        const bool real = k < beam;                 // a group without a row walks an empty one: the barriers stay uniform
+        const long r = row0 + (real ? k : 0);
+        weighted_topk_logprob_row(la + r * lda, lb + r * ldb, real ? V : 0, wa, wb, beam, tid, sa[g], sb[g], si[g], [&](int j, int idx, float val) {
+            if (tid == 0 && real) { c_tok[k * beam + j] = idx; c_val[k * beam + j] = val; }
+        });
+    }
+    beam_rank_and_put(bd, n, t, c_val, c_tok);
+}
+
 // Cache reorder: new row i of an input continues row parents[i] of it.  Positions [lo, t] of every layer and row move from the
 // cache that holds position t to the one position t + 1 will be written into, 16 bytes per lane and access; nothing beyond t is
 // touched.  grid = (chunks of 1024 vectors, rows, L).  Inputs that are done are left where they are: their rows keep running on
@@ -714,6 +745,17 @@ extern "C" int omr_beam_select(const float* logits, long ld, int V, const omr_be
     return OMR_OK;
 }
 
+// The reorder launch after position t of one model: position t + 1 reads keys [lo, t + 1] (decode_steps' band), so positions
+// [lo, t] move from `cur` to `nxt`.  pos_bytes: K|V of one (layer, row, position) of that model.
+static void launch_beam_reorder(const omr_decode_desc& d, const omr_beam_desc& b, const void* cur, void* nxt, size_t pos_bytes, int t, void* stream) {
+    if (t + 1 >= d.max_len) return;
+    const int lo = (d.window > 0 && t + 1 - d.window > 0) ? t + 1 - d.window : 0;
+    const long nvec = (long)(t + 1 - lo) * (long)(pos_bytes / 16);
+    const dim3 grid((unsigned)cdiv(nvec, 1024), (unsigned)d.B, (unsigned)d.L);
+    hipLaunchKernelGGL(beam_reorder_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)cur, (uint4*)nxt, b.parents, b.done, b.beam, d.B,
+                       (long)d.max_len * (long)(pos_bytes / 16), (long)lo * (long)(pos_bytes / 16), nvec);
+}
+
 extern "C" int omr_beam_decode_steps(const omr_decode_desc* dp, const omr_beam_desc* bp, const int* mem_len, int t0, int n_steps, void* stream) {
     if (!dp || !bp || n_steps < 1 || t0 < 0) return OMR_ERR_ARG;
     if (bp->beam < 1 || bp->beam > OMR_MAX_BEAM || bp->N < 1 || (long)dp->B != (long)bp->N * bp->beam) return OMR_ERR_ARG;
@@ -731,13 +773,50 @@ extern "C" int omr_beam_decode_steps(const omr_decode_desc* dp, const omr_beam_d
         float* l32 = nullptr;
         TRY(decode_steps(&d, mem_len, bp->tokens, t, 1, nullptr, nullptr, s == n_steps - 1 ? bp->last_logits : nullptr, stream, bp->beam, &l32));
         hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)bp->N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, l32, (long)d.ldv, d.V, *bp, t);
-        if (t + 1 < d.max_len) {                                               // position t + 1 reads keys [lo, t + 1] (decode_steps' band)
-            const int lo = (d.window > 0 && t + 1 - d.window > 0) ? t + 1 - d.window : 0;
-            const long nvec = (long)(t + 1 - lo) * (long)(pos_bytes / 16);
-            const dim3 grid((unsigned)cdiv(nvec, 1024), (unsigned)d.B, (unsigned)d.L);
-            hipLaunchKernelGGL(beam_reorder_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)cur, (uint4*)nxt, bp->parents, bp->done,
-                               bp->beam, d.B, (long)d.max_len * (long)(pos_bytes / 16), (long)lo * (long)(pos_bytes / 16), nvec);
-        }
+        launch_beam_reorder(d, *bp, cur, nxt, pos_bytes, t, stream);
+        OMR_CHECK_LAUNCH();
+    }
+    return OMR_OK;
+}
+
+extern "C" int omr_weighted_beam_select(const float* logits_a, long lda, const float* logits_b, long ldb, int V, float alpha, const omr_beam_desc* bp, int t,
+                                        void* stream) {
+    if (!logits_a || !logits_b || !bp || !beam_desc_ok(*bp)) return OMR_ERR_ARG;
+    if (V < bp->beam || lda < V || ldb < V || t < 0 || t >= bp->max_len || bp->eos < 0 || bp->eos >= V) return OMR_ERR_ARG;
+    hipLaunchKernelGGL(weighted_beam_select_kernel, dim3((unsigned)bp->N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, logits_a, lda, logits_b, ldb, V,
+                       alpha, (float)(1.0 - (double)alpha), *bp, t);          // the weights as omr_weighted_argmax_rows rounds them
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+/* omr_beam_decode_steps over the weighted late fusion: ONE search state drives two models.  Per position model A's step and
+ * model B's step without a pick (both read bp->tokens, kv_group = beam), one weighted selection launch over both models'
+ * logits, and the cache reorder once per model with that model's own L, d, dtype and window. */
+extern "C" int omr_weighted_beam_decode_steps(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
+                                              const omr_beam_desc* bp, void* self_kv2_b, float alpha, int t0, int n_steps, void* stream) {
+    if (!da || !db || !bp || n_steps < 1 || t0 < 0) return OMR_ERR_ARG;
+    if (bp->beam < 1 || bp->beam > OMR_MAX_BEAM || bp->N < 1 || da->V != db->V) return OMR_ERR_ARG;
+    if ((long)da->B != (long)bp->N * bp->beam || (long)db->B != (long)bp->N * bp->beam) return OMR_ERR_ARG;
+    if (t0 + n_steps > da->max_len || t0 + n_steps > db->max_len || t0 + n_steps > bp->max_len) return OMR_ERR_ARG;      // refuse before the first launch
+    if (!beam_desc_ok(*bp) || !bp->self_kv2 || !self_kv2_b || !da->self_kv || !db->self_kv || da->V < bp->beam || bp->eos < 0 || bp->eos >= da->V)
+        return OMR_ERR_ARG;
+    const size_t pos_a = (size_t)2 * da->d * (da->dtype == OMR_BF16 ? 2 : 4), pos_b = (size_t)2 * db->d * (db->dtype == OMR_BF16 ? 2 : 4);
+    if (pos_a % 16 || pos_b % 16 || (((uintptr_t)da->self_kv | (uintptr_t)bp->self_kv2 | (uintptr_t)db->self_kv | (uintptr_t)self_kv2_b) & 15)) return OMR_ERR_ARG;
+    omr_decode_desc a = *da, b = *db;                                          // own copies: the cache pointers alternate per position
+    for (int s = 0; s < n_steps; ++s) {
+        const int t = t0 + s;
+        void* cur_a = (t & 1) ? bp->self_kv2 : da->self_kv;
+        void* nxt_a = (t & 1) ? da->self_kv : bp->self_kv2;
+        void* cur_b = (t & 1) ? self_kv2_b : db->self_kv;
+        void* nxt_b = (t & 1) ? db->self_kv : self_kv2_b;
+        a.self_kv = cur_a; b.self_kv = cur_b;
+        float *l32_a = nullptr, *l32_b = nullptr;
+        TRY(decode_steps(&a, mem_len_a, bp->tokens, t, 1, nullptr, nullptr, s == n_steps - 1 ? bp->last_logits : nullptr, stream, bp->beam, &l32_a));
+        TRY(decode_steps(&b, mem_len_b, bp->tokens, t, 1, nullptr, nullptr, nullptr, stream, bp->beam, &l32_b));
+        hipLaunchKernelGGL(weighted_beam_select_kernel, dim3((unsigned)bp->N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, l32_a, (long)a.ldv, l32_b,
+                           (long)b.ldv, a.V, alpha, (float)(1.0 - (double)alpha), *bp, t);
+        launch_beam_reorder(a, *bp, cur_a, nxt_a, pos_a, t, stream);
+        launch_beam_reorder(b, *bp, cur_b, nxt_b, pos_b, t, stream);
         OMR_CHECK_LAUNCH();
     }
     return OMR_OK;

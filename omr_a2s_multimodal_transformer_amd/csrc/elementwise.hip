@@ -212,24 +212,10 @@ __global__ void weighted_argmax_kernel(const float* __restrict__ la0, long lda, 
     const int tid = threadIdx.x, row = blockIdx.x;
     const float* __restrict__ la = la0 + (long)row * lda;
     const float* __restrict__ lb = lb0 + (long)row * ldb;
-    float ma = -INFINITY, mb = -INFINITY;
-    for (int i = tid; i < n; i += 256) { ma = fmaxf(ma, la[i]); mb = fmaxf(mb, lb[i]); }
-    sa[tid] = ma; sb[tid] = mb;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) { sa[tid] = fmaxf(sa[tid], sa[tid + o]); sb[tid] = fmaxf(sb[tid], sb[tid + o]); } __syncthreads(); }
-    ma = sa[0]; mb = sb[0];
-    __syncthreads();
-    float ea = 0.f, eb = 0.f;
-    for (int i = tid; i < n; i += 256) { ea += expf(la[i] - ma); eb += expf(lb[i] - mb); }
-    sa[tid] = ea; sb[tid] = eb;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) { sa[tid] += sa[tid + o]; sb[tid] += sb[tid + o]; } __syncthreads(); }
-    const float za = sa[0], zb = sb[0];
-    __syncthreads();
+    const MixStats st = weighted_mix_stats(la, lb, n, tid, sa, sb);
     float best = -INFINITY; int bi = 0x7fffffff;
     for (int i = tid; i < n; i += 256) {
-        const float pa = expf(la[i] - ma) / za, pb = expf(lb[i] - mb) / zb;
-        const float v = __fadd_rn(__fmul_rn(wa, pa), __fmul_rn(wb, pb));
+        const float v = weighted_mix(la[i], lb[i], st, wa, wb);
         if (v > best || (v == best && i < bi)) { best = v; bi = i; }
     }
     sa[tid] = best; si[tid] = bi;
@@ -259,6 +245,21 @@ __global__ void topk_logprob_kernel(const float* __restrict__ x0, int n, long ld
     long* io = idx_out + (long)blockIdx.x * k;
     float* vo = val_out + (long)blockIdx.x * k;
     topk_logprob_row(x0 + (long)blockIdx.x * ld, n, k, tid, sv, si, [&](int j, int idx, float val) {
+        if (tid == 0) { io[j] = idx; vo[j] = val; }
+    });
+}
+
+// ---------------------------------------------------------------- top-k log-probabilities of the weighted mix (beam search)
+// out_val[row][j] = logf(alpha * softmax(la[row]) + (1 - alpha) * softmax(lb[row]))[out_idx[row][j]], j-th largest, ties towards
+// the smaller index (k = 1 is weighted_argmax_kernel's pick).  One workgroup per row pair (weighted_topk_logprob_row).
+__global__ void weighted_topk_logprob_kernel(const float* __restrict__ la0, long lda, const float* __restrict__ lb0, long ldb, int n, float wa, float wb,
+                                             int k, long* __restrict__ idx_out, float* __restrict__ val_out) {
+    __shared__ float sa[256], sb[256];
+    __shared__ int si[256];
+    const int tid = threadIdx.x;
+    long* io = idx_out + (long)blockIdx.x * k;
+    float* vo = val_out + (long)blockIdx.x * k;
+    weighted_topk_logprob_row(la0 + (long)blockIdx.x * lda, lb0 + (long)blockIdx.x * ldb, n, wa, wb, k, tid, sa, sb, si, [&](int j, int idx, float val) {
         if (tid == 0) { io[j] = idx; vo[j] = val; }
     });
 }
@@ -416,6 +417,15 @@ extern "C" int omr_weighted_argmax_rows(const float* logits_a, long lda, const f
     // the reference multiplies fp32 tensors by the Python floats alpha and (1 - alpha): each is rounded to fp32 once
     hipLaunchKernelGGL(weighted_argmax_kernel, rows, 256, 0, (hipStream_t)stream, logits_a, lda, logits_b, ldb, n, alpha, (float)(1.0 - (double)alpha),
                        idx_out, prob_out, tokens_out);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+extern "C" int omr_weighted_topk_logprob(const float* logits_a, long lda, const float* logits_b, long ldb, int rows, int n, float alpha, int k,
+                                         long* idx_out, float* val_out, void* stream) {
+    if (rows < 1 || k < 1 || k > OMR_MAX_BEAM || n < k || lda < n || ldb < n || !logits_a || !logits_b || !idx_out || !val_out) return OMR_ERR_ARG;
+    hipLaunchKernelGGL(weighted_topk_logprob_kernel, rows, 256, 0, (hipStream_t)stream, logits_a, lda, logits_b, ldb, n, alpha, (float)(1.0 - (double)alpha),
+                       k, idx_out, val_out);      // the weights as omr_weighted_argmax_rows rounds them
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }

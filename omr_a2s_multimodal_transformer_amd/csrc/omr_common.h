@@ -196,3 +196,64 @@ __device__ __forceinline__ void topk_logprob_row(const float* __restrict__ x, in
         __syncthreads();
     }
 }
+
+// Weighted late fusion of ONE pair of logit rows by a group of 256 threads (every thread of the WORKGROUP must call these: they
+// synchronise with __syncthreads).  weighted_mix_stats: the two rows' maxima and sums of exponentials over the 256-thread
+// strided partition and the halving trees of weighted_argmax_kernel (elementwise.hip), which calls it.  sa / sb: 256 entries
+// of LDS each, the group's own; free again on return.
+struct MixStats { float ma, mb, za, zb; };
+__device__ __forceinline__ MixStats weighted_mix_stats(const float* __restrict__ la, const float* __restrict__ lb, int n, int tid, float* sa, float* sb) {
+    float ma = -INFINITY, mb = -INFINITY;
+    for (int i = tid; i < n; i += 256) { ma = fmaxf(ma, la[i]); mb = fmaxf(mb, lb[i]); }
+    sa[tid] = ma; sb[tid] = mb;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if (tid < o) { sa[tid] = fmaxf(sa[tid], sa[tid + o]); sb[tid] = fmaxf(sb[tid], sb[tid + o]); } __syncthreads(); }
+    ma = sa[0]; mb = sb[0];
+    __syncthreads();
+    float ea = 0.f, eb = 0.f;
+    for (int i = tid; i < n; i += 256) { ea += expf(la[i] - ma); eb += expf(lb[i] - mb); }
+    sa[tid] = ea; sb[tid] = eb;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if (tid < o) { sa[tid] += sa[tid + o]; sb[tid] += sb[tid + o]; } __syncthreads(); }
+    const MixStats st = {ma, mb, sa[0], sb[0]};
+    __syncthreads();
+    return st;
+}
+// wa * softmax(la)[i] + wb * softmax(lb)[i]: two rounded products and one add like torch's `alpha * p + (1 - alpha) * q`
+// (no fma contraction), so ties break the way they do there
+__device__ __forceinline__ float weighted_mix(float la_i, float lb_i, const MixStats& st, float wa, float wb) {
+    return __fadd_rn(__fmul_rn(wa, expf(la_i - st.ma) / st.za), __fmul_rn(wb, expf(lb_i - st.mb) / st.zb));
+}
+
+// topk_logprob_row for the mixed distribution p = weighted_mix(la, lb) (beam search over the weighted late fusion; an
+// extension: the reference decodes greedily, weighted_multimodal/test.py:50-61): emit(j, index, logf(p[index])) for the j-th
+// largest p, j < k, ties towards the smaller index, the same values in every thread.  Every selection pass recomputes p by the
+// one expression above, so k = 1 is weighted_argmax_kernel's pick and a row's result does not depend on the grid.  p = 0
+// (both exponentials underflowed) is a candidate like any other and emits -inf.  One definition for weighted_topk_logprob_kernel
+// (elementwise.hip) and the weighted beam selection (decode.hip).
+template <typename Emit>
+__device__ __forceinline__ void weighted_topk_logprob_row(const float* __restrict__ la, const float* __restrict__ lb, int n, float wa, float wb, int k,
+                                                          int tid, float* sa, float* sb, int* si, Emit emit) {
+    const MixStats st = weighted_mix_stats(la, lb, n, tid, sa, sb);
+    float last_v = INFINITY; int last_i = -1;
+    for (int j = 0; j < k; ++j) {
+        float best = -INFINITY; int bi = 0x7fffffff;
+        for (int i = tid; i < n; i += 256) {
+            const float v = weighted_mix(la[i], lb[i], st, wa, wb);
+            const bool cand = v < last_v || (v == last_v && i > last_i);
+            if (cand && (v > best || (v == best && i < bi))) { best = v; bi = i; }
+        }
+        sa[tid] = best; si[tid] = bi;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (tid < o) {
+                const float v2 = sa[tid + o]; const int i2 = si[tid + o];
+                if (v2 > sa[tid] || (v2 == sa[tid] && i2 < si[tid])) { sa[tid] = v2; si[tid] = i2; }
+            }
+            __syncthreads();
+        }
+        last_v = sa[0]; last_i = si[0];
+        emit(j, last_i, logf(last_v));
+        __syncthreads();
+    }
+}

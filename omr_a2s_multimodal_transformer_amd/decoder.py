@@ -647,51 +647,40 @@ class _BeamDesc(ctypes.Structure):
         (n, ctypes.c_void_p) for n in STATE_FIELDS + ("self_kv2", "last_logits")]
 
 
-class BeamDecodeState(DecodeState):
-    """Device state of a beam search over N inputs at once (csrc/decode.hip, omr_beam_decode_steps): a ragged decode state of
-    N memories whose B = N * beam rows are the hypotheses (row n * beam + k: hypothesis k of input n; the rows of an input read
-    its one cross-attention K|V slot), two self-attention caches that alternate per position, and the search state
-    (include/omr_hip.h) in one device block.  run(n) issues n positions from one host call; results() reads the block back
-    once and walks the history tables on the host (evaluation.beam_results)."""
+class BeamSearchBlock:
+    """The search state of a batched beam search (include/omr_hip.h, omr_beam_desc) over N inputs of `beam` rows each: one
+    device block, its descriptor, the host image it started from, and the reads of it.  max_len: the positions the history
+    tables hold.  One block serves a BeamDecodeState, or the two models of a WeightedBeamState."""
 
-    def __init__(self, dec: "Decoder", mems, dt: torch.dtype, beam: int, sos: int, eos: int):
-        super().__init__(dec, mems, dt, rows_per_memory=beam)
+    def __init__(self, N: int, beam: int, sos: int, eos: int, max_len: int, device):
         import numpy as np
-        self.beam, self.sos, self.eos, self.N = beam, sos, eos, len(mems)
-        self.self_kv2 = torch.empty_like(self.self_kv)
+        self.N, self.beam, self.rows, self.max_len = N, beam, N * beam, max_len
         bd = self.bdesc = _BeamDesc()
-        bd.beam, bd.N, bd.eos, bd.max_len = beam, self.N, eos, self.max_len
+        bd.beam, bd.N, bd.eos, bd.max_len = beam, N, eos, max_len
         bd.state = None
         nbytes = lib().query("omr_beam_workspace_bytes", ctypes.byref(bd))
         if nbytes <= 0:
             raise RuntimeError("libomr_hip: omr_beam_workspace_bytes rejected the beam descriptor")
         self._off = {n: int(getattr(bd, n) or 0) for n in _BeamDesc.STATE_FIELDS}      # state == NULL: the fields are offsets
         host = np.zeros(nbytes, dtype=np.uint8)
-        rows = self.B
-        self._view(host, "scores", np.float64, rows)[:] = ([0.0] + [float("-inf")] * (beam - 1)) * self.N
-        self._view(host, "best_score", np.float64, self.N)[:] = float("-inf")
-        self._view(host, "tokens", np.int64, rows)[:] = sos
-        self._view(host, "exhausted", np.int32, self.N)[:] = 1
-        self.state = torch.from_numpy(host).to(self.self_kv.device)
+        self._view(host, "scores", np.float64, self.rows)[:] = ([0.0] + [float("-inf")] * (beam - 1)) * N
+        self._view(host, "best_score", np.float64, N)[:] = float("-inf")
+        self._view(host, "tokens", np.int64, self.rows)[:] = sos
+        self._view(host, "exhausted", np.int32, N)[:] = 1
+        self._initial = torch.from_numpy(host)
+        self.state = self._initial.to(device)
         bd.state, bd.state_bytes = self.state.data_ptr(), nbytes
         if lib().query("omr_beam_workspace_bytes", ctypes.byref(bd)) != nbytes:
             raise RuntimeError("libomr_hip: omr_beam_workspace_bytes changed its answer")
-        bd.self_kv2, bd.last_logits = self.self_kv2.data_ptr(), self.logits.data_ptr()
+
+    def rewind(self) -> None:
+        """Upload the block as it was before position 0 (another search over the same inputs)."""
+        self.state.copy_(self._initial)
 
     def _view(self, host, name: str, dtype, count: int):
         import numpy as np
         off = self._off[name]
         return host[off:off + count * np.dtype(dtype).itemsize].view(dtype)
-
-    def share_memory_between(self, rows: int) -> None:
-        raise RuntimeError("share_memory_between: a beam decode state already shares each memory between its hypotheses")
-
-    def run(self, n_steps: int) -> None:                   # noqa: D401 -- positions t .. t + n_steps - 1, nothing returned
-        """Run n_steps positions of every input (decode step, selection, cache reorder) without a host round trip."""
-        if n_steps < 1 or self.t + n_steps > self.max_len:
-            raise RuntimeError("beam decode beyond max_seq_len (positional-encoding table exhausted)")
-        lib().call("omr_beam_decode_steps", ctypes.byref(self.desc), ctypes.byref(self.bdesc), ptr(self.mem_len), self.t, n_steps, cur_stream())
-        self.t += n_steps
 
     def _device_ints(self, name: str, count: int) -> torch.Tensor:
         off = self._off[name]
@@ -703,13 +692,13 @@ class BeamDecodeState(DecodeState):
 
     def parents(self) -> torch.Tensor:
         """int32 [N, beam], on the device: the LOCAL row each row of the next position continues (of the last position run)."""
-        return self._device_ints("parents", self.B).view(self.N, self.beam)
+        return self._device_ints("parents", self.rows).view(self.N, self.beam)
 
     def snapshot(self) -> dict:
         """One device-to-host copy of the whole search state -> {field: numpy array} (history tables [max_len, rows])."""
         import numpy as np
         host = self.state.cpu().numpy()
-        rows, N = self.B, self.N
+        rows, N = self.rows, self.N
         out = {"scores": self._view(host, "scores", np.float64, rows), "best_score": self._view(host, "best_score", np.float64, N),
                "tokens": self._view(host, "tokens", np.int64, rows), "parents": self._view(host, "parents", np.int32, rows)}
         for n in ("best_row", "best_pos", "done", "exhausted"):
@@ -718,9 +707,97 @@ class BeamDecodeState(DecodeState):
             out[n] = self._view(host, n, np.int32, self.max_len * rows).reshape(self.max_len, rows)
         return out
 
-    def results(self):
-        """-> [(token ids, score)] per input, what _Base.beam_search finds for that input alone (evaluation.beam_results)."""
+    def results(self, positions: int):
+        """-> [(token ids, score)] per input after `positions` positions: what the host loop finds for that input alone
+        (evaluation.beam_results)."""
         from .evaluation import beam_results
         s = self.snapshot()
-        return beam_results(self.beam, self.t, int(self.bdesc.eos), s["scores"], s["best_score"], s["best_row"], s["best_pos"], s["done"],
+        return beam_results(self.beam, positions, int(self.bdesc.eos), s["scores"], s["best_score"], s["best_row"], s["best_pos"], s["done"],
                             s["hist_parent"], s["hist_token"])
+
+
+class BeamDecodeState(DecodeState):
+    """Device state of a beam search over N inputs at once (csrc/decode.hip, omr_beam_decode_steps): a ragged decode state of
+    N memories whose B = N * beam rows are the hypotheses (row n * beam + k: hypothesis k of input n; the rows of an input read
+    its one cross-attention K|V slot), two self-attention caches that alternate per position, and the search state
+    (BeamSearchBlock) in one device block.  run(n) issues n positions from one host call; results() reads the block back
+    once and walks the history tables on the host (evaluation.beam_results)."""
+
+    def __init__(self, dec: "Decoder", mems, dt: torch.dtype, beam: int, sos: int, eos: int):
+        super().__init__(dec, mems, dt, rows_per_memory=beam)
+        self.beam, self.sos, self.eos, self.N = beam, sos, eos, len(mems)
+        self.self_kv2 = torch.empty_like(self.self_kv)
+        self.search = BeamSearchBlock(self.N, beam, sos, eos, self.max_len, self.self_kv.device)
+        self.bdesc, self.state = self.search.bdesc, self.search.state
+        self.bdesc.self_kv2, self.bdesc.last_logits = self.self_kv2.data_ptr(), self.logits.data_ptr()
+
+    def share_memory_between(self, rows: int) -> None:
+        raise RuntimeError("share_memory_between: a beam decode state already shares each memory between its hypotheses")
+
+    def run(self, n_steps: int) -> None:                   # noqa: D401 -- positions t .. t + n_steps - 1, nothing returned
+        """Run n_steps positions of every input (decode step, selection, cache reorder) without a host round trip."""
+        if n_steps < 1 or self.t + n_steps > self.max_len:
+            raise RuntimeError("beam decode beyond max_seq_len (positional-encoding table exhausted)")
+        lib().call("omr_beam_decode_steps", ctypes.byref(self.desc), ctypes.byref(self.bdesc), ptr(self.mem_len), self.t, n_steps, cur_stream())
+        self.t += n_steps
+
+    def done(self) -> List[bool]:
+        return self.search.done()
+
+    def parents(self) -> torch.Tensor:
+        return self.search.parents()
+
+    def snapshot(self) -> dict:
+        return self.search.snapshot()
+
+    def results(self):
+        """-> [(token ids, score)] per input, what _Base.beam_search finds for that input alone (evaluation.beam_results)."""
+        return self.search.results(self.t)
+
+
+class WeightedBeamState:
+    """Device state of a beam search over the weighted late fusion of N pairs at once (csrc/decode.hip,
+    omr_weighted_beam_decode_steps; an extension: the reference decodes greedily): per model a ragged decode state of
+    rows_per_memory = beam over its memories with a second self-attention cache, and ONE search block (BeamSearchBlock) that
+    both models read their tokens and parents from.  The history holds min(max_len) positions: no search outlives the shorter
+    positional table.  run(n) issues n positions from one host call; rewind() starts another search over the same pairs (an
+    alpha sweep, `alpha` being the mixing weight run() passes on): the cross-attention K|V stay as projected."""
+
+    def __init__(self, dec_a: "Decoder", mems_a, dec_b: "Decoder", mems_b, beam: int, sos: int, eos: int, alpha: float = 0.5):
+        if not 1 <= beam <= MAX_BEAM:
+            raise ValueError(f"beam must be in 1..{MAX_BEAM}, got {beam}")
+        if len(mems_a) != len(mems_b):
+            raise ValueError(f"weighted beam state: {len(mems_a)} memories for one model, {len(mems_b)} for the other")
+        V = dec_a.output_size
+        if dec_b.output_size != V or beam > V or not (0 <= sos < V and 0 <= eos < V):
+            raise ValueError(f"weighted beam state: vocabularies {V} / {dec_b.output_size}, beam {beam}, sos {sos}, eos {eos} do not fit")
+        self.st_a = DecodeState(dec_a, dec_a.memory_list(mems_a), dec_a._compute_dtype(), rows_per_memory=beam)
+        self.st_b = DecodeState(dec_b, dec_b.memory_list(mems_b), dec_b._compute_dtype(), rows_per_memory=beam)
+        self.kv2_a, self.kv2_b = torch.empty_like(self.st_a.self_kv), torch.empty_like(self.st_b.self_kv)
+        self.beam, self.N, self.t, self.alpha = beam, len(mems_a), 0, float(alpha)
+        self.max_len = min(self.st_a.max_len, self.st_b.max_len)
+        self.search = BeamSearchBlock(self.N, beam, sos, eos, self.max_len, self.st_a.self_kv.device)
+        self.bdesc = self.search.bdesc
+        self.bdesc.self_kv2, self.bdesc.last_logits = self.kv2_a.data_ptr(), None
+
+    def run(self, n_steps: int) -> None:
+        """n_steps positions of every pair (both models' steps, the weighted selection, both cache reorders), no host round trip."""
+        if n_steps < 1 or self.t + n_steps > self.max_len:
+            raise RuntimeError("weighted beam decode beyond a model's max_seq_len (positional-encoding table exhausted)")
+        lib().call("omr_weighted_beam_decode_steps", ctypes.byref(self.st_a.desc), ptr(self.st_a.mem_len), ctypes.byref(self.st_b.desc),
+                   ptr(self.st_b.mem_len), ctypes.byref(self.bdesc), ptr(self.kv2_b), self.alpha, self.t, n_steps, cur_stream())
+        self.t += n_steps
+
+    def done(self) -> List[bool]:
+        return self.search.done()
+
+    def results(self):
+        """-> [(token ids, score)] per pair, what weighted_fusion.weighted_beam_search finds for that pair alone."""
+        return self.search.results(self.t)
+
+    def rewind(self, alpha: Optional[float] = None) -> None:
+        """Back to position 0 over the same pairs, with another alpha if given: the initial search block is uploaded again."""
+        self.search.rewind()
+        self.t = 0
+        if alpha is not None:
+            self.alpha = float(alpha)

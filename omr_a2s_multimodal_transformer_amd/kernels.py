@@ -321,6 +321,22 @@ def weighted_argmax_rows(la: Tensor, lb: Tensor, alpha: float, n: Optional[int] 
     return idx, prob
 
 
+def weighted_topk_logprob(la: Tensor, lb: Tensor, alpha: float, k: int, n: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """The k best tokens of alpha * softmax(la) + (1 - alpha) * softmax(lb) row by row (weighted_argmax_rows' arithmetic; beam
+    search over the weighted fusion, an extension: the reference decodes greedily): fp32 [rows, >= n] logits (row strides free,
+    unit column stride; n defaults to the narrower width) -> (token ids int64 [rows, k], log of the mixed probability fp32
+    [rows, k]), best first, ties towards the smaller id."""
+    require_cuda(la, lb)
+    assert la.dtype == lb.dtype == torch.float32 and la.dim() == lb.dim() == 2 and la.shape[0] == lb.shape[0]
+    rows = la.shape[0]
+    n = min(la.shape[1], lb.shape[1]) if n is None else n
+    assert n <= min(la.shape[1], lb.shape[1]) and (la.stride(1) == 1 and lb.stride(1) == 1 or n == 1)
+    idx = torch.empty((rows, k), dtype=torch.int64, device=la.device)
+    val = torch.empty((rows, k), dtype=torch.float32, device=la.device)
+    lib().call("omr_weighted_topk_logprob", ptr(la), la.stride(0), ptr(lb), lb.stride(0), rows, n, float(alpha), k, ptr(idx), ptr(val), cur_stream())
+    return idx, val
+
+
 def topk_logprob(x: Tensor, k: int) -> Tuple[Tensor, Tensor]:
     """x fp32 [rows, n] -> (token ids int64 [rows, k], log-probabilities fp32 [rows, k]), best first."""
     require_cuda(x)

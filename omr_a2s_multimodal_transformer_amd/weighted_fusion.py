@@ -13,21 +13,52 @@ The reference evaluates a test set one pair at a time (test.py:154-172).  `weigh
 groups of pairs of different sizes as two ragged decode states in lock-step (omr_weighted_decode_steps_varlen: per position
 both models' steps for all rows, then one mixing launch for all rows); every sequence equals `weighted_prediction` of that
 pair.  A sequence of alphas re-runs only the decode: encoders and cross-attention projections run once per pair.
+
+Beam search over the mixed distribution (`weighted_beam_search`, `weighted_beam_search_batch`, `weighted_predict(beam=)`,
+`weighted_evaluate(beam=)`) is an extension: the reference decodes the fusion greedily.  It is `_Base.beam_search` of model.py
+with the log of the mixed probability in place of log_softmax; beam = 1 is the weighted greedy decode.
 """
 from __future__ import annotations
 
+import contextvars
 import ctypes
+import functools
 import itertools
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
+from . import kernels as K
 from ._lib import cur_stream, lib, ptr
+from .decoder import MAX_BEAM, WeightedBeamState, takes_ragged_state
 from .evaluation import WINDOW_BATCHES, decode_rows, decode_stream, plan_pair_groups, refill_enabled, refill_option, stream_order
 from .metrics import compute_metrics
 from .synthetic import EOS_TOKEN, SOS_TOKEN
 
 _EXHAUSTED = "weighted_prediction beyond a model's max_seq_len (positional-encoding table exhausted)"
+
+_BEAM = contextvars.ContextVar("omr_weighted_beam", default=1)
+
+
+def beam_option(fn):
+    """Gives weighted_predict / weighted_evaluate the keyword `beam` (1 .. 8, default 1), like model._beam_option: the
+    function's own parameter list stays as it is; the value is checked here, before anything is encoded; beam = 1 calls the
+    function as before, a wider beam holds for the duration of the call (`_weighted_predict` asks for it).  Goes outside
+    `refill_option`, so that it sees that keyword: a beam state has no slots to refill."""
+    @functools.wraps(fn)
+    def call(*args, beam: int = 1, **kwargs):
+        if not isinstance(beam, int) or not 1 <= beam <= MAX_BEAM:
+            raise ValueError(f"beam must be an integer in 1..{MAX_BEAM}, got {beam}")
+        if beam == 1:
+            return fn(*args, **kwargs)
+        if kwargs.get("refill"):
+            raise ValueError("refill=True decodes greedily: the beam state (two caches per model, a history table) has no slots to refill")
+        token = _BEAM.set(beam)
+        try:
+            return fn(*args, **kwargs)
+        finally:
+            _BEAM.reset(token)
+    return call
 
 
 def _decode_lockstep(st_i, st_a, img_model, audio_model, alpha: float, sync_every: int) -> List[List[str]]:
@@ -102,6 +133,108 @@ def weighted_prediction(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_mod
     return _decode_lockstep(st_i, st_a, img_model, audio_model, alpha, chunk)[0]
 
 
+@torch.no_grad()
+def weighted_beam_search(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_model, alpha: float = 0.5, beam: int = 4) -> Tuple[List[str], float]:
+    """Beam search of ONE pair over the weighted late fusion (an extension: the reference decodes it greedily,
+    weighted_multimodal/test.py:21-70) -> (words incl. <eos> if reached, score).  `_Base.beam_search` written out for two
+    models: both decode the same `beam` hypotheses, the candidates of a row are the `beam` largest
+    alpha * softmax(image logits) + (1 - alpha) * softmax(audio logits) (kernels.weighted_topk_logprob) and a score is the sum
+    of the logs of those mixed probabilities, without length normalisation.  beam = 1 is `weighted_prediction`.  The budget
+    is max(img_model.max_seq_len, audio_model.max_seq_len); a live search that outgrows the shorter positional table raises."""
+    assert xi.size(0) == 1 and xa.size(0) == 1, "Inference only supports batch_size = 1"
+    return _beam_search_memories(img_model.encode(xi), audio_model.encode(xa), img_model, audio_model, alpha, beam)
+
+
+@torch.no_grad()
+def _beam_search_memories(mem_i: torch.Tensor, mem_a: torch.Tensor, img_model, audio_model, alpha: float, beam: int) -> Tuple[List[str], float]:
+    """weighted_beam_search from the two encoded memories [1, S, d]."""
+    assert beam >= 1
+    sos, eos = img_model.w2i[SOS_TOKEN], img_model.w2i[EOS_TOKEN]
+    st_i, st_a = img_model.decoder.init_decode(mem_i), audio_model.decoder.init_decode(mem_a)
+    st_i.share_memory_between(beam)                          # every hypothesis reads the same memory K|V; own self-attention cache rows
+    st_a.share_memory_between(beam)
+    assert st_i.V == st_a.V, "both models share the vocabulary (test.py:62)"
+    dev = st_i.tok.device
+    tok = torch.full((beam, 1), sos, dtype=torch.int64, device=dev)
+    scores = [0.0] + [float("-inf")] * (beam - 1)           # only the first row is a real hypothesis before the first step
+    seqs: List[List[int]] = [[] for _ in range(beam)]
+    best_done: Tuple[float, Optional[List[int]]] = (float("-inf"), None)
+    exhausted = True                                         # the loop ran out of positions with hypotheses still alive
+    for t in range(max(img_model.max_seq_len, audio_model.max_seq_len)):
+        if t >= min(st_i.max_len, st_a.max_len):            # a live hypothesis outgrew the shorter positional table
+            raise RuntimeError(_EXHAUSTED)
+        li, la = (m.decoder.decode_step(tok, st).view(beam, -1) for m, st in ((img_model, st_i), (audio_model, st_a)))
+        idx, val = K.weighted_topk_logprob(li, la, alpha, beam)
+        idx_h, val_h = idx.cpu().tolist(), val.cpu().tolist()
+        cands = [(scores[b] + val_h[b][j], b, idx_h[b][j]) for b in range(beam) if scores[b] > float("-inf") for j in range(beam)]
+        cands.sort(key=lambda c: (-c[0], c[1], c[2]))
+        parents, new_tok, new_scores, new_seqs = [], [], [], []
+        for sc, b, tk in cands:
+            if tk == eos:
+                if sc > best_done[0]:
+                    best_done = (sc, seqs[b] + [tk])
+                continue
+            parents.append(b); new_tok.append(tk); new_scores.append(sc); new_seqs.append(seqs[b] + [tk])
+            if len(parents) == beam:
+                break
+        if not parents or new_scores[0] <= best_done[0]:    # scores only fall: no live hypothesis can overtake the best finished one
+            exhausted = False
+            break
+        while len(parents) < beam:                            # pad with dead rows
+            parents.append(parents[0]); new_tok.append(new_tok[0]); new_scores.append(float("-inf")); new_seqs.append([])
+        pidx = torch.tensor(parents, dtype=torch.int64, device=dev)
+        st_i.reorder_rows(pidx)
+        st_a.reorder_rows(pidx)
+        tok = torch.tensor(new_tok, dtype=torch.int64, device=dev).view(beam, 1)
+        scores, seqs = new_scores, new_seqs
+    if exhausted and scores[0] > best_done[0]:
+        best_done = (scores[0], seqs[0])                      # ran out of length: the best unfinished hypothesis wins
+    return [img_model._i2w(t) for t in best_done[1]], best_done[0]
+
+
+def _run_beam_state(state: WeightedBeamState, img_model, audio_model, sync_every: int) -> List[Tuple[List[str], float]]:
+    """One search of a WeightedBeamState at position 0 to its end: the `done` flags are read every sync_every positions, the
+    state once at the end."""
+    left = max(img_model.max_seq_len, audio_model.max_seq_len)
+    while left > 0:
+        n = min(sync_every, left, state.max_len - state.t)
+        if n <= 0:                                         # a live pair outgrew the shorter positional table
+            raise RuntimeError(_EXHAUSTED)
+        state.run(n)
+        left -= n
+        if left > 0 and all(state.done()):                 # one small device sync per chunk
+            break
+    return [([img_model._i2w(t) for t in seq], score) for seq, score in state.results()]
+
+
+@torch.no_grad()
+def weighted_beam_search_batch(mems_i, mems_a, img_model, audio_model, alpha: float = 0.5, beam: int = 4,
+                               sync_every: int = 8) -> List[Tuple[List[str], float]]:
+    """`weighted_beam_search` of N pairs at once, on the device (decoder.WeightedBeamState; csrc/decode.hip
+    omr_weighted_beam_decode_steps): -> [(words, score)] in input order, each exactly what weighted_beam_search returns for
+    that pair alone.  mems_i / mems_a: each model's encoded memories, [1, S_b, d] / [S_b, d] of different lengths.  Pairs of
+    which either memory has at most 64 or more than 16 384 tokens go through weighted_beam_search."""
+    if not 1 <= beam <= MAX_BEAM:
+        raise ValueError(f"beam must be in 1..{MAX_BEAM}, got {beam}")
+    if sync_every < 1:
+        raise ValueError(f"sync_every must be >= 1, got {sync_every}")
+    if len(mems_i) != len(mems_a):
+        raise ValueError(f"weighted_beam_search_batch: {len(mems_i)} image memories, {len(mems_a)} audio memories")
+    mi = img_model.decoder.memory_list(mems_i, refuse_long=False)
+    ma = audio_model.decoder.memory_list(mems_a, refuse_long=False)
+    out: List[Optional[Tuple[List[str], float]]] = [None] * len(mi)
+    batched = [i for i in range(len(mi)) if takes_ragged_state(mi[i].shape[0]) and takes_ragged_state(ma[i].shape[0])]
+    for i in range(len(mi)):
+        if i not in batched:                               # alone, such a memory takes another attention kernel: search the pair alone
+            out[i] = _beam_search_memories(mi[i].unsqueeze(0), ma[i].unsqueeze(0), img_model, audio_model, alpha, beam)
+    if batched:
+        state = WeightedBeamState(img_model.decoder, [mi[i] for i in batched], audio_model.decoder, [ma[i] for i in batched], beam,
+                                  img_model.w2i[SOS_TOKEN], img_model.w2i[EOS_TOKEN], alpha)
+        for i, result in zip(batched, _run_beam_state(state, img_model, audio_model, sync_every)):
+            out[i] = result
+    return out
+
+
 def _check_models(img_model, audio_model) -> None:
     if img_model.w2i != audio_model.w2i:
         raise ValueError("Vocabularies do not match (weighted_multimodal/test.py:140)")
@@ -111,6 +244,23 @@ def _alphas(alpha) -> Tuple[List[float], bool]:
     if isinstance(alpha, (int, float)):
         return [float(alpha)], False
     return [float(a) for a in alpha], True
+
+
+def _beam_window(mems_i, mems_a, img_model, audio_model, alphas: List[float], batch_size: int, sync_every: int, beam: int, out) -> None:
+    """out[k][i] <- the words weighted_beam_search finds for pair i of a window under alphas[k]: groups of batch_size // beam
+    pairs as one WeightedBeamState each, built once and rewound per alpha; the pairs plan_pair_groups leaves alone one by one."""
+    singles, groups = plan_pair_groups([m.shape[1] for m in mems_i], [m.shape[1] for m in mems_a], max(1, batch_size // beam))
+    for i in singles:
+        for k, alpha in enumerate(alphas):
+            out[k][i] = _beam_search_memories(mems_i[i], mems_a[i], img_model, audio_model, alpha, beam)[0]
+    for g in groups:
+        state = WeightedBeamState(img_model.decoder, [mems_i[i] for i in g], audio_model.decoder, [mems_a[i] for i in g], beam,
+                                  img_model.w2i[SOS_TOKEN], img_model.w2i[EOS_TOKEN])
+        for k, alpha in enumerate(alphas):
+            state.rewind(alpha)
+            for i, (seq, _) in zip(g, _run_beam_state(state, img_model, audio_model, sync_every)):
+                out[k][i] = seq
+        del state
 
 
 @torch.no_grad()
@@ -137,7 +287,12 @@ def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[floa
         mems_i = [img_model.encode(xi) for xi, _ in window]
         mems_a = [audio_model.encode(xa) for _, xa in window]
         out: List[List[Optional[List[str]]]] = [[None] * len(window) for _ in alphas]
-        singles, groups = plan_pair_groups([m.shape[1] for m in mems_i], [m.shape[1] for m in mems_a], batch_size)
+        beam = _BEAM.get()
+        if beam > 1:                                   # beam_option: the whole window is decoded here, nothing is left for the plans below
+            _beam_window(mems_i, mems_a, img_model, audio_model, alphas, batch_size, sync_every, beam, out)
+            singles, groups = [], []
+        else:
+            singles, groups = plan_pair_groups([m.shape[1] for m in mems_i], [m.shape[1] for m in mems_a], batch_size)
         # a single: the pair alone over two batch-size-1 states, `chunk` positions per read-back like weighted_prediction
         plans = [([i], mems_i[i], mems_a[i], chunk) for i in singles]
         rest = [i for g in groups for i in g]
@@ -164,6 +319,7 @@ def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[floa
         del mems_i, mems_a
 
 
+@beam_option
 @refill_option
 def weighted_predict(pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], img_model, audio_model, alpha: Union[float, Sequence[float]] = 0.5,
                      batch_size: int = 32, sync_every: int = 8):
@@ -173,17 +329,20 @@ def weighted_predict(pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], img_mod
     lock-step over ragged batches of up to batch_size rows.  `alpha` may be a sequence (the usual tuning sweep): the result
     is then {alpha: predictions}, with the encoders and the cross-attention projections run once, not once per alpha.
     Keyword `refill` (default False, `refill_option`): continuous batching -- a finished pair's slot goes to the next pair of the window (_decode_lockstep_stream);
-    same predictions."""
+    same predictions.  Keyword `beam` (2 .. 8, `beam_option`; an extension: the reference decodes greedily; not with refill): each
+    prediction is that of weighted_beam_search, batch_size // beam pairs at a time (decoder.WeightedBeamState); a sequence of
+    alphas rewinds each group's state per alpha."""
     alphas, many = _alphas(alpha)
     preds = _weighted_predict(pairs, img_model, audio_model, alphas, batch_size, sync_every)
     return dict(zip(alphas, preds)) if many else preds[0]
 
 
+@beam_option
 @refill_option
 def weighted_evaluate(batches: Iterable, img_model, audio_model, alpha: Union[float, Sequence[float]] = 0.5, batch_size: int = 32):
     """weighted_multimodal/test.py:154-172 over `batches` ((xi, xa, y) as the test loader yields them): compute_metrics of the
     weighted predictions against the ytest_i2w-decoded targets (without <sos>); {alpha: metrics} for a sequence of alphas.
-    Keyword `refill`: as in weighted_predict."""
+    Keywords `refill` and `beam`: as in weighted_predict."""
     _check_models(img_model, audio_model)
     truth: List[List[str]] = []
 

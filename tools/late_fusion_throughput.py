@@ -16,7 +16,10 @@ raised in both models so that the sequences end at different lengths.  Prints on
   batched_faster / sweep_below_5x
                             batched_s < min(loop_s); sweep_batched_s < 5 * batched_s
   --refill: also weighted_predict(refill=True) (continuous batching), three runs alternated with the grouped call
-Usage: python tools/late_fusion_throughput.py [--n 64] [--batch 32] [--refill]"""
+  --beam K: also beam search over the fusion (an extension: the reference decodes greedily): the weighted_beam_search loop over
+            the pairs against weighted_predict(beam=K), three runs each, alternated, after a warm-up
+            (beam_loop_s / beam_batched_s; beside batched_s, the greedy weighted_predict of the same pairs)
+Usage: python tools/late_fusion_throughput.py [--n 64] [--batch 32] [--refill] [--beam 4]"""
 import argparse
 import json
 import os
@@ -31,7 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from omr_a2s_multimodal_transformer_amd import synthetic as syn  # noqa: E402
 from omr_a2s_multimodal_transformer_amd.config import ModelConfig  # noqa: E402
 from omr_a2s_multimodal_transformer_amd.model import Transformer  # noqa: E402
-from omr_a2s_multimodal_transformer_amd.weighted_fusion import weighted_predict, weighted_prediction  # noqa: E402
+from omr_a2s_multimodal_transformer_amd.weighted_fusion import weighted_beam_search, weighted_predict, weighted_prediction  # noqa: E402
 
 SWEEP = [0.1, 0.3, 0.5, 0.7, 0.9]
 
@@ -55,6 +58,7 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--refill", action="store_true", help="also time weighted_predict(refill=True), alternated with the grouped call")
+    ap.add_argument("--beam", type=int, default=1, help="also time weighted_beam_search per pair against weighted_predict(beam=K)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -145,6 +149,27 @@ def main():
             out["grouped_s"] = grouped_s
             out["refill_speedup_vs_grouped"] = round(min(grouped_s) / min(refill_s), 2)
             out["refill_speedup_vs_faster_loop"] = round(min(t_loop1, t_loop2) / min(refill_s), 2)
+        if args.beam > 1:
+            beam_loop = lambda: [weighted_beam_search(xi, xa, img, aud, args.alpha, args.beam)[0] for xi, xa in pairs]
+            weighted_beam_search(pairs[0][0], pairs[0][1], img, aud, args.alpha, args.beam)      # warm-up of both routes
+            weighted_predict(pairs[:max(1, args.batch // args.beam)], img, aud, args.alpha, args.batch, beam=args.beam)
+            beam_loop_s, beam_batched_s = [], []
+            for _ in range(3):
+                want_b, t = timed(beam_loop)
+                beam_loop_s.append(round(t, 3))
+                got_b, t = timed(lambda: weighted_predict(pairs, img, aud, args.alpha, args.batch, beam=args.beam))
+                beam_batched_s.append(round(t, 3))
+                equal["weighted_beam"] = equal.get("weighted_beam", True) and got_b == want_b
+            ntok_b = n_tokens(want_b)
+            out["beam"] = args.beam
+            out["beam_pairs_per_state"] = max(1, args.batch // args.beam)
+            out["beam_loop_s"] = beam_loop_s
+            out["beam_batched_s"] = beam_batched_s
+            out["beam_loop_tokens_per_s"] = round(ntok_b / min(beam_loop_s), 1)
+            out["beam_batched_tokens_per_s"] = round(ntok_b / min(beam_batched_s), 1)
+            out["beam_batched_slowest_vs_loop_fastest"] = round(min(beam_loop_s) / max(beam_batched_s), 2)
+            out["beam_batched_vs_greedy_batched_s"] = round(min(beam_batched_s) / t_batched, 2)
+            out["beam_differs_from_greedy"] = sum(1 for a, b in zip(want_b, want) if a != b)
     out["equal"] = equal
     out["batched_faster"] = t_batched < min(t_loop1, t_loop2)
     out["sweep_below_5x"] = t_sweep < 5 * t_batched
