@@ -196,7 +196,7 @@ __global__ void argmax_kernel(const float* __restrict__ x0, int n, long ld, long
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { idx_out[0] = si[0]; if (val_out) val_out[0] = sv[0]; }
+    if (threadIdx.x == 0) { idx_out[0] = si[0] < n ? si[0] : 0; if (val_out) val_out[0] = sv[0]; }      // no comparison won (all NaN): index 0, as torch.argmax
 }
 
 // ---------------------------------------------------------------- weighted late fusion (weighted_multimodal/test.py:50-61)
@@ -228,9 +228,10 @@ __global__ void weighted_argmax_kernel(const float* __restrict__ la0, long lda, 
         __syncthreads();
     }
     if (tid == 0) {
-        idx_out[row] = si[0];
+        const int pick = si[0] < n ? si[0] : 0;      // no comparison won (all NaN): index 0, never past the row
+        idx_out[row] = pick;
         if (prob_out) prob_out[row] = sa[0];
-        if (tokens_out) tokens_out[row] = si[0];
+        if (tokens_out) tokens_out[row] = pick;
     }
 }
 

@@ -27,16 +27,18 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
 #pragma unroll
             for (int e = 0; e < VEC; ++e) { x[e] = (v0 + e < V) ? to_f32(f[e]) : -INFINITY; cm = fmaxf(cm, x[e]); }
             const float nm = fmaxf(mx, cm);
+            const float sub = nm == -INFINITY ? 0.f : nm;      // only -inf so far: exp(-inf - -inf) is NaN, exp(-inf - 0) = 0 keeps s
             float add = 0.f;
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) add += __expf(x[e] - nm);
-            s = s * __expf(mx - nm) + add;
+            for (int e = 0; e < VEC; ++e) add += __expf(x[e] - sub);
+            s = s * __expf(mx - sub) + add;
             mx = nm;
         }
     } else {
         for (int v = threadIdx.x; v < V; v += 256) {
             const float x = to_f32(lr[v]), nm = fmaxf(mx, x);
-            s = s * __expf(mx - nm) + __expf(x - nm);
+            const float sub = nm == -INFINITY ? 0.f : nm;      // as above
+            s = s * __expf(mx - sub) + __expf(x - sub);
             mx = nm;
         }
     }
