@@ -82,7 +82,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 // LayerNorm of one row held by a wave, lane = PER consecutive columns: v <- (v - mean) * rstd * gamma + beta.  One definition
-// for add_ln_fwd_kernel (norm.hip) and the decode row kernel's prologue (decode.hip): the KV-cached step has to build the rows
+// for add_ln_fwd_kernel (norm.hip) and the decode row kernel's prologue (decode_linear.hip): the KV-cached step has to build the rows
 // the training forward builds, to the bit.
 template <int PER>
 __device__ __forceinline__ void ln_row(float (&v)[PER], const float* __restrict__ gamma, const float* __restrict__ beta, int lane, float eps, float& mu,
@@ -156,7 +156,7 @@ int attn_fwd_split_partials_rows(int dtype, const void* q, const void* k, const 
 // synchronises with __syncthreads): emit(j, index, log_softmax(x)[index]) for the j-th largest, j < k, ties towards the smaller
 // index, with the same values in every thread.  A max / sum-exp pass, then k selection passes over the candidates that come
 // after the previous pick in (value descending, index ascending) order.  sv / si: 256 entries of LDS each, the group's own.
-// One definition for topk_logprob_kernel (elementwise.hip) and the beam selection (decode.hip): the on-device beam search has
+// One definition for topk_logprob_kernel (elementwise.hip) and the beam selection (decode_beam.hip): the on-device beam search has
 // to rank the very floats the host route reads back.
 template <typename Emit>
 __device__ __forceinline__ void topk_logprob_row(const float* __restrict__ x, int n, int k, int tid, float* sv, int* si, Emit emit) {
@@ -230,7 +230,7 @@ __device__ __forceinline__ float weighted_mix(float la_i, float lb_i, const MixS
 // largest p, j < k, ties towards the smaller index, the same values in every thread.  Every selection pass recomputes p by the
 // one expression above, so k = 1 is weighted_argmax_kernel's pick and a row's result does not depend on the grid.  p = 0
 // (both exponentials underflowed) is a candidate like any other and emits -inf.  One definition for weighted_topk_logprob_kernel
-// (elementwise.hip) and the weighted beam selection (decode.hip).
+// (elementwise.hip) and the weighted beam selection (decode_beam.hip).
 template <typename Emit>
 __device__ __forceinline__ void weighted_topk_logprob_row(const float* __restrict__ la, const float* __restrict__ lb, int n, float wa, float wb, int k,
                                                           int tid, float* sa, float* sb, int* si, Emit emit) {
