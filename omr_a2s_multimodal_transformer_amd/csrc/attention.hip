@@ -216,10 +216,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint
             }
         l_run += psum;
         if constexpr (DROP) {
+            constexpr bool P_IS_CONVERTED = std::is_same<T, bf16>::value;      // acc_to_frag below: a VALU conversion only for bf16
 #pragma unroll
-            for (int r = 0; r < 16; ++r) st[0][r] = keep_or_zero(st[0][r], w0[r]);
+            for (int r = 0; r < 16; ++r) st[0][r] = keep_or_zero<P_IS_CONVERTED>(st[0][r], w0[r], lane);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) st[1][r] = keep_or_zero(st[1][r], w1[r]);
+            for (int r = 0; r < 16; ++r) st[1][r] = keep_or_zero<P_IS_CONVERTED>(st[1][r], w1[r], lane);
         }
         // O^T += V^T . P^T
 #pragma unroll

@@ -201,11 +201,22 @@ __device__ __forceinline__ float max_halves(float v) {
     return fmaxf(__uint_as_float(lo), __uint_as_float(hi));
 }
 
-// One score under its dropout bit: mask = the 64-bit word of this accumulator register (bit = lane)
-__device__ __forceinline__ float keep_or_zero(float x, uint64_t mask) {
-    float r;
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(mask));
-    return r;
+// One score under its dropout bit: mask = the 64-bit word of this accumulator register (bit = lane).
+// The compiler pads its own instructions with the wait states gfx950 wants (two between a VALU result and the MFMA that reads it)
+// but does not look inside an asm statement.  RESULT_FEEDS_VALU: the caller passes the result through a VALU instruction of the
+// compiler's before any MFMA reads it (the bf16 forward: the conversion to bf16), so the select may be the one v_cndmask_b32
+// with the word in an SGPR pair, written as an instruction.  Otherwise (the fp32 forward hands the result to the PV MFMA as it
+// is) the select is stated in C++ and every hazard is the compiler's.  DESIGN.md, "Attention error bounds", has the defect this
+// settles.
+template <bool RESULT_FEEDS_VALU>
+__device__ __forceinline__ float keep_or_zero(float x, uint64_t mask, int lane) {
+    if constexpr (RESULT_FEEDS_VALU) {
+        float r;
+        asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(mask));
+        return r;
+    } else {
+        return ((mask >> lane) & 1) ? x : 0.f;
+    }
 }
 __device__ __forceinline__ float keep_or(float x, float alt, uint64_t mask) {
     float r;
