@@ -477,6 +477,53 @@ int omr_ce_fwd(int dtype, const void* logits, const long* target, float* lse, do
 int omr_ce_bwd(int dtype, const void* logits, const long* target, const float* lse, const double* acc2, void* dlogits, long M, int V,
                long ldv, int pad_idx, float grad_scale, const float* grad_out, void* stream);
 
+/* ---- guarded optimizer step ------------------------------------------------------------------------------- */
+/* What the reference gets from Lightning: Trainer(precision="16-mixed") (src/train.py:153) puts every step behind GradScaler,
+ * which skips optimizer.step() when a gradient holds inf / NaN (torch/amp/grad_scaler.py, _maybe_opt_step), and
+ * Trainer(gradient_clip_val=..) clips by the global norm (torch.nn.utils.clip_grad_norm_).  Here the norm, the clip factor and the
+ * apply / skip decision are computed ON THE DEVICE into one small record that the guarded Adam launch reads: the host never waits
+ * for them (it reads a copy of the record one step late).
+ *
+ * omr_step_ctl: the record, device resident, 152 bytes.
+ *   sumsq            sum of g[i]^2 over all ranges (UNscaled gradient), fp64
+ *   norm             (float)(sqrt(sumsq) * grad_scale): the global L2 norm of the gradient the update would see
+ *   clip             1.0f when max_norm <= 0 or max_norm is not finite, else min(1.0f, max_norm / (norm + 1e-6f)) in fp32 -- the
+ *                    order of clip_grad_norm_ (torch/nn/utils/clip_grad.py)
+ *   apply            nonfinite == 0 && isfinite(sumsq)
+ *   nonfinite        number of inf / NaN ELEMENTS in the ranges, saturating at INT_MAX
+ *   range_sumsq[r]   range r's share of sumsq (entries >= n_ranges are 0); sumsq is their sum in index order
+ * Finite elements whose squares overflow fp32 (|g| > ~1.8e19) make the fp32 partial sum infinite: apply = 0 with nonfinite = 0.
+ * A gradient that large cannot be used by an fp32 Adam step either (its second moment overflows), so the step is skipped. */
+typedef struct omr_step_ctl {
+    double sumsq;
+    float norm, clip;
+    int apply, nonfinite;
+    double range_sumsq[16];
+} omr_step_ctl;
+#define OMR_GRAD_NORM_MAX_RANGES 16
+/* The reduction's fixed shape: every thread sums the squares of OMR_GRAD_NORM_K elements in fp32, in a fixed order; everything
+ * above that is fp64 in a fixed order.  Slot j of a range covers elements [j * CHUNK, (j + 1) * CHUNK) of that range, whatever
+ * the device: the result does not depend on the CU count and two runs give identical bits (no atomics).
+ * Error: all terms are >= 0, so |sumsq - exact| <= K 2^-24 sumsq and |norm - exact| <= (K / 2 + 2) 2^-24 norm. */
+#define OMR_GRAD_NORM_K 64
+#define OMR_GRAD_NORM_CHUNK 16384
+/* bytes of workspace for omr_grad_norm over n elements in n_ranges ranges (non-decreasing in n); OMR_ERR_ARG for n < 1 or
+ * n_ranges outside 1..16 */
+long omr_grad_norm_workspace_bytes(long n, int n_ranges);
+/* Two launches: (1) one workgroup per slot writes (sum of squares, non-finite count) of its chunk to ws; (2) one workgroup adds
+ * each range's slots in index order, the ranges in index order, and fills *ctl.  g: 16-byte aligned fp32 [n].  range_begin /
+ * range_end: HOST arrays [n_ranges] of element ranges [begin, end): sorted, disjoint, non-empty, inside [0, n), every begin a
+ * multiple of 4; 1 <= n_ranges <= 16.  Elements outside every range are not read.  Anything else, or a NULL g / ws / ctl, is
+ * refused with OMR_ERR_ARG before any launch.  ws: omr_grad_norm_workspace_bytes(n, n_ranges) bytes, 16-byte aligned. */
+int omr_grad_norm(const float* g, long n, const long* range_begin, const long* range_end, int n_ranges, float grad_scale,
+                  float max_norm, void* ws, omr_step_ctl* ctl, void* stream);
+/* omr_adam behind the record (torch optim/adam.py:347 after clip_grad_norm_; GradScaler's skip): when ctl->apply == 0 the
+ * launch writes NOTHING (p, m, v, p_bf16 keep their bits); otherwise g_i = (g[i] * grad_scale) * ctl->clip goes through the very
+ * update omr_adam applies (one device function), so with clip == 1.0f the results are omr_adam's bit for bit.  ctl is read on
+ * the device, in stream order behind omr_grad_norm. */
+int omr_adam_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2,
+                     float eps, float grad_scale, const omr_step_ctl* ctl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

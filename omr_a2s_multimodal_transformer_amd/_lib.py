@@ -47,6 +47,14 @@ def parse_header(path: str = HEADER) -> Dict[str, Tuple[str, List[str]]]:
     return protos
 
 
+def header_constant(name: str, path: str = HEADER) -> int:
+    """Value of an integer `#define NAME value` of the header (constants the Python side must share with the kernels)."""
+    m = re.search(r"^#define\s+" + re.escape(name) + r"\s+(-?\d+)\s*$", open(path).read(), flags=re.M)
+    if m is None:
+        raise KeyError(f"{path} has no integer #define {name}")
+    return int(m.group(1))
+
+
 def _ctype(t: str):
     if "*" in t:
         return ctypes.c_void_p

@@ -1,6 +1,7 @@
 // HBM-bound elementwise / gather / reduction kernels (gfx950): 16-byte vector access per lane,
 // grid-stride loops capped at 2048 blocks (256 CUs x 8).
 #include "omr_common.h"
+#include "adam_update.h"
 #include "omr_hip.h"
 
 namespace {
@@ -158,20 +159,11 @@ template <typename T> __global__ __launch_bounds__(256) void colsum_kernel(const
 }
 
 // ---------------------------------------------------------------- fused Adam over one flat buffer
-// torch optim/adam.py:347 single-tensor math (model.py:134-139: lr 1e-4, betas (0.9,0.999), eps 1e-8):
-//   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
-// Optionally writes the bf16 compute copy of the updated parameter in the same pass.
+// The per-element math is adam_update (adam_update.h), shared with the guarded step of optim.hip.
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             bf16* __restrict__ p_lp, long n, float lr_over_bc1, float b1, float b2, float eps, float inv_sqrt_bc2, float gscale) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float gi = g[i] * gscale;
-        float mi = b1 * m[i] + (1.f - b1) * gi;
-        float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        float pi = p[i] - lr_over_bc1 * (mi / denom);
-        m[i] = mi; v[i] = vi; p[i] = pi;
-        if (p_lp) p_lp[i] = (bf16)pi;
-    }
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        adam_update(p, m, v, p_lp, i, g[i] * gscale, lr_over_bc1, b1, b2, eps, inv_sqrt_bc2);
 }
 
 // ---------------------------------------------------------------- argmax over fp32 rows (greedy decode, model.py:187)

@@ -1,0 +1,173 @@
+// Guarded optimizer step (gfx950): global gradient norm, clip factor and the apply / skip decision on the device, and the Adam
+// launch that obeys them.  The host never waits for the decision: it is a record in device memory (omr_step_ctl, omr_hip.h) that
+// omr_adam_guarded reads in stream order and the host copies back one step late (params.FusedAdam).
+//
+// The norm is a two-stage slot reduction like the InstanceNorm statistics (norm.hip): no atomics, a fixed order at every level, a
+// chunk size that is a compile-time constant -- the bits do not depend on the CU count or on the run.
+//   stage 1  one workgroup per slot (GN_CHUNK = 256 threads x GN_K elements of ONE range): 16-byte loads, each thread adds its GN_K
+//            squares in fp32 in load order, the workgroup combines the 256 partial sums in fp64 by a halving tree and writes
+//            (sum of squares, number of inf / NaN elements) to its own slot.
+//   stage 2  one workgroup: thread r adds range r's slots in index order (fp64); thread 0 adds the ranges in index order and fills
+//            the record.
+#include <limits.h>
+
+#include "omr_common.h"
+#include "adam_update.h"
+#include "omr_hip.h"
+
+namespace {
+
+constexpr int GN_BLOCK = 256;
+constexpr int GN_K = OMR_GRAD_NORM_K;                  // elements per thread
+constexpr int GN_CHUNK = OMR_GRAD_NORM_CHUNK;          // elements per slot
+constexpr int GN_VECS = GN_K / 4;                      // 16-byte loads per thread
+constexpr int GN_TILE = 1024;                          // slots staged in LDS per round of stage 2
+constexpr int GN_MAXR = OMR_GRAD_NORM_MAX_RANGES;
+static_assert(GN_CHUNK == GN_BLOCK * GN_K && GN_K % 4 == 0, "slot = one workgroup's threads x K elements");
+
+struct GnSlot { double sumsq; long long bad; };        // 16 bytes
+struct GnRanges {                                      // by value in the kernel arguments
+    long begin[GN_MAXR], end[GN_MAXR];
+    int slot0[GN_MAXR + 1];                            // range r owns slots [slot0[r], slot0[r + 1])
+    int n_ranges;
+};
+
+__device__ __forceinline__ int is_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+__global__ __launch_bounds__(GN_BLOCK) void grad_norm_slots_kernel(const float* __restrict__ g, GnRanges rg, GnSlot* __restrict__ ws) {
+    __shared__ double ssum[GN_BLOCK];
+    __shared__ int sbad[GN_BLOCK];
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    int r = 0;
+    while (r + 1 < rg.n_ranges && slot >= rg.slot0[r + 1]) ++r;          // uniform: scalar compares
+    long rb = rg.begin[0], re = rg.end[0];
+    int s0 = rg.slot0[0];
+#pragma unroll
+    for (int k = 1; k < GN_MAXR; ++k)                                    // static indices: the argument struct stays in SGPRs
+        if (k == r) { rb = rg.begin[k]; re = rg.end[k]; s0 = rg.slot0[k]; }
+    const long base = rb + (long)(slot - s0) * GN_CHUNK;                 // a multiple of 4: g + base is 16-byte aligned
+    f32x4 x[GN_VECS];
+#pragma unroll
+    for (int j = 0; j < GN_VECS; ++j) {
+        const long e = base + 4l * (j * GN_BLOCK + tid);
+        if (e + 4 <= re) {
+            x[j] = *reinterpret_cast<const f32x4*>(g + e);
+        } else {                                                         // the range's last vector: nothing at or past `re` is read
+#pragma unroll
+            for (int c = 0; c < 4; ++c) x[j][c] = e + c < re ? g[e + c] : 0.f;
+        }
+    }
+    float acc = 0.f;
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < GN_VECS; ++j)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { acc += x[j][c] * x[j][c]; bad += is_nonfinite(x[j][c]); }
+    ssum[tid] = (double)acc;
+    sbad[tid] = bad;
+    __syncthreads();
+    for (int o = GN_BLOCK / 2; o > 0; o >>= 1) {
+        if (tid < o) { ssum[tid] += ssum[tid + o]; sbad[tid] += sbad[tid + o]; }
+        __syncthreads();
+    }
+    if (tid == 0) { GnSlot s; s.sumsq = ssum[0]; s.bad = sbad[0]; ws[slot] = s; }
+}
+
+__global__ __launch_bounds__(GN_BLOCK) void grad_norm_finish_kernel(const GnSlot* __restrict__ ws, GnRanges rg, float grad_scale, float max_norm,
+                                                                   omr_step_ctl* __restrict__ ctl) {
+    __shared__ GnSlot tile[GN_TILE];
+    __shared__ double rsum[GN_MAXR];
+    __shared__ long long rbad[GN_MAXR];
+    __shared__ int s0[GN_MAXR + 1];
+    const int tid = threadIdx.x, nr = rg.n_ranges;
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k <= GN_MAXR; ++k) s0[k] = rg.slot0[k];          // static indices: the argument struct stays in SGPRs
+    }
+    __syncthreads();
+    const int total = s0[nr];
+    const int lo = tid < nr ? s0[tid] : 0, hi = tid < nr ? s0[tid + 1] : 0;
+    double acc = 0.0;
+    long long bad = 0;
+    for (int t0 = 0; t0 < total; t0 += GN_TILE) {
+        for (int i = tid; i < GN_TILE && t0 + i < total; i += GN_BLOCK) tile[i] = ws[t0 + i];
+        __syncthreads();
+        const int a = lo > t0 ? lo : t0, b = hi < t0 + GN_TILE ? hi : t0 + GN_TILE;
+#pragma unroll 8
+        for (int k = a; k < b; ++k) { acc += tile[k - t0].sumsq; bad += tile[k - t0].bad; }      // index order
+        __syncthreads();
+    }
+    if (tid < GN_MAXR) { rsum[tid] = acc; rbad[tid] = bad; }             // threads >= nr hold zeros
+    __syncthreads();
+    if (tid == 0) {
+        double sumsq = 0.0;
+        long long nbad = 0;
+        for (int r = 0; r < GN_MAXR; ++r) {
+            ctl->range_sumsq[r] = rsum[r];
+            if (r < nr) { sumsq += rsum[r]; nbad += rbad[r]; }
+        }
+        const float norm = (float)(sqrt(sumsq) * (double)grad_scale);
+        float clip = 1.0f;
+        if (max_norm > 0.f && !is_nonfinite(max_norm)) clip = fminf(1.0f, max_norm / (norm + 1e-6f));
+        ctl->sumsq = sumsq;
+        ctl->norm = norm;
+        ctl->clip = clip;
+        ctl->apply = (nbad == 0 && !(sumsq != sumsq) && sumsq <= 1.7976931348623157e308) ? 1 : 0;
+        ctl->nonfinite = nbad > (long long)INT_MAX ? INT_MAX : (int)nbad;
+    }
+}
+
+// omr_adam's loop behind the record.  ctl->apply / ctl->clip are uniform loads; a skipped step leaves before the first access to
+// p, m, v, p_lp.
+__global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                    bf16* __restrict__ p_lp, long n, float lr_over_bc1, float b1, float b2, float eps, float inv_sqrt_bc2,
+                                    float gscale, const omr_step_ctl* __restrict__ ctl) {
+    if (ctl->apply == 0) return;
+    const float clip = ctl->clip;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        adam_update(p, m, v, p_lp, i, (g[i] * gscale) * clip, lr_over_bc1, b1, b2, eps, inv_sqrt_bc2);
+}
+
+inline long gn_slots(long len) { return (len + GN_CHUNK - 1) / GN_CHUNK; }
+
+}  // namespace
+
+extern "C" long omr_grad_norm_workspace_bytes(long n, int n_ranges) {
+    if (n < 1 || n_ranges < 1 || n_ranges > GN_MAXR) return OMR_ERR_ARG;
+    return (n / GN_CHUNK + n_ranges) * (long)sizeof(GnSlot);            // sum over ranges of ceil(len / CHUNK) <= n / CHUNK + n_ranges
+}
+
+extern "C" int omr_grad_norm(const float* g, long n, const long* range_begin, const long* range_end, int n_ranges, float grad_scale,
+                             float max_norm, void* ws, omr_step_ctl* ctl, void* stream) {
+    if (!g || !ws || !ctl || !range_begin || !range_end || n < 1 || n_ranges < 1 || n_ranges > GN_MAXR) return OMR_ERR_ARG;
+    if (((uintptr_t)g & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)ctl & 7)) return OMR_ERR_ARG;
+    GnRanges rg = {};
+    rg.n_ranges = n_ranges;
+    long prev_end = 0, slots = 0;
+    for (int r = 0; r < n_ranges; ++r) {
+        const long b = range_begin[r], e = range_end[r];
+        if (b < prev_end || e <= b || e > n || (b & 3)) return OMR_ERR_ARG;
+        rg.begin[r] = b; rg.end[r] = e; rg.slot0[r] = (int)slots;
+        slots += gn_slots(e - b);
+        prev_end = e;
+    }
+    if (slots > INT_MAX) return OMR_ERR_UNSUPPORTED;
+    rg.slot0[n_ranges] = (int)slots;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(grad_norm_slots_kernel, (int)slots, GN_BLOCK, 0, s, g, rg, (GnSlot*)ws);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, 1, GN_BLOCK, 0, s, (const GnSlot*)ws, rg, grad_scale, max_norm, ctl);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+extern "C" int omr_adam_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2,
+                                float eps, float grad_scale, const omr_step_ctl* ctl, void* stream) {
+    if (n <= 0) return OMR_OK;
+    if (step < 1 || !ctl) return OMR_ERR_ARG;
+    double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    const long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(adam_guarded_kernel, (int)(blocks > 2048 ? 2048 : blocks), 256, 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n,
+                       (float)(lr / bc1), b1, b2, eps, (float)(1.0 / sqrt(bc2)), grad_scale, ctl);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}

@@ -14,6 +14,12 @@ backward kernels.  finish() makes the compute stream wait for all outstanding bu
 Unused parameters (MultimodalTransformer drops a modality in ~20 % of the steps, model.py:510-519): their slice of
 the flat buffer simply stays zero and is reduced like any other -- every rank reduces the same buckets every
 step, so there is nothing to negotiate and nothing can hang.
+
+Guarded optimizer step (FusedAdam.enable_guard: gradient norm, clipping, skip of a non-finite step): grad_scale = 1/world
+reaches both of its kernels, so the norm is that of the MEAN gradient.  After the all-reduce every rank holds the same bucket
+bits, and the norm is a fixed-order reduction with no atomics whose shape does not depend on the device (csrc/optim.hip), so
+every rank computes the same record to the bit and takes the same clip factor and the same apply / skip decision -- no extra
+collective, and the replicas cannot drift apart over a skipped step.
 """
 from __future__ import annotations
 

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from ._lib import cur_stream, dtype_code, lib, ptr, require_cuda
+from ._lib import cur_stream, dtype_code, header_constant, lib, ptr, require_cuda
 
 Tensor = torch.Tensor
 
@@ -281,6 +281,64 @@ def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, 
     if p_lowp is not None:
         assert p_lowp.dtype == torch.bfloat16 and p_lowp.numel() == n
     lib().call("omr_adam", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_lowp), n, step, lr, betas[0], betas[1], eps, grad_scale, cur_stream())
+
+
+class StepCtl(ctypes.Structure):
+    """omr_step_ctl of include/omr_hip.h: the device-resident record of the guarded optimizer step."""
+    _fields_ = [("sumsq", ctypes.c_double), ("norm", ctypes.c_float), ("clip", ctypes.c_float), ("apply", ctypes.c_int),
+                ("nonfinite", ctypes.c_int), ("range_sumsq", ctypes.c_double * 16)]
+
+
+GRAD_NORM_K = header_constant("OMR_GRAD_NORM_K")              # elements a thread adds in fp32: the norm's error is <= (K / 2 + 2) 2^-24
+GRAD_NORM_CHUNK = header_constant("OMR_GRAD_NORM_CHUNK")      # elements per slot of the reduction
+GRAD_NORM_MAX_RANGES = header_constant("OMR_GRAD_NORM_MAX_RANGES")
+
+
+def grad_norm_workspace_bytes(n: int, n_ranges: int) -> int:
+    nbytes = lib().query("omr_grad_norm_workspace_bytes", n, n_ranges)
+    if nbytes < 0:
+        raise RuntimeError(f"libomr_hip: omr_grad_norm_workspace_bytes refused n = {n}, n_ranges = {n_ranges}")
+    return nbytes
+
+
+def new_step_ctl(device) -> Tensor:
+    """One omr_step_ctl in device memory (as bytes; read_step_ctl decodes a host copy)."""
+    return torch.zeros(ctypes.sizeof(StepCtl), dtype=torch.uint8, device=device)
+
+
+def read_step_ctl(host_bytes: Tensor) -> StepCtl:
+    """Decode a HOST copy of the record (a uint8 tensor of sizeof(omr_step_ctl) bytes whose copy has completed)."""
+    assert not host_bytes.is_cuda and host_bytes.dtype == torch.uint8 and host_bytes.numel() == ctypes.sizeof(StepCtl)
+    return StepCtl.from_buffer_copy(host_bytes.numpy().tobytes())
+
+
+def grad_norm(g: Tensor, ranges, grad_scale: float, max_norm: Optional[float], ws: Tensor, ctl: Tensor) -> None:
+    """Global L2 norm of g over the element ranges [(begin, end), ...] (sorted, disjoint, begins multiples of 4; at most 16), the
+    clip factor for max_norm (None / <= 0 / inf: no clipping) and the apply / skip decision, into the record `ctl` -- two
+    launches, nothing is read back (omr_grad_norm)."""
+    require_cuda(g, ws, ctl)
+    assert g.dtype == torch.float32 and g.is_contiguous()
+    nr = len(ranges)
+    assert ctl.numel() * ctl.element_size() == ctypes.sizeof(StepCtl)
+    assert 1 <= nr <= GRAD_NORM_MAX_RANGES and ws.numel() * ws.element_size() >= grad_norm_workspace_bytes(g.numel(), nr)
+    begins = (ctypes.c_long * nr)(*[b for b, _ in ranges])
+    ends = (ctypes.c_long * nr)(*[e for _, e in ranges])
+    lib().call("omr_grad_norm", ptr(g), g.numel(), begins, ends, nr, grad_scale, 0.0 if max_norm is None else max_norm, ptr(ws), ptr(ctl),
+               cur_stream())
+
+
+def adam_step_guarded(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                      grad_scale: float = 1.0, p_lowp: Optional[Tensor] = None, *, ctl: Tensor) -> None:
+    """adam_step behind the record grad_norm filled: no write at all when it says skip, else g * grad_scale * clip."""
+    require_cuda(p, g, m, v, ctl)
+    n = p.numel()
+    for t in (p, g, m, v):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    if p_lowp is not None:
+        assert p_lowp.dtype == torch.bfloat16 and p_lowp.numel() == n
+    assert ctl.numel() * ctl.element_size() == ctypes.sizeof(StepCtl)
+    lib().call("omr_adam_guarded", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_lowp), n, step, lr, betas[0], betas[1], eps, grad_scale, ptr(ctl),
+               cur_stream())
 
 
 def argmax(x: Tensor) -> Tuple[Tensor, Tensor]:

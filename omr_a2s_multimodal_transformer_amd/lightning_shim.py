@@ -64,8 +64,19 @@ class Trainer:
     rank-0 parameter broadcast, bucketed all-reduce overlapped with backward), steps the optimizer on the MEAN gradient
     (Lightning-DDP semantics) and the evaluation loops shard their samples over the ranks and all-reduce the metric counts."""
 
-    def __init__(self, max_epochs: int = 1, check_val_every_n_epoch: int = 1, reducer=None, log_every: int = 0, **_ignored):
+    def __init__(self, max_epochs: int = 1, check_val_every_n_epoch: int = 1, reducer=None, log_every: int = 0,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm", skip_nonfinite: bool = False, **_ignored):
+        """gradient_clip_val / gradient_clip_algorithm: Lightning's arguments; clipping by the global L2 norm ("norm") is what the
+        guarded optimizer step provides (FusedAdam.enable_guard), clipping by value is not built.  skip_nonfinite: skip an
+        optimizer step whose gradient holds inf / NaN, as the reference's GradScaler does under precision="16-mixed" (train.py:153).
+        Either one switches the guard on; with it, fit() logs `grad_norm` (one step late: the host never waits for the device)
+        and leaves the number of skipped steps in callback_metrics["skipped_steps"]."""
+        if gradient_clip_algorithm != "norm":
+            raise ValueError(f"gradient_clip_algorithm={gradient_clip_algorithm!r} is not supported: only \"norm\" (clipping by the global "
+                             "L2 norm, torch.nn.utils.clip_grad_norm_) is")
         self.max_epochs, self.check_val_every_n_epoch, self.reducer, self.log_every = max_epochs, check_val_every_n_epoch, reducer, log_every
+        self.gradient_clip_val = gradient_clip_val if gradient_clip_val else None       # Lightning: None and 0 both mean "no clipping"
+        self.skip_nonfinite = bool(skip_nonfinite)
         self.callback_metrics: Dict[str, Any] = {}
 
     @staticmethod
@@ -85,6 +96,9 @@ class Trainer:
 
     def fit(self, model, train_dataloaders: Iterable, val_dataloaders: Optional[Iterable] = None) -> None:
         opt = model.configure_optimizers()
+        guarded = self.gradient_clip_val is not None or self.skip_nonfinite
+        if guarded:
+            opt.enable_guard(max_norm=self.gradient_clip_val, skip_nonfinite=True)
         reducer = self._reducer_for(model)
         for epoch in range(self.max_epochs):
             model.train()
@@ -100,10 +114,16 @@ class Trainer:
                     opt.step(grad_scale=reducer.grad_scale)      # all-reduced SUM -> mean (1/world folded into the Adam kernel)
                 else:
                     opt.step()
+                if guarded and opt.settled_grad_norm is not None:
+                    model.log("grad_norm", opt.settled_grad_norm)        # the previous step's: step() has just settled it
                 if self.log_every and i % self.log_every == 0:
                     print(f"epoch {epoch} step {i} train_loss {float(loss):.4f}")
             if val_dataloaders is not None and (epoch + 1) % self.check_val_every_n_epoch == 0:
                 self.callback_metrics.update(self._eval(model, val_dataloaders, "val"))
+        if guarded:
+            if opt.last_grad_norm is not None:                           # waits for the last step
+                model.log("grad_norm", opt.last_grad_norm)
+            self.callback_metrics["skipped_steps"] = opt.skipped
 
     def _eval(self, model, loader: Iterable, name: str) -> Dict[str, float]:
         """Validation / test loop (bs = 1 samples, model.py:170-218).  Data parallel: rank r decodes samples r, r + world, ...;

@@ -167,6 +167,79 @@ class FlatParams:
         return ranges
 
 
+class StepLedger:
+    """Step counts of the guarded optimizer step when the apply / skip decision of a step arrives AFTER the next one is due:
+    host values only (no tensors, no events), in the spirit of evaluation.decode_rows, so a CPU test can script it.
+
+    count(names) counts a step TENTATIVELY for the sub-modules it touches and returns its index k; settle(k, applied) closes it:
+    a step that was not applied gives its +1 back to exactly those sub-modules and raises `skipped`.  At most one step is open:
+    the caller settles step k - 1 before it counts step k, so the counts it reads for step k's bias corrections are exact -- a
+    skipped step never counts, whichever sub-modules it touched."""
+
+    def __init__(self, names: Iterable[str]):
+        self.steps: Dict[str, int] = {n: 0 for n in names}
+        self.skipped = 0
+        self.issued = 0                                    # index of the next step
+        self._open: Optional[Tuple[int, Tuple[str, ...]]] = None
+
+    @property
+    def open(self) -> Optional[int]:
+        """Index of the step whose record has not been settled (None: every step is settled)."""
+        return None if self._open is None else self._open[0]
+
+    def count(self, names: Iterable[str]) -> int:
+        if self._open is not None:
+            raise RuntimeError(f"StepLedger: step {self._open[0]} has to be settled before the next one is counted")
+        names = tuple(names)
+        for n in names:
+            self.steps[n] += 1
+        k = self.issued
+        self.issued += 1
+        self._open = (k, names)
+        return k
+
+    def settle(self, k: int, applied: bool) -> None:
+        """Record k says applied / not applied.  Settling a step that is not open (again, or never counted) changes nothing."""
+        if self._open is None or self._open[0] != k:
+            return
+        if not applied:
+            for n in self._open[1]:
+                self.steps[n] -= 1
+            self.skipped += 1
+        self._open = None
+
+
+class _Guard:
+    """Device side of FusedAdam's guard: the reduction workspace, ONE omr_step_ctl on the device, and a two-deep ring of pinned host
+    copies with an event each (step k's copy goes to slot k % 2, so the last settled record stays readable while the next copy
+    is in flight)."""
+
+    def __init__(self, flat: FlatParams, max_norm: Optional[float]):
+        self.max_norm = max_norm
+        self.ws = torch.empty(K.grad_norm_workspace_bytes(flat.total, K.GRAD_NORM_MAX_RANGES), dtype=torch.uint8, device=flat.device)
+        self.ctl = K.new_step_ctl(flat.device)
+        self.ring = torch.zeros((2, self.ctl.numel()), dtype=torch.uint8)
+        if self.ctl.is_cuda:
+            self.ring = self.ring.pin_memory()
+        self.events: List[Optional[torch.cuda.Event]] = [None, None]
+        self.meta: List[Optional[Tuple[Tuple[str, ...], float]]] = [None, None]     # (range names, grad_scale) of the step in each slot
+        self.settled = None               # (StepCtl, names, grad_scale) of the newest settled record
+
+    def push(self, k: int, names: Tuple[str, ...], grad_scale: float) -> None:
+        self.ring[k % 2].copy_(self.ctl, non_blocking=True)
+        if self.events[k % 2] is None:
+            self.events[k % 2] = torch.cuda.Event()
+        self.events[k % 2].record()
+        self.meta[k % 2] = (names, grad_scale)
+
+    def pull(self, k: int) -> bool:
+        """Wait for step k's copy (one whole forward and backward old in steady state: no wait) and decode it -> applied."""
+        self.events[k % 2].synchronize()
+        rec = K.read_step_ctl(self.ring[k % 2])
+        self.settled = (rec,) + self.meta[k % 2]
+        return bool(rec.apply)
+
+
 class FusedAdam:
     """torch.optim.Adam(lr=1e-4, amsgrad=False) semantics (model.py:134-139,475-483) as one kernel launch per top-level
     sub-module over the flat buffers (one launch in the common case that every sub-module has gradients).
@@ -184,18 +257,81 @@ class FusedAdam:
         self.flat = flat
         self.param_groups = [dict(params=flat.params, lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False)]
         self.ranges = flat.module_ranges()
-        self.steps = {g: 0 for g in self.ranges}
+        self._ledger = StepLedger(self.ranges)             # owns `steps` and `skipped`
         self.touched_fn = touched_fn
+        self._guard: Optional[_Guard] = None
         if flat.exp_avg is None:
             flat.exp_avg = torch.zeros_like(flat.master)
             flat.exp_avg_sq = torch.zeros_like(flat.master)
 
     @property
+    def steps(self) -> Dict[str, int]:
+        """{top-level sub-module: optimizer steps applied to it}; with the guard on, the last step's count is tentative until
+        settle()."""
+        return self._ledger.steps
+
+    @steps.setter
+    def steps(self, value: Dict[str, int]) -> None:
+        self._ledger.steps = value
+
+    @property
     def step_count(self) -> int:
+        self.settle()
         return max(self.steps.values())
 
     def zero_grad(self, set_to_none: bool = False) -> None:
         self.flat.zero_grad()
+
+    # ---- guard: global gradient norm, clipping and the skip of a non-finite step, decided on the device (csrc/optim.hip)
+    def enable_guard(self, max_norm: Optional[float] = None, skip_nonfinite: bool = True) -> None:
+        """From the next step() on: one omr_grad_norm over the touched sub-modules' ranges, then omr_adam_guarded instead of
+        omr_adam.  max_norm: clip the gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_; None = no clipping).
+        A step whose gradient holds inf / NaN (or whose sum of squares overflows) writes nothing and does not count.  That
+        holds whenever the guard is on -- a clip factor computed from a non-finite norm has no meaning -- so skip_nonfinite only
+        says whether a guard WITHOUT clipping is wanted; enable_guard(None, False) asks for nothing and is refused.
+        The host learns of a step's outcome one step late (settle())."""
+        if max_norm is None and not skip_nonfinite:
+            raise ValueError("enable_guard: nothing to guard -- give max_norm and / or skip_nonfinite=True")
+        if max_norm is not None and not max_norm > 0:
+            raise ValueError(f"enable_guard: max_norm must be positive (got {max_norm}); None switches clipping off")
+        self.settle()
+        self._guard = _Guard(self.flat, max_norm)
+
+    def disable_guard(self) -> None:
+        """Back to the unguarded path (omr_adam alone); the step counts and `skipped` stay."""
+        self.settle()
+        self._guard = None
+
+    def settle(self) -> None:
+        """Close the last guarded step: wait for the copy of its record and, if the device skipped it, take its step count back."""
+        k = self._ledger.open
+        if k is not None:
+            self._ledger.settle(k, self._guard.pull(k))
+
+    @property
+    def skipped(self) -> int:
+        """Guarded steps the device did not apply."""
+        self.settle()
+        return self._ledger.skipped
+
+    @property
+    def last_grad_norm(self) -> Optional[float]:
+        """Global L2 norm of the last guarded step's gradient, times its grad_scale, before clipping (waits for that step)."""
+        self.settle()
+        return self.settled_grad_norm
+
+    @property
+    def settled_grad_norm(self) -> Optional[float]:
+        """The same for the newest step that is ALREADY settled -- one step behind right after step(); never waits."""
+        s = None if self._guard is None else self._guard.settled
+        return None if s is None else float(s[0].norm)
+
+    @property
+    def last_range_norms(self) -> Optional[Dict[str, float]]:
+        """{sub-module: L2 norm of its gradient range, times grad_scale} of the last guarded step (waits for that step)."""
+        self.settle()
+        s = None if self._guard is None else self._guard.settled
+        return None if s is None else {n: float(s[0].range_sumsq[r]) ** 0.5 * s[2] for r, n in enumerate(s[1])}
 
     def step(self, grad_scale: float = 1.0, touched=None) -> None:
         """touched: names of the top-level sub-modules that received gradients this step (None = all; default: ask the model)."""
@@ -204,29 +340,50 @@ class FusedAdam:
         if touched is None and self.touched_fn is not None:
             touched = self.touched_fn()
         names = list(self.ranges) if touched is None else [n for n in self.ranges if n in set(touched)]
-        for n in names:
-            self.steps[n] += 1
+        guard = self._guard if names else None
+        if guard is None:
+            for n in names:
+                self.steps[n] += 1
+        else:
+            # The previous step's outcome first (its copy is a whole forward and backward old: no wait in steady state), only
+            # then this step's count: the bias corrections below are exact although the decision is taken on the device.
+            self.settle()
+            k = self._ledger.count(names)
         from .runtime import WgradStream
         WgradStream.join()
         # merge neighbouring ranges that share a step count: one launch over the whole buffer in the common case
         runs: List[List[int]] = []
-        for n in sorted(names, key=lambda k: self.ranges[k][0]):
+        names = sorted(names, key=lambda nm: self.ranges[nm][0])
+        for n in names:
             b, e = self.ranges[n]
             if runs and runs[-1][1] == b and runs[-1][2] == self.steps[n]:
                 runs[-1][1] = e
             else:
                 runs.append([b, e, self.steps[n]])
+        if guard is not None:
+            K.grad_norm(f.grad, [self.ranges[n] for n in names], grad_scale, guard.max_norm, guard.ws, guard.ctl)
         for b, e, st in runs:
-            K.adam_step(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, g["lr"], g["betas"], g["eps"], grad_scale,
-                        p_lowp=None if f.lowp is None else f.lowp[b:e])
+            if guard is None:
+                K.adam_step(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, g["lr"], g["betas"], g["eps"], grad_scale,
+                            p_lowp=None if f.lowp is None else f.lowp[b:e])
+            else:
+                K.adam_step_guarded(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, g["lr"], g["betas"], g["eps"], grad_scale,
+                                    p_lowp=None if f.lowp is None else f.lowp[b:e], ctl=guard.ctl)
+        if guard is not None:
+            guard.push(k, tuple(names), grad_scale)
         f.updates += 1
-        f.refresh_flips()           # the next backward pass finds its data-gradient weights ready
+        f.refresh_flips()           # the next backward pass finds its data-gradient weights ready (harmless after a skipped step)
 
     def state_dict(self):
-        return dict(step=self.step_count, steps=dict(self.steps), exp_avg=self.flat.exp_avg, exp_avg_sq=self.flat.exp_avg_sq, param_groups=[
+        sd = dict(step=self.step_count, steps=dict(self.steps), exp_avg=self.flat.exp_avg, exp_avg_sq=self.flat.exp_avg_sq, param_groups=[
             {k: v for k, v in self.param_groups[0].items() if k != "params"}])
+        if self._guard is not None:
+            sd["skipped"] = self.skipped
+        return sd
 
     def load_state_dict(self, sd) -> None:
+        self.settle()
         self.steps = {g: int(sd.get("steps", {}).get(g, sd["step"])) for g in self.ranges}
+        self._ledger.skipped = int(sd.get("skipped", 0))
         self.flat.exp_avg.copy_(sd["exp_avg"])
         self.flat.exp_avg_sq.copy_(sd["exp_avg_sq"])
