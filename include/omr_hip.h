@@ -124,6 +124,37 @@ int omr_add_layernorm_bwd(int dtype, const void* dy, const void* x, const void* 
                           const float* rstd, void* ds, float* dgamma, float* dbeta, long M, int d, float drop_p,
                           unsigned long long drop_seed, void* dx, void* stream);
 
+/* ---- ragged batches: samples of different sizes in one padded plane ----------------------------------------- */
+/* The reference trains on inputs of different sizes at batch size 1 (its encoder, encoder.py:241-291, pads nothing: zero padding
+ * would move every conv's border and enter every InstanceNorm).  Here B samples share one NHWC plane x[B][H][W][C], sample b's
+ * content in the top-left corner, extents [B][2] int32 ON THE DEVICE = (h_b, w_b) at this layer's resolution (ceil(h / stride)
+ * per strided conv, the rule of omr_conv3x3_fwd's output size); every activation is kept zero outside its extent, which makes
+ * sample b's features and gradients those of b run alone (DESIGN.md "Ragged training").  No function below reads a value that
+ * lies outside an extent.  16-byte accesses when C is a multiple of 4 (fp32) / 8 (bf16), element-wise otherwise.  Limits: B <= 65535;
+ * H * W * C <= 2^31 - 1 per sample (and Smax * C for the pack pair), else OMR_ERR_ARG; the two InstanceNorm entries keep one channel
+ * group (4 / 8 channels, or 1 on the element-wise path) per thread of a 256-thread workgroup and return OMR_ERR_UNSUPPORTED beyond
+ * that: C <= 1024 (fp32) / 2048 (bf16) when C is a multiple of 4 / 8, C <= 256 otherwise.  omr_extent_zero and the pack pair take any C.
+ * A thread of the statistics passes adds its pixels in fp32 before the fp64 slot sum (omr_instnorm_stats' convention): 2048 pixels per
+ * workgroup over 256 / (channel groups) threads per group, i.e. up to 512 pixels per thread at the encoder's widest map (C = 256 fp32)
+ * and all 2048 at the widest C the entries take.
+ *   omr_extent_zero: x[b,i,j,:] = 0 for i >= h_b or j >= w_b, in place, after the bias + ReLU of encoder.py:163-176,222-236 made the
+ *     outside non-zero; its own adjoint, so the same call serves the gradient.  Stores to the outside only.
+ *   omr_instnorm_extent_fwd: nn.InstanceNorm2d(eps, affine=False) of encoder.py:151-156,174,232 with sums over the extent (count
+ *     h_b * w_b, biased variance, fp64 slots, omr_instnorm_finalize's arithmetic): y = (x - mean) * rstd inside, 0 outside; mean /
+ *     rstd [B][C] fp32.  workspace: omr_instnorm_workspace_bytes(B, C, omr_instnorm_extent_slots(B, H * W)), no clearing needed.
+ *   omr_instnorm_extent_bwd: dx = rstd * (g - sum g / n - xhat * sum(g * xhat) / n) [* (x > 0) * relu_scale] inside, 0 outside
+ *     (omr_instnorm_bwd over the extent); same workspace.
+ *   omr_pack_memory_fwd / _bwd: x.flatten(2).permute(0, 2, 1) of model.py:147 per sample: out[b][i * w_b + j][:] = x[b][i][j][:],
+ *     rows h_b * w_b <= r < Smax of out[B][Smax][C] zero; the backward scatters dout back (zeros outside, rows >= h_b * w_b ignored). */
+int omr_extent_zero(int dtype, void* x, const int* extents, int B, int H, int W, int C, void* stream);
+int omr_instnorm_extent_slots(int B, long HW);
+int omr_instnorm_extent_fwd(int dtype, const void* x, const int* extents, void* y, float* mean, float* rstd, int B, int H, int W, int C,
+                            float eps, void* workspace, void* stream);
+int omr_instnorm_extent_bwd(int dtype, const void* dxhat, const void* x, const float* mean, const float* rstd, const int* extents, void* dx,
+                            int B, int H, int W, int C, int relu_mask, float relu_scale, void* workspace, void* stream);
+int omr_pack_memory_fwd(int dtype, const void* x, const int* extents, void* out, int B, int H, int W, int C, int Smax, void* stream);
+int omr_pack_memory_bwd(int dtype, const void* dout, const int* extents, void* dx, int B, int H, int W, int C, int Smax, void* stream);
+
 /* ---- GEMM: C[M,N] (+)= act(opA(A) . opB(B)^T + bias) ------------------------------------------------------ */
 /* aten::linear/addmm/mm of the decoder layers (torch nn/modules/transformer.py:1158-1199), 1x1 point_conv
  * (encoder.py:65-70), Conv1d(k=1) head (decoder.py:98-102,146).  transA/transB: operand stored reduction-major.

@@ -1,12 +1,14 @@
 """Convolutional encoder on HIP kernels -- same classes, constructor signatures, attribute and state-dict
 names as the reference's src/transformer/encoder.py; activations are NHWC internally and every conv /
 norm / dropout is a hand-written gfx950 kernel (csrc/conv.hip, conv1.hip, dwconv.hip, norm.hip, gemm.hip, elementwise.hip).
+A padded batch of different-sized inputs takes the ragged route (`Encoder.forward_nhwc(..., extents=sizes)`, csrc/extent.hip).
 """
 from __future__ import annotations
 
 import math
+import os
 import random
-from typing import Optional, Tuple, Union
+from typing import NamedTuple, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -17,6 +19,24 @@ from .runtime import next_seed
 
 HEIGHT_REDUCTION = 16  # encoder.py:8
 WIDTH_REDUCTION = 8    # encoder.py:9
+
+# Ragged route, debugging aid: check after every block and residual add that the activation is exactly zero outside the extents (the
+# invariant every kernel of the route relies on; a consumer added later that breaks it is caught here).  One device sync per check.
+RAGGED_DEBUG = os.environ.get("OMR_RAGGED_DEBUG", "0") not in ("", "0")
+
+
+class ExtentTable(NamedTuple):
+    """Encoder.extent_table: the extents of a ragged batch at every resolution, computed and uploaded once per step."""
+    host: torch.Tensor      # int32 [levels, B, 2] on the host
+    dev: torch.Tensor       # the same on the device the encoder runs on
+
+
+def _assert_zero_outside(x: torch.Tensor, ext: torch.Tensor, what: str) -> None:
+    B, H, W, _ = x.shape
+    e = ext.to(x.device).long()
+    inside = (torch.arange(H, device=x.device).view(1, H, 1) < e[:, 0].view(B, 1, 1)) & (torch.arange(W, device=x.device).view(1, 1, W) < e[:, 1].view(B, 1, 1))
+    if bool((x.detach()[~inside] != 0).any()):
+        raise AssertionError(f"ragged route: {what} is not zero outside its samples' extents")
 
 
 class Conv2d(nn.Module):
@@ -79,6 +99,14 @@ class DepthSepConv2D(nn.Module):
         t = Fn.DwConv3x3Fn.apply(x, self.depth_conv.weight, self.depth_conv.bias, use_norm, mask_input, in_scale)
         return Fn.linear(t, self.point_conv.weight, self.point_conv.bias, relu=relu, mask_own=mask_own)
 
+    def nhwc_ragged(self, x: torch.Tensor, ext: torch.Tensor, relu: bool) -> torch.Tensor:
+        """Ragged batch (x zero outside the extents `ext`): both convs plain, each followed by the zeroing; a ReLU'd output applies
+        its own activation backward."""
+        t = Fn.DwConv3x3Fn.apply(x, self.depth_conv.weight, self.depth_conv.bias, False, False, 1.0)
+        t = Fn.ExtentZeroFn.apply(t, ext)
+        y = Fn.linear(t, self.point_conv.weight, self.point_conv.bias, relu=relu, mask_own=True)
+        return Fn.ExtentZeroFn.apply(y, ext)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.nhwc(_to_nhwc(x), False, False, 1.0, False, True).permute(0, 3, 1, 2)
 
@@ -105,12 +133,15 @@ class ConvBlock(nn.Module):
             return None
         return (p, next_seed("nhwc", p, channel_mode), channel_mode)
 
-    def nhwc(self, x: torch.Tensor, in_mask: bool, in_scale: float, defer_out: bool) -> Tuple[torch.Tensor, float]:
+    def nhwc(self, x: torch.Tensor, in_mask: bool, in_scale: float, defer_out: bool, extents=None) -> Tuple[torch.Tensor, float]:
         """x NHWC.  in_mask/in_scale: x is a ReLU(+dropout) output whose activation backward this block must
         apply.  defer_out: the consumer of the returned tensor applies OUR final ReLU(+dropout) backward;
         returns (y, scale) with scale = 1/(1-p) of a dropout applied after conv3 (else 1).
         Every conv is ONE kernel: bias, ReLU, the MixDropout of this position, the InstanceNorm statistics (conv2) and
-        the InstanceNorm apply (conv3's loads) are fused into it."""
+        the InstanceNorm apply (conv3's loads) are fused into it.
+        extents = (ext_in, ext_out): the ragged route (`_nhwc_ragged`), which returns scale 1 and defers nothing."""
+        if extents is not None:
+            return self._nhwc_ragged(x, extents[0], extents[1]), 1.0
         pos = random.randint(1, 3)  # encoder.py:160 (drawn in eval mode too)
         c1, c2, c3 = self.conv1, self.conv2, self.conv3
         d1 = self._drop() if pos == 1 else None
@@ -131,6 +162,26 @@ class ConvBlock(nn.Module):
         s3 = 1.0 / (1.0 - d3[0]) if d3 is not None else 1.0
         return x, s3
 
+    def _nhwc_ragged(self, x: torch.Tensor, ext_in: torch.Tensor, ext_out: torch.Tensor) -> torch.Tensor:
+        """Ragged batch: x [B, H, W, C] is zero outside ext_in [B, 2] (each sample's rows / columns at this resolution) and the
+        result is zero outside ext_out (= ceil(ext_in / stride)), which makes sample b's values those of b run alone at its own size
+        (DESIGN.md "Ragged training").  Every conv is the plain kernel with its own ReLU(+dropout) backward, followed by the zeroing;
+        the InstanceNorm is the stand-alone extent kernel: no normalise-on-load, no statistics epilogue, no gradient hand-on.
+        The `random` draws are those of the dense route."""
+        pos = random.randint(1, 3)  # encoder.py:160 (drawn in eval mode too)
+        convs = ((self.conv1, (1, 1), ext_in), (self.conv2, (1, 1), ext_in), (self.conv3, self.stride, ext_out))
+        for i, (c, stride, ext) in enumerate(convs, start=1):
+            d = self._drop() if pos == i else None
+            if i == 3:
+                x = Fn.InstNormExtentFn.apply(x, ext_in)
+            if d is not None and x.shape[-1] == 1:       # 1-channel first layer: direct kernel without the fused dropout
+                x = Fn.Conv3x3Fn.apply(x, c.weight, c.bias, stride, True, None, True, False, 1.0, None, False)
+                x = Fn.DropoutFn.apply(x, d[0], d[1], d[2], False)
+            else:
+                x = Fn.Conv3x3Fn.apply(x, c.weight, c.bias, stride, True, None, True, False, 1.0, d, False)
+            x = Fn.ExtentZeroFn.apply(x, ext)
+        return x
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         y, _ = self.nhwc(_to_nhwc(x), False, 1.0, False)
         return y.permute(0, 3, 1, 2)
@@ -149,8 +200,20 @@ class DSCBlock(nn.Module):
         self.conv3 = DepthSepConv2D(out_c, out_c, kernel_size=(3, 3), padding=(1, 1), stride=(1, 1))
         self.dropout = MixDropout(dropout_prob=dropout, dropout_2d_prob=dropout / 2)
 
-    def nhwc(self, x: torch.Tensor) -> torch.Tensor:
+    def nhwc(self, x: torch.Tensor, extents=None) -> torch.Tensor:
+        """extents [B, 2] (ragged batch, x zero outside them): the route of ConvBlock._nhwc_ragged, same `random` draws as the dense one."""
         pos = random.randint(1, 3)  # encoder.py:219
+        if extents is not None:
+            x = self.conv1.nhwc_ragged(x, extents, True)
+            if pos == 1:
+                x, _ = self.dropout.apply_nhwc(x, False)
+            x = self.conv2.nhwc_ragged(x, extents, True)
+            if pos == 2:
+                x, _ = self.dropout.apply_nhwc(x, False)
+            x = self.conv3.nhwc_ragged(Fn.InstNormExtentFn.apply(x, extents), extents, False)
+            if pos == 3:
+                x, _ = self.dropout.apply_nhwc(x, False)
+            return x
         x = self.conv1.nhwc(x, False, False, 1.0, True, False)
         s = 1.0
         if pos == 1:
@@ -196,7 +259,60 @@ class Encoder(nn.Module):
             DSCBlock(in_c=128, out_c=out_channels, stride=(1, 1), dropout=dropout),
         ])
 
-    def forward_nhwc(self, x: torch.Tensor, compute_dtype: torch.dtype) -> torch.Tensor:
+    def extent_levels(self, sizes: torch.Tensor) -> torch.Tensor:
+        """sizes [B, 2] = (height, width) of each sample in pixels -> int32 [n + 1, B, 2] on the host: level 0 the sizes themselves,
+        level i + 1 the extents behind conv block i, ceil(previous / stride) (kernels.conv_out_hw's rule).  The last level is
+        (ceil(h / 16), ceil(w / 8)): the feature grid, whose product is the sample's memory length."""
+        s = sizes.detach().to("cpu", torch.int64)
+        if s.dim() != 2 or s.shape[1] != 2 or bool((s < 1).any()):
+            raise ValueError(f"sizes must be [B, 2] positive (height, width) pairs, got {tuple(sizes.shape)}")
+        levels = [s]
+        for blk in self.conv_blocks:
+            st = torch.tensor(blk.stride, dtype=torch.int64)
+            levels.append((levels[-1] + st - 1) // st)
+        return torch.stack(levels).to(torch.int32)
+
+    def extent_table(self, sizes: torch.Tensor, device) -> ExtentTable:
+        """extent_levels(sizes) on the host and, in ONE copy, on `device`: what forward_nhwc(extents=...) and the caller's pack / key
+        mask share, so that a step computes and uploads it once."""
+        host = self.extent_levels(sizes)
+        return ExtentTable(host, host.to(device, non_blocking=True))
+
+    def _forward_nhwc_ragged(self, x: torch.Tensor, compute_dtype: torch.dtype, extents) -> torch.Tensor:
+        """forward_nhwc over a padded batch whose sample b fills the top-left (h_b, w_b) pixels: -> [B, ceil(H/16), ceil(W/8), C]
+        with sample b's features, those of b encoded alone, in the top-left ceil(h_b/16) x ceil(w_b/8) cells and zeros elsewhere.
+        extents: the pixel sizes [B, 2], or the ExtentTable made from them."""
+        table = extents if isinstance(extents, ExtentTable) else self.extent_table(extents, x.device)
+        levels = table.host
+        if x.shape[0] != levels.shape[1] or int(levels[0, :, 0].max()) > x.shape[2] or int(levels[0, :, 1].max()) > x.shape[3]:
+            raise ValueError(f"sizes {levels[0].tolist()} do not fit the batch {tuple(x.shape)}")
+        src = x
+        x = _to_nhwc(x)
+        if x.dtype != compute_dtype:
+            x = K.cast(x, compute_dtype)
+        elif x.data_ptr() == src.data_ptr():
+            x = x.clone()                                  # the zeroing below is in place: not on the caller's tensor
+        lv = table.dev
+        x = Fn.ExtentZeroFn.apply(x, lv[0])                # the collate pad value is the caller's
+        for i, blk in enumerate(self.conv_blocks):
+            x, _ = blk.nhwc(x, False, 1.0, False, extents=(lv[i], lv[i + 1]))
+            if RAGGED_DEBUG:
+                _assert_zero_outside(x, lv[i + 1], f"the output of conv block {i}")
+        if torch.is_grad_enabled() and x.requires_grad:
+            from .ddp import GradBoundary                  # as in forward_nhwc
+            x = GradBoundary.apply(None, (), x)
+        for blk in self.dscblocks:
+            xt = blk.nhwc(x, extents=lv[-1])
+            x = Fn.AddFn.apply(x, xt) if x.shape == xt.shape else xt  # encoder.py:289
+            if RAGGED_DEBUG:
+                _assert_zero_outside(x, lv[-1], "a DSC block's output")
+        return x
+
+    def forward_nhwc(self, x: torch.Tensor, compute_dtype: torch.dtype, extents=None) -> torch.Tensor:
+        """extents [B, 2] = (height, width) in pixels of each sample's content in the top-left corner of the padded batch x (or the
+        ExtentTable made from them, `extent_table`): the ragged route.  None: every sample fills the plane."""
+        if extents is not None:
+            return self._forward_nhwc_ragged(x, compute_dtype, extents)
         x = _to_nhwc(x)
         if x.dtype != compute_dtype:
             x = K.cast(x, compute_dtype)

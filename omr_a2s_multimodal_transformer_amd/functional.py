@@ -286,6 +286,58 @@ class AddPE2DFn(Function):
         return g, None
 
 
+class ExtentZeroFn(Function):
+    """x[b, i, j, :] = 0 outside sample b's extent (ragged batches, csrc/extent.hip), in place; the op is its own adjoint.
+    The zeros are written through the kernel, behind autograd's back: the producer conv has saved this very tensor as its ReLU
+    mask, and the zeroed tensor is the mask it needs ((y > 0) is false outside the extent, which is this op's backward).  The
+    backward zeroes the incoming gradient in place too: a gradient that another branch shares (the residual add) belongs to a
+    tensor that is itself zero outside the extents, so whoever else reads it zeroes or ignores its outside as well.
+    WARNING for whoever extends the ragged route: neither write is visible to autograd (no mark_dirty, no version bump), so nothing
+    raises if a new consumer saves the producer's output BEFORE this op and reads it in backward expecting the unzeroed values, or
+    reads the shared gradient's outside after it.  Consume only this op's result; encoder.RAGGED_DEBUG checks the forward invariant."""
+
+    @staticmethod
+    def forward(ctx, x, ext):
+        ctx.ext = ext
+        K.extent_zero(x, ext)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return K.extent_zero(g.contiguous(), ctx.ext), None
+
+
+class InstNormExtentFn(Function):
+    """InstanceNorm2d(eps=1e-3, affine=False) over each sample's extent, stand-alone (the ragged route normalises before conv3
+    instead of on its loads): y = (x - mean) * rstd inside, 0 outside."""
+
+    @staticmethod
+    def forward(ctx, x, ext):
+        y, mean, rstd = K.instnorm_extent_fwd(x, ext)
+        ctx.ext = ext
+        ctx.save_for_backward(x, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mean, rstd = ctx.saved_tensors
+        return K.instnorm_extent_bwd(g.contiguous(), x, mean, rstd, ctx.ext), None
+
+
+class PackMemoryFn(Function):
+    """Feature grid [B, H', W', d] of a ragged batch -> decoder memory [B, smax, d] (x.flatten(2).permute(0, 2, 1) of each sample's
+    own h'_b x w'_b grid, model.py:147); rows past a sample's own length are zeros, and masked by the caller."""
+
+    @staticmethod
+    def forward(ctx, x, ext, smax):
+        ctx.ext, ctx.hw = ext, (x.shape[1], x.shape[2])
+        return K.pack_memory_fwd(x.contiguous(), ext, smax)
+
+    @staticmethod
+    def backward(ctx, g):
+        return K.pack_memory_bwd(g.contiguous(), ctx.ext, *ctx.hw), None, None
+
+
 class DropoutFn(Function):
     """nn.Dropout / nn.Dropout2d with a counter-based mask that is regenerated (not stored) in backward.
     bwd_identity: the consumer applies (x > 0) * 1/(1-p) itself (see module docstring)."""

@@ -113,6 +113,22 @@ def pad_batch_inputs(x: Sequence[Tensor], pad_value: float = 0.0, dtype: torch.d
     return out
 
 
+def collate_ragged(images: Sequence[Tensor]) -> Tuple[Tensor, Tensor]:
+    """Samples [C, h_b, w_b] (or [h_b, w_b]) of different sizes -> (x [B, C, max h, max w] padded with zeros at the right and the
+    bottom, sizes int64 [B, 2] = (h_b, w_b) on the host): the (x, xl) pair of `Transformer.forward`'s ragged route and of
+    `Transformer.encode_ragged`.  Works on host or device tensors (plain copies, no kernel)."""
+    if len(images) == 0:
+        raise ValueError("collate_ragged needs at least one image")
+    imgs = [im.unsqueeze(0) if im.dim() == 2 else im for im in images]
+    if any(im.dim() != 3 or im.shape[0] != imgs[0].shape[0] for im in imgs):
+        raise ValueError("expected images [C, h, w] (or [h, w]) with the same number of channels")
+    sizes = torch.tensor([[int(im.shape[1]), int(im.shape[2])] for im in imgs], dtype=torch.int64)
+    out = torch.zeros((len(imgs), imgs[0].shape[0], int(sizes[:, 0].max()), int(sizes[:, 1].max())), dtype=imgs[0].dtype, device=imgs[0].device)
+    for i, im in enumerate(imgs):
+        out[i, :, : im.shape[1], : im.shape[2]] = im
+    return out, sizes
+
+
 def image_batch(raws: Sequence, img_height: Optional[int], pad_value: float = 1.0, dtype: torch.dtype = torch.float32, device=None) -> Tuple[Tensor, Tensor]:
     """preprocess_image + pad_batch_inputs(pad_value=1.0: white background, preprocessing.py:104-109) in one go: every image is
     resampled straight into its slot of the padded batch.  Returns (x [B, 1, Hmax, Wmax], widths int32 [B])."""

@@ -462,6 +462,74 @@ def instnorm_bwd(dxhat: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, relu_mask
     return dx
 
 
+# ------------------------------------------------------------------------------------------------ ragged batches (csrc/extent.hip)
+
+def _check_extents(x: Tensor, ext: Tensor) -> Tuple[int, int, int, int]:
+    """x NHWC, ext int32 [B, 2] on x's device = (rows, columns) of each sample's content in the top-left corner of its plane."""
+    require_cuda(x, ext)
+    assert x.dim() == 4 and x.is_contiguous(), f"expected a contiguous NHWC tensor, got shape {tuple(x.shape)} strides {x.stride()}"
+    assert ext.dtype == torch.int32 and ext.is_contiguous() and tuple(ext.shape) == (x.shape[0], 2) and ext.device == x.device, \
+        f"extents must be int32 [B, 2] on the device of x, got {ext.dtype} {tuple(ext.shape)} on {ext.device}"
+    return tuple(x.shape)
+
+
+def _extent_stat_ws(B: int, H: int, W: int, C: int, device) -> Tensor:
+    """Workspace of the extent statistics passes (slots per sample from the library; a negative value is its error code)."""
+    slots = lib().query("omr_instnorm_extent_slots", B, H * W)
+    assert slots > 0, f"omr_instnorm_extent_slots({B}, {H * W}) failed: {slots}"
+    return _stat_ws(B, C, slots, device, False)
+
+
+def extent_zero(x: Tensor, ext: Tensor) -> Tensor:
+    """x[b, i, j, :] = 0 for i >= ext[b, 0] or j >= ext[b, 1], IN PLACE (returns x).  Stores to the outside only."""
+    B, H, W, C = _check_extents(x, ext)
+    lib().call("omr_extent_zero", dtype_code(x.dtype), ptr(x), ptr(ext), B, H, W, C, cur_stream())
+    return x
+
+
+def instnorm_extent_fwd(x: Tensor, ext: Tensor, eps: float = 1e-3) -> Tuple[Tensor, Tensor, Tensor]:
+    """InstanceNorm over each sample's extent: -> (y = (x - mean) * rstd inside / 0 outside, mean [B, C], rstd [B, C])."""
+    B, H, W, C = _check_extents(x, ext)
+    y = torch.empty_like(x)
+    mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    ws = _extent_stat_ws(B, H, W, C, x.device)
+    lib().call("omr_instnorm_extent_fwd", dtype_code(x.dtype), ptr(x), ptr(ext), ptr(y), ptr(mean), ptr(rstd), B, H, W, C, eps, ptr(ws), cur_stream())
+    return y, mean, rstd
+
+
+def instnorm_extent_bwd(dxhat: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, ext: Tensor, relu_mask: bool = False, relu_scale: float = 1.0) -> Tensor:
+    """Backward of instnorm_extent_fwd (dxhat = gradient of y; its values outside the extents are not read); optionally times
+    (x > 0) * relu_scale, the activation backward of the producer of x."""
+    B, H, W, C = _check_extents(x, ext)
+    assert dxhat.shape == x.shape and dxhat.dtype == x.dtype and dxhat.is_contiguous()
+    assert mean.dtype == rstd.dtype == torch.float32 and mean.numel() == rstd.numel() == B * C
+    dx = torch.empty_like(x)
+    ws = _extent_stat_ws(B, H, W, C, x.device)
+    lib().call("omr_instnorm_extent_bwd", dtype_code(x.dtype), ptr(dxhat), ptr(x), ptr(mean), ptr(rstd), ptr(ext), ptr(dx), B, H, W, C, int(relu_mask),
+               float(relu_scale), ptr(ws), cur_stream())
+    return dx
+
+
+def pack_memory_fwd(x: Tensor, ext: Tensor, smax: int) -> Tensor:
+    """Feature grid [B, H, W, d] -> decoder memory [B, smax, d]: row i * w_b + j of sample b = cell (i, j); rows >= h_b * w_b zero."""
+    B, H, W, C = _check_extents(x, ext)
+    assert smax >= 1
+    out = torch.empty((B, smax, C), dtype=x.dtype, device=x.device)
+    lib().call("omr_pack_memory_fwd", dtype_code(x.dtype), ptr(x), ptr(ext), ptr(out), B, H, W, C, smax, cur_stream())
+    return out
+
+
+def pack_memory_bwd(dout: Tensor, ext: Tensor, H: int, W: int) -> Tensor:
+    """Adjoint of pack_memory_fwd: gradient [B, smax, d] -> [B, H, W, d], zeros outside the extents."""
+    require_cuda(dout, ext)
+    assert dout.dim() == 3 and dout.is_contiguous() and ext.dtype == torch.int32 and ext.is_contiguous() and tuple(ext.shape) == (dout.shape[0], 2)
+    B, smax, C = dout.shape
+    dx = torch.empty((B, H, W, C), dtype=dout.dtype, device=dout.device)
+    lib().call("omr_pack_memory_bwd", dtype_code(dout.dtype), ptr(dout), ptr(ext), ptr(dx), B, H, W, C, smax, cur_stream())
+    return dx
+
+
 def add_layernorm_fwd(x: Tensor, res: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float = 1e-5, drop_p: float = 0.0, drop_seed: int = 0):
     """LayerNorm(dropout(x) + res); drop_p = 0 is the plain residual add."""
     require_cuda(x, res, gamma, beta)

@@ -458,9 +458,48 @@ class Transformer(_Base):
         f = self.encoder.forward_nhwc(x, flat.compute_dtype).permute(0, 3, 1, 2)
         return self._boundary(_flatten_memory(self.pos_2d(f)))
 
+    def _encode_packed(self, x: torch.Tensor, sizes: torch.Tensor) -> Tuple[torch.Tensor, List[int], torch.Tensor]:
+        """Ragged batch: x [B, C, Hmax, Wmax] with sample b's sizes[b] = (h_b, w_b) pixels in the top-left corner -> (memory
+        [B, Smax, d], [S_b], S_b on the device) with S_b = ceil(h_b / 16) * ceil(w_b / 8): rows [0, S_b) of sample b are `encode` of b
+        alone (to rounding: the InstanceNorm sums are added in another order), the rows behind them zeros.  encoder -> 2-D PE on the
+        padded grid -> pack.  The extents of all resolutions are computed and uploaded once (Encoder.extent_table)."""
+        flat = self.ensure_flat()
+        if sizes.dim() != 2 or sizes.shape != (x.shape[0], 2):
+            raise ValueError(f"per-sample sizes must be [B, 2] (height, width), got {tuple(sizes.shape)} for a batch of {x.shape[0]}")
+        x = x.to(flat.device, non_blocking=True)
+        table = self.encoder.extent_table(sizes, flat.device)
+        grid, grid_dev = table.host[-1], table.dev[-1]                            # int32 [B, 2]: each sample's feature grid
+        lens = (grid[:, 0].long() * grid[:, 1].long()).tolist()
+        f = self.encoder.forward_nhwc(x, flat.compute_dtype, extents=table).permute(0, 3, 1, 2)
+        f = self.pos_2d(f).permute(0, 2, 3, 1)                                    # NHWC again (a view of the PE kernel's output)
+        mem = Fn.PackMemoryFn.apply(f, grid_dev, max(lens))
+        return self._boundary(mem), lens, grid_dev[:, 0] * grid_dev[:, 1]
+
+    @torch.no_grad()
+    def encode_ragged(self, x: torch.Tensor, sizes: torch.Tensor) -> List[torch.Tensor]:
+        """Memories [S_b, d] of a padded batch of inputs of different sizes (`image.collate_ragged`), one encoder pass for all:
+        each equals `encode` of that input alone to rounding (not bit for bit: `predict` / `evaluate` keep the batch-size-1 encoder)."""
+        mem, lens, _ = self._encode_packed(x, sizes)
+        return [mem[b, :n] for b, n in enumerate(lens)]
+
     def forward(self, x: torch.Tensor, xl: torch.Tensor, y_in: torch.Tensor) -> torch.Tensor:
+        """xl as the decoder's memory_len, the reference's forms (every sample fills the plane of x): None, integer lengths [B], or a bool
+        key-padding mask [B, S].  An INTEGER xl of shape [B, 2] -- never a valid memory_len -- holds the (height, width) in pixels
+        of each sample's content in the top-left corner of x and takes the ragged route: sample b's logits, loss share and gradients are
+        those of b run alone at its own size; the memory rows past a sample's own length are masked out (-inf)."""
+        if self._is_pixel_sizes(xl):
+            mem, _, lens_dev = self._encode_packed(x, xl)
+            pad = torch.arange(mem.shape[1], device=mem.device).unsqueeze(0) >= lens_dev.unsqueeze(1)     # bool [B, Smax]: True = no key
+            return self.decoder(tgt=y_in, memory=mem, memory_len=pad)
         mem = self.encode(x)
         return self.decoder(tgt=y_in, memory=mem, memory_len=xl)     # host-resident ids / lengths go as they are: the decoder reads them before the copy
+
+    @staticmethod
+    def _is_pixel_sizes(xl) -> bool:
+        """Whether `forward`'s xl names per-sample pixel sizes (the ragged route): a 2-D tensor [B, 2] of an integer type.  A bool
+        [B, S] key-padding mask (also with S == 2) and everything else is a memory_len and goes to the decoder as it always did."""
+        return (isinstance(xl, torch.Tensor) and xl.dim() == 2 and xl.shape[1] == 2 and xl.dtype != torch.bool
+                and not xl.is_floating_point() and not xl.is_complex())
 
     def apply_teacher_forcing(self, y: torch.Tensor) -> torch.Tensor:
         """model.py:152-160: each non-pad token is replaced w.p. teacher_forcing_prob by randint(0, V-1) drawn
