@@ -5,6 +5,7 @@
 
 #include "omr_common.h"
 #include "launch_setup.h"
+#include "instnorm_slots.h"
 
 namespace omr_conv {
 
@@ -53,7 +54,7 @@ struct ConvArgs {
     //   mode 1: {sum y, sum y^2}            -> InstanceNorm statistics of this conv's output (encoder.py:174)
     //   mode 2: {sum g, sum g * xhat}       -> InstanceNorm backward sums, xhat = (stat_x - mean) * rstd at the same position
     // The reduction is DETERMINISTIC: per-thread fp32 partials (fixed tile walk) -> fixed-order fp64 sum over the block's
-    // threads -> plain store into the block's own slot stat_ws[b][blockIdx.x][COUT][2]; the consumer (omr_instnorm_finalize /
+    // threads -> slot_store into the block's own slot (instnorm_slots.h: layout, spare slots); the consumer (omr_instnorm_finalize /
     // omr_instnorm_bwd_apply) adds the stat_slots slots of an image in index order.  No atomics anywhere.
     //   mode 4: the sums of mode 2 WITHOUT storing the output; mode 5: the output of mode 2 with the InstanceNorm backward
     //           applied in the epilogue,  dx = rstd * (g - s1 - xhat * s2) [* (stat_x > 0) * stat_relu_scale],  s1 / s2 = the
@@ -171,11 +172,7 @@ __global__ __launch_bounds__(256, (SINGLE && NT == 32) ? ((CK == 16 && EPI != 2)
                     const int n = n0 + i;
                     double acc2 = 0.0;
                     for (int g = 0; g < NGRP; ++g) acc2 += (double)red[g * RP + i];
-                    if (n < a.COUT) {
-                        a.stat_ws[(((long)bimg * a.stat_slots + blockIdx.x) * a.COUT + n) * 2 + k] = acc2;
-                        if (blockIdx.x == 0)          // slots no block of this launch owns read as zero: the caller need not clear the workspace
-                            for (int sl = gridDim.x; sl < a.stat_slots; ++sl) a.stat_ws[(((long)bimg * a.stat_slots + sl) * a.COUT + n) * 2 + k] = 0.0;
-                    }
+                    if (n < a.COUT) slot_store(a.stat_ws, bimg, a.stat_slots, a.COUT, n, k, acc2);
                 }
             }
         }
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(256, (SINGLE && NT == 32) ? ((CK == 16 && EPI != 2)
     const int b = blockIdx.z;
     if constexpr (EPI == 2) {
         if (stat2 || apply5) {
-            const double* compact = a.stat_ws + (long)a.B * a.stat_slots * a.COUT * 2;       // [B][COUT][2]: the image's finished sums (mode 5)
+            const double* compact = a.stat_ws + slot_compact_offset(a.B, a.stat_slots, a.COUT);       // [B][COUT][2]: the image's finished sums (mode 5)
             const double inv_hw = 1.0 / ((double)a.Ho * a.Wo);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
@@ -450,7 +447,7 @@ __global__ __launch_bounds__(256, (SINGLE && NT == 32) ? ((CK == 16 && EPI != 2)
                 __builtin_memcpy(&v, &bits, sizeof(bits));
             }
             if constexpr (EPI == 2) {
-                if (apply5) {          // InstanceNorm backward on the way out (norm.hip instnorm_bwd_apply_kernel's arithmetic)
+                if (apply5) {          // InstanceNorm backward on the way out (instnorm_slots.h instnorm_apply_kernel's arithmetic)
                     const F xv = *reinterpret_cast<const F*>(SX + o);
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {

@@ -36,6 +36,7 @@
 #include "omr_hip.h"
 #include "dma_common.h"
 #include "launch_setup.h"
+#include "instnorm_slots.h"
 
 namespace {
 
@@ -144,6 +145,59 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base, int off0, i
     const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LdsV4*)(base + off0 + imm));
     const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LdsV4*)(base + off1 + imm));
     return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
+// ---- normalise-on-load pieces shared by the stride-1 XN mode and the stride-2 kernel: the conv normalised its input X (CI channels, tile
+//      Tile<CI>) on load, so xhat is the weight gradient's operand and the data gradient dL/dxhat leaves with the InstanceNorm-backward sums
+//      {sum dx, sum dx * xhat} in the slots of instnorm_slots.h (what conv3x3_mfma.h's stat_mode 2 epilogue does for the separate kernel).
+typedef __attribute__((ext_vector_type(4))) bf16 B4;
+// xhat = x * rstd - mean * rstd in place over the X tile of the tile at (oh0, ow0): one 16-byte chunk per thread, cst = [rstd | -mean * rstd]
+// per channel; pixels of an overhanging tile stay 0
+template <int CI> __device__ __forceinline__ void xhat_pass(unsigned char* Xt, const float* cst, int tid, int oh0, int ow0, int H, int W) {
+    constexpr int XCPP = CI / 8, NXCH = NCORE * XCPP;
+    static_assert(NXCH <= 1024, "one chunk per thread");
+    if (tid < NXCH) {
+        const int pix = tid / XCPP, k = tid % XCPP;
+        if (oh0 + (pix >> 5) < H && ow0 + (pix & 31) < W) {
+            unsigned char* px = Xt + Tile<CI>::chunk(pix, pix & 31, k);
+            bf16x8 v = *reinterpret_cast<const bf16x8*>(px);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (bf16)fmaf((float)v[e], cst[k * 8 + e], cst[32 + k * 8 + e]);
+            *reinterpret_cast<bf16x8*>(px) = v;
+        }
+    }
+}
+// the stored run o = channels 8 g4 + 4 h .. + 3 of pixel (wave, frow) joins the lane's partial sums (xrow = X tile + 8 h); pixels outside the image add 0
+template <int CI> __device__ __forceinline__ void stat_accumulate(const B4& o, const unsigned char* xrow, int wave, int frow, int g4, bool inside, float* ssum,
+                                                                  float* ssq) {
+    const B4 xh = *reinterpret_cast<const B4*>(xrow + Tile<CI>::chunk(wave * TW + frow, frow, g4));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const float f = inside ? (float)o[e] : 0.f; ssum[4 * g4 + e] += f; ssq[4 * g4 + e] += f * (float)xh[e]; }
+}
+// DETERMINISTIC reduction of the workgroup's partial sums (called by all 1024 threads once the ring is dead): the 256 data-gradient lanes of
+// a channel lay theirs out as red[2][CI][256] over the ring, thread (k, c) adds its 256 in index order in fp64, slot_store does the rest
+template <int CI, bool DG> __device__ __forceinline__ void stat_reduce(unsigned char* smem, const float* ssum, const float* ssq, int tid, int wave, int frow,
+                                                                       int h, int b, double* stat_ws, int stat_slots) {
+    float* red = reinterpret_cast<float*>(smem);
+    __syncthreads();
+    if constexpr (DG) {
+        const int j = wave * 32 + frow;
+#pragma unroll
+        for (int g4 = 0; g4 < CI / 8; ++g4)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c = 8 * g4 + 4 * h + e;
+                red[c * 256 + j] = ssum[4 * g4 + e];
+                red[(CI + c) * 256 + j] = ssq[4 * g4 + e];
+            }
+    }
+    __syncthreads();
+    if (DG && tid < 2 * CI) {
+        const int k = tid / CI, c = tid - k * CI;
+        double acc2 = 0.0;
+        for (int j = 0; j < 256; ++j) acc2 += (double)red[(k * CI + c) * 256 + j];
+        slot_store(stat_ws, b, stat_slots, CI, c, k, acc2);
+    }
 }
 
 // One tile loop, compiled twice: DG = the data-gradient waves (0-7), !DG = the weight-gradient / DMA waves (8-15).  Both meet at the
@@ -307,21 +361,7 @@ __device__ __forceinline__ void tile_loop(const FusedArgs& a, unsigned char* sme
                 *reinterpret_cast<bf16x8*>(Gs + off) = v;
             }
         }
-        if constexpr (XN) {
-            // xhat = x * rstd - mean * rstd in place over the X tile (pixels of an overhanging tile stay 0)
-            constexpr int NXCH = NCORE * XCPP;
-            static_assert(NXCH <= 1024, "one chunk per thread");
-            if (tid < NXCH) {
-                const int pix = tid / XCPP, k = tid % XCPP;
-                if (oh0 + (pix >> 5) < a.H && ow0 + (pix & 31) < a.W) {
-                    unsigned char* px = Xt + XT::chunk(pix, pix & 31, k);
-                    bf16x8 v = *reinterpret_cast<const bf16x8*>(px);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (bf16)fmaf((float)v[e], cst[k * 8 + e], cst[32 + k * 8 + e]);
-                    *reinterpret_cast<bf16x8*>(px) = v;
-                }
-            }
-        }
+        if constexpr (XN) xhat_pass<CI>(Xt, cst, tid, oh0, ow0, a.H, a.W);
         if constexpr (APPLY || XN) __syncthreads();
 
         if constexpr (DG) {
@@ -350,7 +390,6 @@ __device__ __forceinline__ void tile_loop(const FusedArgs& a, unsigned char* sme
             const unsigned char* xrow = Xt + 8 * h;
 #pragma unroll
             for (int g4 = 0; g4 < XCPP; ++g4) {
-                typedef __attribute__((ext_vector_type(4))) bf16 B4;
                 typedef __attribute__((ext_vector_type(4))) short S4;
                 B4 o;
 #pragma unroll
@@ -365,11 +404,7 @@ __device__ __forceinline__ void tile_loop(const FusedArgs& a, unsigned char* sme
                 }
                 // (asm: the store must be ONE instruction per run whatever the compiler thinks of the addresses -- the waits count them)
                 asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(drow + dstep * g4), "v"(o) : "memory");
-                if constexpr (XN) {      // InstanceNorm-backward sums over the stored values (conv3x3_mfma.h stat_mode 2)
-                    const B4 xh = *reinterpret_cast<const B4*>(xrow + XT::chunk(wave * TW + frow, frow, g4));
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float f = inside ? (float)o[e] : 0.f; ssum[4 * g4 + e] += f; ssq[4 * g4 + e] += f * (float)xh[e]; }
-                }
+                if constexpr (XN) stat_accumulate<CI>(o, xrow, wave, frow, g4, inside, ssum, ssq);      // InstanceNorm-backward sums over the stored values
             }
         }
         if constexpr (WG) {
@@ -402,32 +437,7 @@ __device__ __forceinline__ void tile_loop(const FusedArgs& a, unsigned char* sme
     }
 
     dma_drain();        // the trailing dummy DMA must not outlive the workgroup's LDS
-    if constexpr (XN) {
-        // DETERMINISTIC reduction of the sums (conv3x3_mfma.h's protocol: fixed-order fp64 sum of the block's partials, plain store into
-        // the block's own slot stat_ws[b][blockIdx.x][CI][2]; slots no block owns are zeroed by block 0)
-        float* red = reinterpret_cast<float*>(smem);          // [2][CI][256]: the ring is dead
-        __syncthreads();
-        if constexpr (DG) {
-            const int j = wave * 32 + frow;
-#pragma unroll
-            for (int g4 = 0; g4 < XCPP; ++g4)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int c = 8 * g4 + 4 * h + e;
-                    red[c * 256 + j] = ssum[4 * g4 + e];
-                    red[(CI + c) * 256 + j] = ssq[4 * g4 + e];
-                }
-        }
-        __syncthreads();
-        if (DG && tid < 2 * CI) {
-            const int k = tid / CI, c = tid - k * CI;
-            double acc2 = 0.0;
-            for (int j = 0; j < 256; ++j) acc2 += (double)red[(k * CI + c) * 256 + j];
-            a.stat_ws[(((long)b * a.stat_slots + blockIdx.x) * CI + c) * 2 + k] = acc2;
-            if (blockIdx.x == 0)
-                for (int sl = gridDim.x; sl < a.stat_slots; ++sl) a.stat_ws[(((long)b * a.stat_slots + sl) * CI + c) * 2 + k] = 0.0;
-        }
-    }
+    if constexpr (XN) stat_reduce<CI, DG>(smem, ssum, ssq, tid, wave, frow, h, b, a.stat_ws, a.stat_slots);
     if constexpr (WG) {
         // ---- the workgroup's weight-gradient sums: one atomic per element (tap 8 and the bias arrive in four quarters)
 #pragma unroll
@@ -492,6 +502,17 @@ __global__ __launch_bounds__(1024) void conv_bwd_fused_kernel(FusedArgs a) {
     else tile_loop<CO, CI, APPLY, XN, NSLOT, false>(a, smem, cst);
 }
 
+// Blocks per image: one workgroup per CU, split evenly over the images; never more than the image has tiles nor (with_stats: every block
+// of an image owns one slot of the statistics workspace) than a.stat_slots
+unsigned fused_grid_x(const FusedArgs& a, bool with_stats) {
+    const long tiles_per_img = (long)a.tiles_w * a.tiles_h;
+    long gx = (OMR_NUM_CU + a.B - 1) / a.B;
+    if (gx > tiles_per_img) gx = tiles_per_img;
+    if (with_stats && gx > a.stat_slots) gx = a.stat_slots;
+    if (gx < 1) gx = 1;
+    return (unsigned)gx;
+}
+
 template <int CO, int CI, bool APPLY, bool XN, int NSLOT> int launch(FusedArgs a, hipStream_t s) {
     typedef Lds<CO, CI, APPLY, NSLOT> L;
     static_assert(L::TOTAL <= 160 * 1024, "LDS ring does not fit");
@@ -504,12 +525,7 @@ template <int CO, int CI, bool APPLY, bool XN, int NSLOT> int launch(FusedArgs a
     auto kern = conv_bwd_fused_kernel<CO, CI, APPLY, XN, NSLOT>;
     static std::atomic<int> ready{0};
     if (!omr_launch_setup(ready, (const void*)kern, L::TOTAL, true)) return OMR_ERR_LAUNCH;
-    const long tiles_per_img = (long)a.tiles_w * a.tiles_h;
-    long gx = (OMR_NUM_CU + a.B - 1) / a.B;                  // one workgroup per CU, split evenly over the images
-    if (gx > tiles_per_img) gx = tiles_per_img;
-    if (XN && gx > a.stat_slots) gx = a.stat_slots;          // one workspace slot per block of an image
-    if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, 1, a.B), dim3(1024), L::TOTAL, s, a);
+    hipLaunchKernelGGL(kern, dim3(fused_grid_x(a, XN), 1, a.B), dim3(1024), L::TOTAL, s, a);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }
@@ -653,16 +669,7 @@ __device__ __forceinline__ void tile_loop_s2(const FusedArgs& a, unsigned char* 
         __syncthreads();
         issue(ith, itw, (cur + NSLOT - 1) & (NSLOT - 1));
         advance(ith, itw);
-        {   // xhat = x * rstd - mean * rstd in place (one 16-byte chunk per thread; pixels of an overhanging tile stay 0)
-            const int pix = tid >> 2, k = tid & 3;
-            if (oh0 + (pix >> 5) < a.H && ow0 + (pix & 31) < a.W) {
-                unsigned char* px = Xt + T32::chunk(pix, pix & 31, k);
-                bf16x8 v = *reinterpret_cast<const bf16x8*>(px);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (bf16)fmaf((float)v[e], cst[k * 8 + e], cst[32 + k * 8 + e]);
-                *reinterpret_cast<bf16x8*>(px) = v;
-            }
-        }
+        xhat_pass<32>(Xt, cst, tid, oh0, ow0, a.H, a.W);
         __syncthreads();
 
         if constexpr (DG) {
@@ -694,14 +701,11 @@ __device__ __forceinline__ void tile_loop_s2(const FusedArgs& a, unsigned char* 
             const unsigned char* xrow = Xt + 8 * h;
 #pragma unroll
             for (int g4 = 0; g4 < XCPP; ++g4) {
-                typedef __attribute__((ext_vector_type(4))) bf16 B4;
                 B4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = (bf16)acc[4 * g4 + e];
                 asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(drow + dstep * g4), "v"(o) : "memory");
-                const B4 xh = *reinterpret_cast<const B4*>(xrow + T32::chunk(wave * TW + frow, frow, g4));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const float f = inside ? (float)o[e] : 0.f; ssum[4 * g4 + e] += f; ssq[4 * g4 + e] += f * (float)xh[e]; }
+                stat_accumulate<32>(o, xrow, wave, frow, g4, inside, ssum, ssq);
             }
         }
         if constexpr (WG) {
@@ -730,30 +734,7 @@ __device__ __forceinline__ void tile_loop_s2(const FusedArgs& a, unsigned char* 
         }
     }
     dma_drain();
-    {   // deterministic reduction of the InstanceNorm-backward sums (see the stride-1 XN mode)
-        float* red = reinterpret_cast<float*>(smem);          // [2][32][256]
-        __syncthreads();
-        if constexpr (DG) {
-            const int j = wave * 32 + frow;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int c = 8 * g4 + 4 * h + e;
-                    red[c * 256 + j] = ssum[4 * g4 + e];
-                    red[(32 + c) * 256 + j] = ssq[4 * g4 + e];
-                }
-        }
-        __syncthreads();
-        if (DG && tid < 64) {
-            const int k = tid >> 5, c = tid & 31;
-            double acc2 = 0.0;
-            for (int j = 0; j < 256; ++j) acc2 += (double)red[(k * 32 + c) * 256 + j];
-            a.stat_ws[(((long)b * a.stat_slots + blockIdx.x) * 32 + c) * 2 + k] = acc2;
-            if (blockIdx.x == 0)
-                for (int sl = gridDim.x; sl < a.stat_slots; ++sl) a.stat_ws[(((long)b * a.stat_slots + sl) * 32 + c) * 2 + k] = 0.0;
-        }
-    }
+    stat_reduce<32, DG>(smem, ssum, ssq, tid, wave, frow, h, b, a.stat_ws, a.stat_slots);
     if constexpr (WG) {
         const int tapw = third_bias ? -1 : 8;
 #pragma unroll
@@ -815,7 +796,7 @@ extern "C" int omr_conv3x3_bwd_fused(const void* g, const void* x, const void* w
         if (!norm_mean || !norm_rstd || !norm_workspace || norm_slots < 1) return OMR_ERR_ARG;
         if (!relu_mask) return OMR_ERR_UNSUPPORTED;       // the in-LDS pass relies on (Y > 0) to keep out-of-image pixels zero
         a.ny = (const bf16*)norm_y; a.mean = norm_mean; a.rstd = norm_rstd;
-        a.sums = (const double*)norm_workspace + (long)B * norm_slots * COUT * 2;      // the compact [B][COUT][2] sums behind the slots
+        a.sums = (const double*)norm_workspace + slot_compact_offset(B, norm_slots, COUT);      // the compact [B][COUT][2] sums behind the slots
         a.inv_hw = (float)(1.0 / ((double)H * W)); a.relu_scale = relu_scale;
         return pick<true>(a, COUT, CIN, (hipStream_t)stream);
     }
@@ -841,12 +822,7 @@ extern "C" int omr_conv3x3_bwd_fused_s2(const void* g, const void* x, const void
     a.tiles_w = cdiv(W, TW); a.tiles_h = cdiv(H, TH);
     static std::atomic<int> ready{0};
     if (!omr_launch_setup(ready, (const void*)conv_bwd_fused_s2_kernel, S2::TOTAL, true)) return OMR_ERR_LAUNCH;
-    const long tiles_per_img = (long)a.tiles_w * a.tiles_h;
-    long gx = (OMR_NUM_CU + B - 1) / B;
-    if (gx > tiles_per_img) gx = tiles_per_img;
-    if (gx > stat_slots) gx = stat_slots;
-    if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(conv_bwd_fused_s2_kernel, dim3((unsigned)gx, 1, B), dim3(1024), S2::TOTAL, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(conv_bwd_fused_s2_kernel, dim3(fused_grid_x(a, true), 1, B), dim3(1024), S2::TOTAL, (hipStream_t)stream, a);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }

@@ -1,151 +1,11 @@
 // Normalisation kernels (gfx950), all statistics in fp32/fp64:
-//   InstanceNorm2d(eps=1e-3, affine=False, no running stats) on NHWC maps  -- encoder.py:151-156,210-215
+//   InstanceNorm2d(eps=1e-3, affine=False, no running stats) on NHWC maps  -- encoder.py:151-156,210-215 (kernels: instnorm_slots.h)
 //   residual + LayerNorm(eps=1e-5) of the post-norm decoder layer          -- torch nn/modules/transformer.py:1146-1154
 #include "omr_common.h"
 #include "omr_hip.h"
+#include "instnorm_slots.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------
-// InstanceNorm statistics over x[B][HW][C] (NHWC): per (b, c) mean and 1/sqrt(biased var + eps).
-// DETERMINISTIC two-stage reduction (no atomics): stage 1 -- each block reduces a slab of pixels for all channels (per-thread
-// fp32 partials over a short run, combined over the block's threads in a fixed order in fp64) and stores the result into
-// its own slot ws[b][slot][c][2] = (sum, sum of squares); stage 2 adds an image's slots in index order and finalises.
-// The same slot layout is written by the conv kernels' fused statistics epilogue (conv3x3_mfma.h).
-// The apply is fused into the consumer's tile load (conv3 / depthwise conv3), never materialised.
-// Thread t owns channel group (t % (C/VEC)) and walks pixels with 16-byte loads (fully coalesced: NHWC rows are contiguous).
-template <typename T, bool BWD>
-__global__ __launch_bounds__(256) void instnorm_partial_kernel(const T* __restrict__ x, const T* __restrict__ g, const float* __restrict__ mean,
-                                                               const float* __restrict__ rstd, double* __restrict__ ws, long HW, int C,
-                                                               int pix_per_block) {
-    typedef typename Frag<T>::type F;
-    constexpr int VEC = Frag<T>::N;
-    extern __shared__ __attribute__((aligned(16))) float red[];   // [nphase][C][2]
-    const int b = blockIdx.y;
-    const int ncg = C / VEC;                       // channel groups; divides blockDim for the encoder's widths
-    const int cg = threadIdx.x % ncg, phase = threadIdx.x / ncg, nphase = blockDim.x / ncg;
-    const long p0 = (long)blockIdx.x * pix_per_block;
-    const long p1 = p0 + pix_per_block < HW ? p0 + pix_per_block : HW;
-    const long base = (long)b * HW * C;
-    float s[VEC], q[VEC], mu[VEC], rs[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        s[e] = q[e] = 0.f;
-        mu[e] = BWD ? mean[(long)b * C + cg * VEC + e] : 0.f;
-        rs[e] = BWD ? rstd[(long)b * C + cg * VEC + e] : 1.f;
-    }
-    for (long p = p0 + phase; p < p1; p += nphase) {
-        const F xv = *reinterpret_cast<const F*>(x + base + p * C + cg * VEC);
-        if (BWD) {
-            const F gv = *reinterpret_cast<const F*>(g + base + p * C + cg * VEC);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const float gg = to_f32(gv[e]);
-                s[e] += gg;
-                q[e] += gg * ((to_f32(xv[e]) - mu[e]) * rs[e]);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const float v = to_f32(xv[e]);
-                s[e] += v;
-                q[e] += v * v;
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        red[(phase * C + cg * VEC + e) * 2 + 0] = s[e];
-        red[(phase * C + cg * VEC + e) * 2 + 1] = q[e];
-    }
-    __syncthreads();
-    double* out = ws + ((long)b * gridDim.x + blockIdx.x) * C * 2;
-    for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-        double acc = 0.0;
-        for (int ph = 0; ph < nphase; ++ph) acc += (double)red[ph * 2 * C + i];
-        out[i] = acc;
-    }
-}
-// Stage 2.  One workgroup per image: value v = (channel, {sum | sum of squares}) of slot k lives at ws[b][k][v]; the 256 threads
-// are dealt out as (v, part) so that `parts` threads share a value, each adding the slots k = part, part + parts, ... in that
-// order, and the partial sums are then added in part order -- fixed order, no atomics, and no thread walks more than
-// slots / parts slots (a single thread per value was a 20-27 us latency chain per launch).
-// FINAL: mean / rstd; else: the compact sums [b][C][2] that the backward apply kernel reads.
-template <bool FINAL>
-__global__ __launch_bounds__(256) void instnorm_reduce_slots_kernel(const double* __restrict__ ws, int slots, int C, float* __restrict__ mean,
-                                                                    float* __restrict__ rstd, double* __restrict__ compact, double inv_hw, float eps) {
-    __shared__ double red[512];
-    const int b = blockIdx.x, NV = 2 * C, tid = threadIdx.x;
-    const double* base = ws + (long)b * slots * NV;
-    for (int v0 = 0; v0 < NV; v0 += 256) {                       // NV <= 256 in one round (C <= 128), two rounds for C = 256
-        const int nv = NV - v0 < 256 ? NV - v0 : 256;            // values of this round (a power of two for the encoder's widths)
-        const int parts = 256 / nv > 0 ? 256 / nv : 1;
-        const int v = tid % nv, part = tid / nv;
-        double acc = 0.0;
-        if (part < parts)
-            for (int k = part; k < slots; k += parts) acc += base[(long)k * NV + v0 + v];
-        __syncthreads();
-        if (part < parts) red[part * nv + v] = acc;
-        __syncthreads();
-        if (tid < nv) {
-            double s = 0.0;
-            for (int q = 0; q < parts; ++q) s += red[q * nv + tid];
-            red[256 + tid] = s;
-        }
-        __syncthreads();
-        if (FINAL) {
-            if (tid < nv / 2) {                                   // channel c = (v0 + 2 tid) / 2
-                const double m = red[256 + 2 * tid] * inv_hw;
-                double var = red[256 + 2 * tid + 1] * inv_hw - m * m;
-                if (var < 0) var = 0;
-                const long o = (long)b * C + v0 / 2 + tid;
-                mean[o] = (float)m;
-                rstd[o] = (float)(1.0 / sqrt(var + (double)eps));
-            }
-        } else if (tid < nv) {
-            compact[(long)b * NV + v0 + tid] = red[256 + tid];
-        }
-    }
-}
-
-// InstanceNorm backward.  With xhat = (x - mean) * rstd and g = dL/dxhat:
-//   dx = rstd * (g - mean_hw(g) - xhat * mean_hw(g * xhat))
-// Stage 1 accumulates sum(g), sum(g*xhat) per (b,c) in fp64; stage 2 applies, and optionally folds
-// in the ReLU(+dropout) backward of the producer of x: dx *= (x > 0) * relu_scale.
-// Apply: thread owns one channel group (statistics loaded once into registers) and walks its pixels: no index divisions.
-template <typename T>
-__global__ __launch_bounds__(256) void instnorm_bwd_apply_kernel(const T* __restrict__ g, const T* __restrict__ x, const float* __restrict__ mean,
-                                                                 const float* __restrict__ rstd, const double* __restrict__ ws, T* __restrict__ dx, long HW,
-                                                                 int C, int pix_per_block, float inv_hw, int relu_mask, float relu_scale) {
-    typedef typename Frag<T>::type F;
-    constexpr int VEC = Frag<T>::N;
-    const int b = blockIdx.y;
-    const int ncg = C / VEC;
-    const int cg = threadIdx.x % ncg, phase = threadIdx.x / ncg, nphase = blockDim.x / ncg;
-    float mu[VEC], rs[VEC], s1[VEC], s2[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        const long bc = (long)b * C + cg * VEC + e;
-        mu[e] = mean[bc]; rs[e] = rstd[bc];
-        s1[e] = (float)(ws[2 * bc] * (double)inv_hw); s2[e] = (float)(ws[2 * bc + 1] * (double)inv_hw);
-    }
-    const long p0 = (long)blockIdx.x * pix_per_block;
-    const long p1 = p0 + pix_per_block < HW ? p0 + pix_per_block : HW;
-    const long base = (long)b * HW * C + cg * VEC;
-#pragma unroll 4
-    for (long p = p0 + phase; p < p1; p += nphase) {
-        const F gv = *reinterpret_cast<const F*>(g + base + p * C), xv = *reinterpret_cast<const F*>(x + base + p * C);
-        F o;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const float xf = to_f32(xv[e]);
-            float d = rs[e] * (to_f32(gv[e]) - s1[e] - (xf - mu[e]) * rs[e] * s2[e]);
-            if (relu_mask) d = xf > 0.f ? d * relu_scale : 0.f;
-            o[e] = from_f32<T>(d);
-        }
-        *reinterpret_cast<F*>(dx + base + p * C) = o;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // out = LayerNorm(dropout(x) + res) * gamma + beta.  One wave per row; lane l owns the PER = d/64 CONSECUTIVE elements
@@ -274,31 +134,52 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(const T* __restrict__ d
 
 }  // namespace
 
-// Pixels per workgroup of the statistics passes: 2048 on the big maps, fewer on the small DSC maps so that at least ~1000
-// workgroups are in flight (16 x 256 maps with 2048 pixels per workgroup left 3/4 of the CUs idle).
-static int stat_pixels_per_block(long HW, int B) {
-    long ppb = 2048;
-    while (ppb > 64 && cdiv(HW, ppb) * (long)B < 1024) ppb /= 2;
-    return (int)ppb;
+// ------------------------------------------------------------------------------------------------
+// InstanceNorm on dense maps x[B][HW][C] (NHWC): launchers over the slot protocol of instnorm_slots.h.  16-byte accesses only
+// (VEC = Frag<T>::N, C / VEC a divisor of 256).  The forward apply is fused into the consumer's tile load (conv3 / depthwise conv3), never
+// materialised.  Backward, with xhat = (x - mean) * rstd and g = dL/dxhat:  dx = rstd * (g - mean_hw(g) - xhat * mean_hw(g * xhat)),
+// optionally times the ReLU(+dropout) backward of the producer of x: (x > 0) * relu_scale.
+static bool dense_width_ok(int dtype, int C) {
+    const int vec = dtype == OMR_BF16 ? 8 : 4;
+    return C % vec == 0 && 256 % (C / vec) == 0;
 }
-static size_t partial_lds_bytes(int dtype) { return (size_t)256 * (dtype == OMR_BF16 ? 8 : 4) * 2 * sizeof(float); }   // [nphase][C][2] with nphase * C/VEC = 256
+// stage 1 over the whole map; returns the slots per image it filled
+template <bool BWD>
+static int launch_partial(int dtype, const void* x, const void* g, const float* mean, const float* rstd, double* ws, int B, long HW, int C, hipStream_t s) {
+    const int ppb = instnorm_pixels_per_block(HW, B), slots = cdiv(HW, ppb);
+    DISPATCH_T(dtype, hipLaunchKernelGGL((instnorm_partial_kernel<T, Frag<T>::N, BWD, false>), dim3(slots, B), 256, instnorm_partial_lds_bytes(C, Frag<T>::N), s,
+                                         (const T*)x, (const T*)g, mean, rstd, (const int*)nullptr, ws, 0, 0, HW, C, ppb));
+    return slots;
+}
+// stage 2: mean / rstd (FINAL) or the compact sums behind the slots
+template <bool FINAL>
+static void launch_reduce(double* ws, int slots, int B, long HW, int C, float* mean, float* rstd, float eps, hipStream_t s) {
+    hipLaunchKernelGGL((instnorm_reduce_slots_kernel<FINAL>), B, 256, 0, s, (const double*)ws, (const int*)nullptr, slots, 0, 0, C, mean, rstd,
+                       FINAL ? (double*)nullptr : ws + slot_compact_offset(B, slots, C), FINAL ? 1.0 / (double)HW : 0.0, eps);
+}
+static int launch_bwd_apply(int dtype, const void* dxhat, const void* x, const float* mean, const float* rstd, void* dx, int B, long HW, int C,
+                            int relu_mask, float relu_scale, double* ws, int slots, hipStream_t s) {
+    launch_reduce<false>(ws, slots, B, HW, C, nullptr, nullptr, 0.f, s);
+    const int ppb2 = 1024;
+    DISPATCH_T(dtype, hipLaunchKernelGGL((instnorm_apply_kernel<T, Frag<T>::N, true, false>), dim3(cdiv(HW, ppb2), B), 256, 0, s, (const T*)x, (const T*)dxhat, mean,
+                                         rstd, (const double*)(ws + slot_compact_offset(B, slots, C)), (const int*)nullptr, (T*)dx, 0, 0, HW, C, ppb2,
+                                         (float)(1.0 / (double)HW), relu_mask, relu_scale));
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
 
 /* slots per image of the stand-alone statistics passes (omr_instnorm_stats / omr_instnorm_bwd) */
-extern "C" int omr_instnorm_slots(int B, long HW) { return (B <= 0 || HW <= 0) ? OMR_ERR_ARG : cdiv(HW, stat_pixels_per_block(HW, B)); }
+extern "C" int omr_instnorm_slots(int B, long HW) { return (B <= 0 || HW <= 0) ? OMR_ERR_ARG : cdiv(HW, instnorm_pixels_per_block(HW, B)); }
 /* bytes of a statistics workspace with `slots` slots per image: partials [B][slots][C][2] + compact sums [B][C][2], fp64 */
-extern "C" long omr_instnorm_workspace_bytes(int B, int C, int slots) { return ((long)B * slots * C * 2 + (long)B * C * 2) * sizeof(double); }
+extern "C" long omr_instnorm_workspace_bytes(int B, int C, int slots) { return slot_workspace_bytes(B, C, slots); }
 
 extern "C" int omr_instnorm_stats(int dtype, const void* x, float* mean, float* rstd, int B, long HW, int C, float eps, void* workspace,
                                   void* stream) {
     if (B <= 0 || HW <= 0 || C <= 0 || !workspace) return OMR_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int vec = dtype == OMR_BF16 ? 8 : 4;
-    if (C % vec || 256 % (C / vec)) return OMR_ERR_UNSUPPORTED;
-    int ppb = stat_pixels_per_block(HW, B);
-    dim3 grid(cdiv(HW, ppb), B);
-    DISPATCH_T(dtype, hipLaunchKernelGGL((instnorm_partial_kernel<T, false>), grid, 256, partial_lds_bytes(dtype), s, (const T*)x, (const T*)nullptr,
-                                         (const float*)nullptr, (const float*)nullptr, (double*)workspace, HW, C, ppb));
-    hipLaunchKernelGGL((instnorm_reduce_slots_kernel<true>), B, 256, 0, s, (const double*)workspace, (int)grid.x, C, mean, rstd, (double*)nullptr, 1.0 / (double)HW, eps);
+    if (!dense_width_ok(dtype, C)) return OMR_ERR_UNSUPPORTED;
+    const int slots = launch_partial<false>(dtype, x, nullptr, nullptr, nullptr, (double*)workspace, B, HW, C, (hipStream_t)stream);
+    if (slots < 0) return slots;
+    launch_reduce<true>((double*)workspace, slots, B, HW, C, mean, rstd, eps, (hipStream_t)stream);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }
@@ -306,7 +187,7 @@ extern "C" int omr_instnorm_stats(int dtype, const void* x, float* mean, float* 
 /* mean / rstd from the fp64 {sum, sum of squares} slots that a producer kernel filled (omr_conv3x3_fwd stat_mode 1) */
 extern "C" int omr_instnorm_finalize(const void* workspace, int slots, float* mean, float* rstd, int B, long HW, int C, float eps, void* stream) {
     if (B <= 0 || HW <= 0 || C <= 0 || slots < 1 || !workspace) return OMR_ERR_ARG;
-    hipLaunchKernelGGL((instnorm_reduce_slots_kernel<true>), B, 256, 0, (hipStream_t)stream, (const double*)workspace, slots, C, mean, rstd, (double*)nullptr, 1.0 / (double)HW, eps);
+    launch_reduce<true>((double*)workspace, slots, B, HW, C, mean, rstd, eps, (hipStream_t)stream);      // FINAL reads the workspace only
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }
@@ -315,21 +196,7 @@ extern "C" int omr_instnorm_finalize(const void* workspace, int slots, float* me
  * compact region [B][C][2] behind them: what omr_conv3x3_fwd stat_mode 5 (and omr_instnorm_bwd_apply) read */
 extern "C" int omr_instnorm_reduce_sums(void* workspace, int slots, int B, int C, void* stream) {
     if (B <= 0 || C <= 0 || slots < 1 || !workspace) return OMR_ERR_ARG;
-    double* ws = (double*)workspace;
-    hipLaunchKernelGGL((instnorm_reduce_slots_kernel<false>), B, 256, 0, (hipStream_t)stream, (const double*)ws, slots, C, (float*)nullptr, (float*)nullptr,
-                       ws + (long)B * slots * C * 2, 0.0, 0.f);
-    OMR_CHECK_LAUNCH();
-    return OMR_OK;
-}
-
-static int launch_bwd_apply(int dtype, const void* dxhat, const void* x, const float* mean, const float* rstd, void* dx, int B, long HW, int C,
-                            int relu_mask, float relu_scale, double* ws, int slots, hipStream_t s) {
-    double* compact = ws + (long)B * slots * C * 2;
-    hipLaunchKernelGGL((instnorm_reduce_slots_kernel<false>), B, 256, 0, s, (const double*)ws, slots, C, (float*)nullptr, (float*)nullptr, compact, 0.0, 0.f);
-    int ppb2 = 1024;
-    dim3 grid2(cdiv(HW, ppb2), B);
-    DISPATCH_T(dtype, hipLaunchKernelGGL((instnorm_bwd_apply_kernel<T>), grid2, 256, 0, s, (const T*)dxhat, (const T*)x, mean, rstd,
-                                         (const double*)compact, (T*)dx, HW, C, ppb2, (float)(1.0 / (double)HW), relu_mask, relu_scale));
+    launch_reduce<false>((double*)workspace, slots, B, 0, C, nullptr, nullptr, 0.f, (hipStream_t)stream);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }
@@ -339,22 +206,17 @@ static int launch_bwd_apply(int dtype, const void* dxhat, const void* x, const f
 extern "C" int omr_instnorm_bwd_apply(int dtype, const void* dxhat, const void* x, const float* mean, const float* rstd, void* dx, int B, long HW,
                                       int C, int relu_mask, float relu_scale, void* workspace, int slots, void* stream) {
     if (B <= 0 || HW <= 0 || C <= 0 || slots < 1 || !workspace) return OMR_ERR_ARG;
-    const int vec = dtype == OMR_BF16 ? 8 : 4;
-    if (C % vec || 256 % (C / vec)) return OMR_ERR_UNSUPPORTED;
+    if (!dense_width_ok(dtype, C)) return OMR_ERR_UNSUPPORTED;
     return launch_bwd_apply(dtype, dxhat, x, mean, rstd, dx, B, HW, C, relu_mask, relu_scale, (double*)workspace, slots, (hipStream_t)stream);
 }
 
 extern "C" int omr_instnorm_bwd(int dtype, const void* dxhat, const void* x, const float* mean, const float* rstd, void* dx, int B, long HW,
                                 int C, int relu_mask, float relu_scale, void* workspace, void* stream) {
     if (B <= 0 || HW <= 0 || C <= 0 || !workspace) return OMR_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int vec = dtype == OMR_BF16 ? 8 : 4;
-    if (C % vec || 256 % (C / vec)) return OMR_ERR_UNSUPPORTED;
-    int ppb = stat_pixels_per_block(HW, B);
-    dim3 grid(cdiv(HW, ppb), B);
-    DISPATCH_T(dtype, hipLaunchKernelGGL((instnorm_partial_kernel<T, true>), grid, 256, partial_lds_bytes(dtype), s, (const T*)x, (const T*)dxhat, mean, rstd,
-                                         (double*)workspace, HW, C, ppb));
-    return launch_bwd_apply(dtype, dxhat, x, mean, rstd, dx, B, HW, C, relu_mask, relu_scale, (double*)workspace, (int)grid.x, s);
+    if (!dense_width_ok(dtype, C)) return OMR_ERR_UNSUPPORTED;
+    const int slots = launch_partial<true>(dtype, x, dxhat, mean, rstd, (double*)workspace, B, HW, C, (hipStream_t)stream);
+    if (slots < 0) return slots;
+    return launch_bwd_apply(dtype, dxhat, x, mean, rstd, dx, B, HW, C, relu_mask, relu_scale, (double*)workspace, slots, (hipStream_t)stream);
 }
 
 #define LN_DISPATCH_PER(KERNEL, ...)                                                                       \

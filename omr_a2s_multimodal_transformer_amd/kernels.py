@@ -407,16 +407,23 @@ def topk_logprob(x: Tensor, k: int) -> Tuple[Tensor, Tensor]:
 
 # ------------------------------------------------------------------------------------------------ normalisation
 
-def _stat_ws(B: int, C: int, slots: int, device, zero: bool) -> Tensor:
-    """fp64 statistics workspace: partial slots [B][slots][C][2] + compact sums [B][C][2] (include/omr_hip.h, normalisation)."""
-    n = lib().query("omr_instnorm_workspace_bytes", B, C, slots) // 8
-    return (torch.zeros if zero else torch.empty)(n, dtype=torch.float64, device=device)
+def slot_workspace(slot_query: str, B: int, C: int, device, *dims: int) -> Tuple[Tensor, int]:
+    """(fp64 statistics workspace, slots per image) of the InstanceNorm slot protocol: partial slots [B][slots][C][2] +
+    compact sums [B][C][2].  The library owns both numbers: slots = slot_query(B, *dims) (a value < 1 is its error code), the size is
+    omr_instnorm_workspace_bytes.  Uninitialised: the producer launch writes every slot."""
+    slots = lib().query(slot_query, B, *dims)
+    assert slots >= 1, f"{slot_query}{(B,) + dims} failed: {slots}"
+    return torch.empty(slot_workspace_elems(B, C, slots), dtype=torch.float64, device=device), slots
+
+
+def slot_workspace_elems(B: int, C: int, slots: int) -> int:
+    """fp64 elements of a statistics workspace with `slots` slots per image (compact sums included)."""
+    return lib().query("omr_instnorm_workspace_bytes", B, C, slots) // 8
 
 
 def conv_stat_ws(B: int, Ho: int, Wo: int, C: int, device) -> Tuple[Tensor, int]:
-    """Workspace + slot count for a conv launch with a fused statistics epilogue (stat_mode 1 / 2); the launch writes every slot."""
-    slots = lib().query("omr_conv3x3_stat_slots", B, Ho, Wo)
-    return _stat_ws(B, C, slots, device, False), slots
+    """Workspace + slot count for a conv launch with a fused statistics epilogue (stat_mode 1 / 2)."""
+    return slot_workspace("omr_conv3x3_stat_slots", B, C, device, Ho, Wo)
 
 
 def instnorm_stats(x: Tensor, eps: float = 1e-3) -> Tuple[Tensor, Tensor]:
@@ -426,7 +433,7 @@ def instnorm_stats(x: Tensor, eps: float = 1e-3) -> Tuple[Tensor, Tensor]:
     assert x.is_contiguous()
     mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
-    ws = _stat_ws(B, C, lib().query("omr_instnorm_slots", B, H * W), x.device, False)
+    ws, _ = slot_workspace("omr_instnorm_slots", B, C, x.device, H * W)
     lib().call("omr_instnorm_stats", dtype_code(x.dtype), ptr(x), ptr(mean), ptr(rstd), B, H * W, C, eps, ptr(ws), cur_stream())
     return mean, rstd
 
@@ -456,7 +463,7 @@ def instnorm_bwd(dxhat: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, relu_mask
     B, H, W, C = x.shape
     assert dxhat.shape == x.shape and dxhat.is_contiguous() and x.is_contiguous()
     dx = torch.empty_like(x)
-    ws = _stat_ws(B, C, lib().query("omr_instnorm_slots", B, H * W), x.device, False)
+    ws, _ = slot_workspace("omr_instnorm_slots", B, C, x.device, H * W)
     lib().call("omr_instnorm_bwd", dtype_code(x.dtype), ptr(dxhat), ptr(x), ptr(mean), ptr(rstd), ptr(dx), B, H * W, C, int(relu_mask),
                float(relu_scale), ptr(ws), cur_stream())
     return dx
@@ -473,13 +480,6 @@ def _check_extents(x: Tensor, ext: Tensor) -> Tuple[int, int, int, int]:
     return tuple(x.shape)
 
 
-def _extent_stat_ws(B: int, H: int, W: int, C: int, device) -> Tensor:
-    """Workspace of the extent statistics passes (slots per sample from the library; a negative value is its error code)."""
-    slots = lib().query("omr_instnorm_extent_slots", B, H * W)
-    assert slots > 0, f"omr_instnorm_extent_slots({B}, {H * W}) failed: {slots}"
-    return _stat_ws(B, C, slots, device, False)
-
-
 def extent_zero(x: Tensor, ext: Tensor) -> Tensor:
     """x[b, i, j, :] = 0 for i >= ext[b, 0] or j >= ext[b, 1], IN PLACE (returns x).  Stores to the outside only."""
     B, H, W, C = _check_extents(x, ext)
@@ -493,7 +493,7 @@ def instnorm_extent_fwd(x: Tensor, ext: Tensor, eps: float = 1e-3) -> Tuple[Tens
     y = torch.empty_like(x)
     mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
-    ws = _extent_stat_ws(B, H, W, C, x.device)
+    ws, _ = slot_workspace("omr_instnorm_extent_slots", B, C, x.device, H * W)
     lib().call("omr_instnorm_extent_fwd", dtype_code(x.dtype), ptr(x), ptr(ext), ptr(y), ptr(mean), ptr(rstd), B, H, W, C, eps, ptr(ws), cur_stream())
     return y, mean, rstd
 
@@ -505,7 +505,7 @@ def instnorm_extent_bwd(dxhat: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, ex
     assert dxhat.shape == x.shape and dxhat.dtype == x.dtype and dxhat.is_contiguous()
     assert mean.dtype == rstd.dtype == torch.float32 and mean.numel() == rstd.numel() == B * C
     dx = torch.empty_like(x)
-    ws = _extent_stat_ws(B, H, W, C, x.device)
+    ws, _ = slot_workspace("omr_instnorm_extent_slots", B, C, x.device, H * W)
     lib().call("omr_instnorm_extent_bwd", dtype_code(x.dtype), ptr(dxhat), ptr(x), ptr(mean), ptr(rstd), ptr(ext), ptr(dx), B, H, W, C, int(relu_mask),
                float(relu_scale), ptr(ws), cur_stream())
     return dx
@@ -591,11 +591,10 @@ def conv3x3(x: Tensor, w_phys: Tensor, bias: Optional[Tensor], stride=(1, 1), re
     p, seed, chan = drop if drop is not None else (0.0, 0, False)
     smean = srstd = None
     if stat_mode:
-        assert stat_ws is not None and stat_ws.dtype == torch.float64 and stat_slots >= 1 and stat_ws.numel() >= B * stat_slots * COUT * 2
+        assert stat_ws is not None and stat_ws.dtype == torch.float64 and stat_slots >= 1 and stat_ws.numel() >= slot_workspace_elems(B, COUT, stat_slots)
     if stat_mode >= 2:
         smean, srstd = stat_stats
         assert stat_x is not None and tuple(stat_x.shape) == (B, Ho, Wo, COUT) and stat_x.is_contiguous() and tuple(smean.shape) == (B, COUT)
-        assert stat_ws.numel() >= B * stat_slots * COUT * 2 + B * COUT * 2
     lib().call("omr_conv3x3_fwd", dtype_code(x.dtype), ptr(x), ptr(w_phys), ptr(bias), ptr(y), ptr(mean), ptr(rstd), ptr(out_mask), float(mask_scale),
                B, H, W, CIN, COUT, stride[0], stride[1], dil[0], dil[1], Ho, Wo, int(relu), float(p), int(seed) & (2**64 - 1), int(chan),
                int(stat_mode), ptr(stat_ws), int(stat_slots), ptr(stat_x), ptr(smean), ptr(srstd), cur_stream())
