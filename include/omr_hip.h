@@ -145,7 +145,14 @@ int omr_add_layernorm_bwd(int dtype, const void* dy, const void* x, const void* 
  *   omr_instnorm_extent_bwd: dx = rstd * (g - sum g / n - xhat * sum(g * xhat) / n) [* (x > 0) * relu_scale] inside, 0 outside
  *     (omr_instnorm_bwd over the extent); same workspace.
  *   omr_pack_memory_fwd / _bwd: x.flatten(2).permute(0, 2, 1) of model.py:147 per sample: out[b][i * w_b + j][:] = x[b][i][j][:],
- *     rows h_b * w_b <= r < Smax of out[B][Smax][C] zero; the backward scatters dout back (zeros outside, rows >= h_b * w_b ignored). */
+ *     rows h_b * w_b <= r < Smax of out[B][Smax][C] zero; the backward scatters dout back (zeros outside, rows >= h_b * w_b ignored).
+ *   omr_concat_memory_fwd / _bwd: torch.cat([xi, xa], dim=1) of mixer_concat, model.py:644-675, per sample.  a [B][La][C] and
+ *     b [B][Lb][C] are packed memories, len_a / len_b int32 [B] ON THE DEVICE, la = clamp(len_a[b], 0, La), lb likewise:
+ *     out[b][r] = a[b][r] for r < la, b[b][r - la] for la <= r < la + lb, 0 for la + lb <= r < Smax (out [B][Smax][C]; rows the
+ *     concatenation has beyond Smax are dropped).  Backward: da[b][r] = dout[b][r] for r < la and r < Smax, db[b][r] = dout[b][la + r]
+ *     for r < lb and la + r < Smax, 0 elsewhere, both in one launch.  Tail-zeroing form: b (db) = NULL with Lb = 0 (len_b is not
+ *     read) copies the first la rows and zeroes the rest.  Rows of a / b at or past their length and rows of dout at or past
+ *     la + lb are never read.  La * C, Lb * C and Smax * C <= 2^31 - 1, else OMR_ERR_ARG; any C. */
 int omr_extent_zero(int dtype, void* x, const int* extents, int B, int H, int W, int C, void* stream);
 int omr_instnorm_extent_slots(int B, long HW);
 int omr_instnorm_extent_fwd(int dtype, const void* x, const int* extents, void* y, float* mean, float* rstd, int B, int H, int W, int C,
@@ -154,6 +161,10 @@ int omr_instnorm_extent_bwd(int dtype, const void* dxhat, const void* x, const f
                             int B, int H, int W, int C, int relu_mask, float relu_scale, void* workspace, void* stream);
 int omr_pack_memory_fwd(int dtype, const void* x, const int* extents, void* out, int B, int H, int W, int C, int Smax, void* stream);
 int omr_pack_memory_bwd(int dtype, const void* dout, const int* extents, void* dx, int B, int H, int W, int C, int Smax, void* stream);
+int omr_concat_memory_fwd(int dtype, const void* a, const int* len_a, int La, const void* b, const int* len_b, int Lb, void* out, int B, int C,
+                          int Smax, void* stream);
+int omr_concat_memory_bwd(int dtype, const void* dout, const int* len_a, int La, const int* len_b, int Lb, void* da, void* db, int B, int C,
+                          int Smax, void* stream);
 
 /* ---- GEMM: C[M,N] (+)= act(opA(A) . opB(B)^T + bias) ------------------------------------------------------ */
 /* aten::linear/addmm/mm of the decoder layers (torch nn/modules/transformer.py:1158-1199), 1x1 point_conv

@@ -5,6 +5,7 @@
 //   omr_extent_zero                  writes the zeros back after every conv (bias + ReLU made the outside non-zero); its own adjoint
 //   omr_instnorm_extent_fwd / _bwd   InstanceNorm2d(eps=1e-3, affine=False) with its sums over the extent only, count h_b * w_b
 //   omr_pack_memory_fwd / _bwd       [B][H'][W'][d] feature grid <-> [B][Smax][d] decoder memory, row i * w'_b + j = cell (i, j)
+//   omr_concat_memory_fwd / _bwd     two packed memories with per-sample lengths <-> their per-sample concatenation (multimodal mixers)
 // All memory-bound: 16-byte accesses where C is a multiple of the fragment width (else one element per access: the 1-channel input
 // image, odd widths), long offsets, statistics by the deterministic fp64 slot protocol of instnorm_slots.h (its EXTENT kernels; no
 // atomics).  One sample holds at
@@ -66,6 +67,50 @@ __global__ __launch_bounds__(256) void pack_memory_kernel(const T* __restrict__ 
             o = *reinterpret_cast<const P*>(sb + (long)(i * W + j) * C + c);
         }
         *reinterpret_cast<P*>(db + (long)t * VEC) = o;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Two packed memories a [B][La][C], b [B][Lb][C] with per-sample lengths la, lb -> one memory [B][Smax][C]: torch.cat([xi, xa], dim=1)
+// of each sample alone.  !BWD (src = a, src2 = b, dst = out): out[r] = a[r] for r < la, b[r - la] for la <= r < la + lb, 0 behind.
+// BWD (src = dout, dst = da, dst2 = db): da[r] = dout[r] for r < min(la, Smax), db[r] = dout[la + r] for r < lb and la + r < Smax, 0
+// elsewhere; da, then db, each walked linearly.  Lb = 0 (b / db null, len_b not read): copy the first la rows and zero the rest.  Rows
+// of a / b at or past their length and rows of dout at or past la + lb are not read.
+template <typename T, int VEC, bool BWD>
+__global__ __launch_bounds__(256) void concat_memory_kernel(const T* __restrict__ src, const T* __restrict__ src2, const int* __restrict__ len_a,
+                                                            const int* __restrict__ len_b, T* __restrict__ dst, T* __restrict__ dst2, int La, int Lb, int C,
+                                                            int Smax) {
+    typedef Pack<T, VEC> P;
+    const int b = blockIdx.y;
+    const unsigned cv = C / VEC;
+    const unsigned la = clampi(len_a[b], 0, La), lb = Lb > 0 ? clampi(len_b[b], 0, Lb) : 0;
+    const unsigned first = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+    const P z = pack_zero<T, VEC>();
+    if (!BWD) {
+        const T* ab = src + (long)b * La * C;
+        const T* bb = src2 + (long)b * Lb * C;       // not dereferenced when Lb = 0
+        T* ob = dst + (long)b * Smax * C;
+        for (unsigned t = first; t < (unsigned)Smax * cv; t += step) {
+            const unsigned r = t / cv, c = (t - r * cv) * VEC;
+            P o = z;
+            if (r < la) o = *reinterpret_cast<const P*>(ab + (long)r * C + c);
+            else if (r < la + lb) o = *reinterpret_cast<const P*>(bb + (long)(r - la) * C + c);
+            *reinterpret_cast<P*>(ob + (long)t * VEC) = o;
+        }
+    } else {
+        const T* gb = src + (long)b * Smax * C;
+        T* da = dst + (long)b * La * C;
+        T* db = dst2 + (long)b * Lb * C;
+        const unsigned na = la < (unsigned)Smax ? la : (unsigned)Smax;                 // rows of da that have a row of dout
+        const unsigned nb = la >= (unsigned)Smax ? 0u : (lb < Smax - la ? lb : Smax - la);   // rows of db that have one
+        for (unsigned t = first; t < (unsigned)La * cv; t += step) {
+            const unsigned r = t / cv;
+            *reinterpret_cast<P*>(da + (long)t * VEC) = r < na ? *reinterpret_cast<const P*>(gb + (long)t * VEC) : z;
+        }
+        for (unsigned t = first; t < (unsigned)Lb * cv; t += step) {
+            const unsigned r = t / cv;
+            *reinterpret_cast<P*>(db + (long)t * VEC) = r < nb ? *reinterpret_cast<const P*>(gb + (long)la * C + (long)t * VEC) : z;
+        }
     }
 }
 
@@ -150,6 +195,35 @@ extern "C" int omr_pack_memory_bwd(int dtype, const void* dout, const int* exten
     const int vec = extent_vec(dtype, C, dout, dx);
     DISPATCH_T_VEC(dtype, vec, hipLaunchKernelGGL((pack_memory_kernel<T, VEC, true>), dim3(pack_grid((long)H * W * (C / vec)), B), 256, 0, (hipStream_t)stream,
                                                   (const T*)dout, extents, (T*)dx, H, W, C, Smax));
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+// a / La: the first memory (in the backward: its gradient); b / Lb: the second one, absent (null, Lb = 0) in the tail-zeroing form
+static bool concat_args_ok(const void* a, const int* len_a, int La, const void* b, const int* len_b, int Lb, const void* o, int B, int C, int Smax) {
+    return a && len_a && o && B > 0 && B <= 65535 && La > 0 && Lb >= 0 && C > 0 && Smax > 0 && (Lb == 0 || (b && len_b)) &&
+           (long)La * C <= 0x7fffffffL && (long)Lb * C <= 0x7fffffffL && (long)Smax * C <= 0x7fffffffL;
+}
+
+extern "C" int omr_concat_memory_fwd(int dtype, const void* a, const int* len_a, int La, const void* b, const int* len_b, int Lb, void* out, int B, int C,
+                                     int Smax, void* stream) {
+    if (!concat_args_ok(a, len_a, La, b, len_b, Lb, out, B, C, Smax)) return OMR_ERR_ARG;
+    if (Lb == 0) b = nullptr;
+    const int vec = extent_vec(dtype, C, a, b, out);
+    DISPATCH_T_VEC(dtype, vec, hipLaunchKernelGGL((concat_memory_kernel<T, VEC, false>), dim3(pack_grid((long)Smax * (C / vec)), B), 256, 0, (hipStream_t)stream,
+                                                  (const T*)a, (const T*)b, len_a, len_b, (T*)out, (T*)nullptr, La, Lb, C, Smax));
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+extern "C" int omr_concat_memory_bwd(int dtype, const void* dout, const int* len_a, int La, const int* len_b, int Lb, void* da, void* db, int B, int C,
+                                     int Smax, void* stream) {
+    if (!concat_args_ok(da, len_a, La, db, len_b, Lb, dout, B, C, Smax)) return OMR_ERR_ARG;
+    if (Lb == 0) db = nullptr;
+    const int vec = extent_vec(dtype, C, dout, da, db);
+    const long frags = (long)(La > Lb ? La : Lb) * (C / vec);         // both destinations are walked by the same grid
+    DISPATCH_T_VEC(dtype, vec, hipLaunchKernelGGL((concat_memory_kernel<T, VEC, true>), dim3(pack_grid(frags), B), 256, 0, (hipStream_t)stream,
+                                                  (const T*)dout, (const T*)nullptr, len_a, len_b, (T*)da, (T*)db, La, Lb, C, Smax));
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }

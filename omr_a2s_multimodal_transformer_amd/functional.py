@@ -338,6 +338,23 @@ class PackMemoryFn(Function):
         return K.pack_memory_bwd(g.contiguous(), ctx.ext, *ctx.hw), None, None
 
 
+class ConcatMemoryFn(Function):
+    """Packed memories a [B, La, d] and b [B, Lb, d] of a ragged batch, per-sample lengths int32 [B] on the device -> [B, smax, d]:
+    torch.cat([xi, xa], dim=1) of mixer_concat (model.py:644-675) of each sample alone, zeros behind.  b = len_b = None: the
+    tail-zeroing form (the first la rows of a, zeros behind them).  Nothing but the lengths is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, a, len_a, b, len_b, smax):
+        ctx.lens = (len_a, a.shape[1], len_b, 0 if b is None else b.shape[1])
+        return K.concat_memory_fwd(a.contiguous(), len_a, None if b is None else b.contiguous(), len_b, smax)
+
+    @staticmethod
+    def backward(ctx, g):
+        len_a, La, len_b, Lb = ctx.lens
+        da, db = K.concat_memory_bwd(g.contiguous(), len_a, La, len_b, Lb)
+        return da, None, db, None, None
+
+
 class DropoutFn(Function):
     """nn.Dropout / nn.Dropout2d with a counter-based mask that is regenerated (not stored) in backward.
     bwd_identity: the consumer applies (x > 0) * 1/(1-p) itself (see module docstring)."""

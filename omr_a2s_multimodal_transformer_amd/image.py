@@ -129,6 +129,16 @@ def collate_ragged(images: Sequence[Tensor]) -> Tuple[Tensor, Tensor]:
     return out, sizes
 
 
+def collate_ragged_pairs(images: Sequence[Tensor], audios: Sequence[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(image, spectrogram) pairs of different sizes -> (xi, xli, xa, xla): `collate_ragged` of each modality, the arguments of
+    `MultimodalTransformer.forward`'s ragged route and of `MultimodalTransformer.encode_ragged`."""
+    if len(images) != len(audios):
+        raise ValueError(f"collate_ragged_pairs needs as many images as audios, got {len(images)} and {len(audios)}")
+    xi, xli = collate_ragged(images)
+    xa, xla = collate_ragged(audios)
+    return xi, xli, xa, xla
+
+
 def image_batch(raws: Sequence, img_height: Optional[int], pad_value: float = 1.0, dtype: torch.dtype = torch.float32, device=None) -> Tuple[Tensor, Tensor]:
     """preprocess_image + pad_batch_inputs(pad_value=1.0: white background, preprocessing.py:104-109) in one go: every image is
     resampled straight into its slot of the padded batch.  Returns (x [B, 1, Hmax, Wmax], widths int32 [B])."""

@@ -530,6 +530,48 @@ def pack_memory_bwd(dout: Tensor, ext: Tensor, H: int, W: int) -> Tensor:
     return dx
 
 
+def _check_lengths(lens: Tensor, B: int, device) -> None:
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and tuple(lens.shape) == (B,) and lens.device == device, \
+        f"lengths must be int32 [B] on the device of the memory, got {lens.dtype} {tuple(lens.shape)} on {lens.device}"
+
+
+def concat_memory_fwd(a: Tensor, len_a: Tensor, b: Optional[Tensor], len_b: Optional[Tensor], smax: int, out: Optional[Tensor] = None) -> Tensor:
+    """Packed memories a [B, La, d], b [B, Lb, d] with per-sample lengths -> [B, smax, d]: rows [0, la) of a, then rows [0, lb) of b,
+    then zeros (torch.cat of each sample alone).  b = None: the first la rows of a, zeros behind them.  out: write there ([B, smax, d])."""
+    require_cuda(a, len_a, b, len_b)
+    assert a.dim() == 3 and a.is_contiguous() and smax >= 1
+    B, La, C = a.shape
+    _check_lengths(len_a, B, a.device)
+    Lb = 0
+    if b is not None:
+        assert b.is_contiguous() and b.dtype == a.dtype and b.dim() == 3 and b.shape[0] == B and b.shape[2] == C and b.device == a.device
+        Lb = b.shape[1]
+        _check_lengths(len_b, B, a.device)
+    if out is None:
+        out = torch.empty((B, smax, C), dtype=a.dtype, device=a.device)
+    assert out.is_contiguous() and tuple(out.shape) == (B, smax, C) and out.dtype == a.dtype and out.device == a.device
+    lib().call("omr_concat_memory_fwd", dtype_code(a.dtype), ptr(a), ptr(len_a), La, ptr(b), ptr(len_b) if Lb else None, Lb, ptr(out), B, C, smax,
+               cur_stream())
+    return out
+
+
+def concat_memory_bwd(dout: Tensor, len_a: Tensor, La: int, len_b: Optional[Tensor], Lb: int) -> Tuple[Tensor, Optional[Tensor]]:
+    """Adjoint of concat_memory_fwd: gradient [B, smax, d] -> (da [B, La, d], db [B, Lb, d] or None when Lb = 0), zeros at and past
+    each length; rows of dout at or past la + lb are not read."""
+    require_cuda(dout, len_a, len_b)
+    assert dout.dim() == 3 and dout.is_contiguous() and La >= 1 and Lb >= 0
+    B, smax, C = dout.shape
+    _check_lengths(len_a, B, dout.device)
+    da = torch.empty((B, La, C), dtype=dout.dtype, device=dout.device)
+    db = None
+    if Lb:
+        _check_lengths(len_b, B, dout.device)
+        db = torch.empty((B, Lb, C), dtype=dout.dtype, device=dout.device)
+    lib().call("omr_concat_memory_bwd", dtype_code(dout.dtype), ptr(dout), ptr(len_a), La, ptr(len_b) if Lb else None, Lb, ptr(da), ptr(db), B, C, smax,
+               cur_stream())
+    return da, db
+
+
 def add_layernorm_fwd(x: Tensor, res: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float = 1e-5, drop_p: float = 0.0, drop_seed: int = 0):
     """LayerNorm(dropout(x) + res); drop_p = 0 is the plain residual add."""
     require_cuda(x, res, gamma, beta)

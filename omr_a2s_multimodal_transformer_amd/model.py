@@ -82,6 +82,28 @@ class CrossEntropyLoss(nn.Module):
         return Fn.cross_entropy(logits_bvt, target, self.ignore_index)
 
 
+def _is_pixel_sizes(xl) -> bool:
+    """Whether a `forward` length argument names per-sample pixel sizes (the ragged route): a 2-D tensor [B, 2] of an integer type.
+    A bool [B, S] key-padding mask (also with S == 2) and everything else is a memory_len and goes to the decoder as it always did."""
+    return (isinstance(xl, torch.Tensor) and xl.dim() == 2 and xl.shape[1] == 2 and xl.dtype != torch.bool
+            and not xl.is_floating_point() and not xl.is_complex())
+
+
+def _pair_route(xli, xla) -> str:
+    """Which route a (xli, xla) pair of `MultimodalTransformer.forward` takes: "ragged" when BOTH are per-sample pixel sizes
+    (`_is_pixel_sizes`), "dense" when neither is (None, integer lengths [B], bool masks: the reference's forms); one of each is an error."""
+    ri, ra = _is_pixel_sizes(xli), _is_pixel_sizes(xla)
+    if ri != ra:
+        raise ValueError("the ragged route takes per-sample pixel sizes [B, 2] for BOTH modalities: got "
+                         f"xli {None if xli is None else tuple(xli.shape)} and xla {None if xla is None else tuple(xla.shape)}")
+    return "ragged" if ri else "dense"
+
+
+def _pad_mask(n: int, lens_dev: torch.Tensor) -> torch.Tensor:
+    """bool [B, n], True = no key: the rows at and past each sample's length (device lengths, no sync)."""
+    return torch.arange(n, device=lens_dev.device).unsqueeze(0) >= lens_dev.unsqueeze(1)
+
+
 def _beam_option(fn):
     """Gives a `predict` / `evaluate` method the keyword `beam` (1 .. 8, default 1).  The method's own parameter list -- part
     of the public surface the late-fusion code and its tests build on -- stays as it is; beam = 1 calls it as before, a
@@ -152,6 +174,22 @@ class _Base(FlatModuleMixin, LightningModule):
             return mems[0] if len(mems) == 1 else mems
         from .ddp import GradBoundary      # without a reducer the node only starts the decoder's collected weight gradients (runtime.WgradStream)
         return GradBoundary.apply(self._reducer, (1,), *mems)
+
+    def _pack_encode(self, enc: Encoder, pos: "PositionalEncoding2D", x: torch.Tensor, sizes: torch.Tensor) -> Tuple[torch.Tensor, List[int], torch.Tensor]:
+        """Ragged batch through one encoder: x [B, C, Hmax, Wmax] with sample b's sizes[b] = (h_b, w_b) pixels in the top-left corner ->
+        (memory [B, Smax, d], [S_b], S_b int32 on the device) with S_b = ceil(h_b / 16) * ceil(w_b / 8).  encoder -> 2-D PE on the
+        padded grid -> pack.  The extents of all resolutions are computed and uploaded once (Encoder.extent_table)."""
+        flat = self.ensure_flat()
+        if sizes.dim() != 2 or sizes.shape != (x.shape[0], 2):
+            raise ValueError(f"per-sample sizes must be [B, 2] (height, width), got {tuple(sizes.shape)} for a batch of {x.shape[0]}")
+        x = x.to(flat.device, non_blocking=True)
+        table = enc.extent_table(sizes, flat.device)
+        grid, grid_dev = table.host[-1], table.dev[-1]                            # int32 [B, 2]: each sample's feature grid
+        lens = (grid[:, 0].long() * grid[:, 1].long()).tolist()
+        f = enc.forward_nhwc(x, flat.compute_dtype, extents=table).permute(0, 3, 1, 2)
+        f = pos(f).permute(0, 2, 3, 1)                                            # NHWC again (a view of the PE kernel's output)
+        mem = Fn.PackMemoryFn.apply(f, grid_dev, max(lens))
+        return mem, lens, grid_dev[:, 0] * grid_dev[:, 1]
 
     def configure_optimizers(self):
         """torch.optim.Adam(lr=1e-4, amsgrad=False) over all parameters (model.py:134-139,475-483) as ONE fused kernel."""
@@ -463,17 +501,8 @@ class Transformer(_Base):
         [B, Smax, d], [S_b], S_b on the device) with S_b = ceil(h_b / 16) * ceil(w_b / 8): rows [0, S_b) of sample b are `encode` of b
         alone (to rounding: the InstanceNorm sums are added in another order), the rows behind them zeros.  encoder -> 2-D PE on the
         padded grid -> pack.  The extents of all resolutions are computed and uploaded once (Encoder.extent_table)."""
-        flat = self.ensure_flat()
-        if sizes.dim() != 2 or sizes.shape != (x.shape[0], 2):
-            raise ValueError(f"per-sample sizes must be [B, 2] (height, width), got {tuple(sizes.shape)} for a batch of {x.shape[0]}")
-        x = x.to(flat.device, non_blocking=True)
-        table = self.encoder.extent_table(sizes, flat.device)
-        grid, grid_dev = table.host[-1], table.dev[-1]                            # int32 [B, 2]: each sample's feature grid
-        lens = (grid[:, 0].long() * grid[:, 1].long()).tolist()
-        f = self.encoder.forward_nhwc(x, flat.compute_dtype, extents=table).permute(0, 3, 1, 2)
-        f = self.pos_2d(f).permute(0, 2, 3, 1)                                    # NHWC again (a view of the PE kernel's output)
-        mem = Fn.PackMemoryFn.apply(f, grid_dev, max(lens))
-        return self._boundary(mem), lens, grid_dev[:, 0] * grid_dev[:, 1]
+        mem, lens, lens_dev = self._pack_encode(self.encoder, self.pos_2d, x, sizes)
+        return self._boundary(mem), lens, lens_dev
 
     @torch.no_grad()
     def encode_ragged(self, x: torch.Tensor, sizes: torch.Tensor) -> List[torch.Tensor]:
@@ -489,17 +518,11 @@ class Transformer(_Base):
         those of b run alone at its own size; the memory rows past a sample's own length are masked out (-inf)."""
         if self._is_pixel_sizes(xl):
             mem, _, lens_dev = self._encode_packed(x, xl)
-            pad = torch.arange(mem.shape[1], device=mem.device).unsqueeze(0) >= lens_dev.unsqueeze(1)     # bool [B, Smax]: True = no key
-            return self.decoder(tgt=y_in, memory=mem, memory_len=pad)
+            return self.decoder(tgt=y_in, memory=mem, memory_len=_pad_mask(mem.shape[1], lens_dev))     # bool [B, Smax]: True = no key
         mem = self.encode(x)
         return self.decoder(tgt=y_in, memory=mem, memory_len=xl)     # host-resident ids / lengths go as they are: the decoder reads them before the copy
 
-    @staticmethod
-    def _is_pixel_sizes(xl) -> bool:
-        """Whether `forward`'s xl names per-sample pixel sizes (the ragged route): a 2-D tensor [B, 2] of an integer type.  A bool
-        [B, S] key-padding mask (also with S == 2) and everything else is a memory_len and goes to the decoder as it always did."""
-        return (isinstance(xl, torch.Tensor) and xl.dim() == 2 and xl.shape[1] == 2 and xl.dtype != torch.bool
-                and not xl.is_floating_point() and not xl.is_complex())
+    _is_pixel_sizes = staticmethod(_is_pixel_sizes)
 
     def apply_teacher_forcing(self, y: torch.Tensor) -> torch.Tensor:
         """model.py:152-160: each non-pad token is replaced w.p. teacher_forcing_prob by randint(0, V-1) drawn
@@ -593,6 +616,16 @@ class CrossAttention(nn.Module):
         out = self.attention.cross_attention(query.contiguous(), kv, None, self.training, blk_lq, blk_lkv)
         return out, None
 
+    def forward_key_lengths(self, query, key_value, len_key_value):
+        """The attention of `forward` over a ragged batch's packed memories: sample b sees the first len_key_value[b] (int32 [B] on the
+        device) keys of key_value [B, Skv, d] and nothing else, an exact -inf key bias (float32 [B, Skv], built like
+        Decoder._as_key_bias builds the decoder's) -- what b computes alone, where `forward` gets no lengths and masks nothing.  The
+        block mask of `forward` is not used: it is empty at batch size 1, and at B > 1 it hands sample b another sample's lengths
+        (quirk 2).  Query rows past a sample's own length give finite rows the caller drops (ConcatMemoryFn)."""
+        key_bias = Decoder._as_key_bias(_pad_mask(key_value.shape[1], len_key_value))
+        kv = self.attention.project_kv(key_value.contiguous())
+        return self.attention.cross_attention(query.contiguous(), kv, key_bias, self.training, None, None)
+
 
 class MultimodalTransformer(_Base):
     """model.py:358-726."""
@@ -615,6 +648,7 @@ class MultimodalTransformer(_Base):
         self.audio_pos_2d = PositionalEncoding2D(c.d_model, math.ceil(max_audio_height / HEIGHT_REDUCTION),
                                                  math.ceil(max_audio_width / WIDTH_REDUCTION), c.dropout)
         self.decoder = self._make_decoder()
+        self._mixer_kind = mixer_type            # the ragged route's mixers (`_mix_ragged`) go by name
         if mixer_type == "concat":
             self.mixer = self.mixer_concat
         elif mixer_type in ("attn_img", "attn_audio", "attn_both"):
@@ -629,7 +663,11 @@ class MultimodalTransformer(_Base):
         return _flatten_memory(pos(f))
 
     def encoder_forward(self, xi, xa, xli=None, xla=None, apply_teacher_forcing_modality: bool = False):
-        """model.py:485-522: BOTH encoders always run; one memory may then be returned alone."""
+        """model.py:485-522: BOTH encoders always run; one memory may then be returned alone.  xli and xla both integer [B, 2]
+        (`_is_pixel_sizes`): the ragged route, see `forward`."""
+        if _pair_route(xli, xla) == "ragged":
+            x, lens_dev, _ = self._encoder_forward_ragged(xi, xli, xa, xla, apply_teacher_forcing_modality)
+            return x, _pad_mask(x.shape[1], lens_dev)                            # bool [B, Smax]: True = no key
         xi = self._encode(self.image_encoder, self.image_pos_2d, xi)
         xa = self._encode(self.audio_encoder, self.audio_pos_2d, xa)
         xi, xa = self._boundary(xi, xa)
@@ -650,7 +688,61 @@ class MultimodalTransformer(_Base):
             x, xl = self.mixer(xi=xi, xa=xa, xli=xli, xla=xla)
         return x, xl
 
+    def _encoder_forward_ragged(self, xi, xli, xa, xla, apply_teacher_forcing_modality: bool):
+        """`encoder_forward` of a padded batch of pairs of different sizes -> (memory [B, Smax, d], its per-sample lengths int32 [B] on
+        the device, the same on the host): rows [0, S_b) of sample b are the memory of pair b run alone with xli = xla = None
+        (validation_step's form) to rounding, the rows behind them zeros.  Same draws from `random` as the dense route."""
+        if _pair_route(xli, xla) != "ragged":
+            raise ValueError("per-sample pixel sizes [B, 2] are needed for both modalities")
+        mi, li, di = self._pack_encode(self.image_encoder, self.image_pos_2d, xi, xli)
+        ma, la, da = self._pack_encode(self.audio_encoder, self.audio_pos_2d, xa, xla)
+        mi, ma = self._boundary(mi, ma)
+        self._touched = None
+        modality = self._draw_modality() if apply_teacher_forcing_modality else "both"
+        if modality == "image":
+            self._touched = ("image_encoder", "decoder")
+            return mi, di, li
+        if modality == "audio":
+            self._touched = ("audio_encoder", "decoder")
+            return ma, da, la
+        if modality != "both":
+            raise ValueError(f"Invalid modality: {modality}")
+        return self._mix_ragged(mi, li, di, ma, la, da)
+
+    def _mix_ragged(self, mi, li, di, ma, la, da):
+        """The mixers over packed memories (mi / ma [B, S, d], host lengths li / la, device lengths di / da).  The attention mixers
+        mask keys by the key memory's own lengths (CrossAttention.forward_key_lengths); ConcatMemoryFn places the rows and writes the
+        zeros behind each sample's length."""
+        kind = self._mixer_kind
+        if kind == "concat":
+            lens = [a + b for a, b in zip(li, la)]
+            return Fn.ConcatMemoryFn.apply(mi, di, ma, da, max(lens)), di + da, lens
+        if kind == "attn_img":                                                   # q = audio, kv = image
+            x = self.cross_attn.forward_key_lengths(ma, mi, di)
+            return Fn.ConcatMemoryFn.apply(x, da, None, None, x.shape[1]), da, la
+        if kind == "attn_audio":                                                 # q = image, kv = audio
+            x = self.cross_attn.forward_key_lengths(mi, ma, da)
+            return Fn.ConcatMemoryFn.apply(x, di, None, None, x.shape[1]), di, li
+        if kind == "attn_both":                                                  # model.py:723-725: the second attention's keys are the ATTENDED audio (quirk 3)
+            xa2 = self.cross_attn.forward_key_lengths(ma, mi, di)
+            xi2 = self.cross_attn.forward_key_lengths(mi, xa2, da)
+            lens = [a + b for a, b in zip(li, la)]
+            return Fn.ConcatMemoryFn.apply(xi2, di, xa2, da, max(lens)), di + da, lens
+        raise ValueError(f"Invalid mixer type: {kind}")
+
+    @torch.no_grad()
+    def encode_ragged(self, xi: torch.Tensor, sizes_i: torch.Tensor, xa: torch.Tensor, sizes_a: torch.Tensor) -> List[torch.Tensor]:
+        """Mixed memories [S_b, d] of a padded batch of (image, audio) pairs of different sizes (`image.collate_ragged_pairs`), one pass
+        of each encoder and of the mixer for all: each equals `_encode_input` of that pair alone to rounding (not bit for bit:
+        `predict` / `evaluate` keep the batch-size-1 passes)."""
+        x, _, lens = self._encoder_forward_ragged(xi, sizes_i, xa, sizes_a, False)
+        return [x[b, :n] for b, n in enumerate(lens)]
+
     def forward(self, xi, xli, xa, xla, y_in, apply_teacher_forcing_modality: bool = False) -> torch.Tensor:
+        """xli / xla as the reference's forms (None, integer lengths [B], bool masks): the dense route, every sample fills the planes
+        of xi and xa.  BOTH integer [B, 2], the (height, width) in pixels of each sample's content in the top-left corner of xi /
+        xa: the ragged route -- sample b's logits, loss share and gradients are those of pair b run alone at its own sizes; the
+        memory rows past a sample's own length are zeros and masked out (-inf).  One [B, 2] and one of another form: ValueError."""
         x, xl = self.encoder_forward(xi=xi, xa=xa, xli=xli, xla=xla, apply_teacher_forcing_modality=apply_teacher_forcing_modality)
         return self.decoder(tgt=y_in, memory=x, memory_len=xl)
 
