@@ -19,6 +19,8 @@ extern "C" {
 
 #define OMR_DTYPE_F32 0
 #define OMR_DTYPE_BF16 1
+/* a SOURCE type of omr_gather_ragged_batch only (8-bit grays); no other entry takes it */
+#define OMR_DTYPE_U8 2
 
 int omr_abi_version(void);
 
@@ -165,6 +167,19 @@ int omr_concat_memory_fwd(int dtype, const void* a, const int* len_a, int La, co
                           int Smax, void* stream);
 int omr_concat_memory_bwd(int dtype, const void* dout, const int* len_a, int La, const int* len_b, int Lb, void* da, void* db, int B, int C,
                           int Smax, void* stream);
+/* A padded batch out [B][1][H][W] from a device-resident data set in ONE launch: pad_batch_inputs (src/data/preprocessing.py:55-75)
+ * plus the / 255 of preprocess_image (:44-52).  src is one packed device buffer of src_dtype elements (OMR_DTYPE_U8: grays before the
+ * / 255; OMR_F32: spectrograms); sample n is a row-major h_n x w_n plane that starts at ELEMENT offsets[n] (int64 [N] on the device),
+ * sizes int32 [N][2] on the device = (h_n, w_n) clamped to [0, H] x [0, W], idx int32 [B] on the device (clamped to [0, N)), the
+ * same index may occur twice.  out[b][0][i][j] = conv(src[offsets[n] + i * w_n + j]) for i < h_n, j < w_n, n = idx[b], pad_value
+ * everywhere else (0: the ragged route; 1.0: the white background of preprocessing.py:104-109; a NaN pad stays a NaN: fp32 keeps its bits,
+ * bf16 gets 0xFFFF, what torch's host fp32 -> bf16 conversion writes for any NaN).  conv(uint8 v)
+ * = v / 255 by a correctly rounded fp32 DIVISION (omr_image_vpass_to_float's expression: the floats of preprocess_image, to the
+ * bit); an fp32 source is copied.  dst_dtype OMR_F32 or OMR_BF16 (the rounded fp32 value: omr_cast's).  Of src exactly the h_n * w_n
+ * elements of each listed sample are read.  16-byte stores when W is a multiple of 4 (fp32) / 8 (bf16) and out is 16-byte aligned.
+ * B < 1, B > 65535, N < 1, H * W > 2^31 - 1 or a null pointer: OMR_ERR_ARG; any other dtype code: OMR_ERR_UNSUPPORTED. */
+int omr_gather_ragged_batch(int src_dtype, const void* src, const long* offsets, const int* sizes, int N, const int* idx, int dst_dtype,
+                            void* out, int B, int H, int W, float pad_value, void* stream);
 
 /* ---- GEMM: C[M,N] (+)= act(opA(A) . opB(B)^T + bias) ------------------------------------------------------ */
 /* aten::linear/addmm/mm of the decoder layers (torch nn/modules/transformer.py:1158-1199), 1x1 point_conv

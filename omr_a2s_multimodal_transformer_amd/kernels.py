@@ -572,6 +572,32 @@ def concat_memory_bwd(dout: Tensor, len_a: Tensor, La: int, len_b: Optional[Tens
     return da, db
 
 
+_GATHER_SRC_CODE = {torch.uint8: header_constant("OMR_DTYPE_U8"), torch.float32: dtype_code(torch.float32)}
+
+
+def gather_ragged_batch(src: Tensor, offsets: Tensor, sizes: Tensor, idx: Tensor, H: int, W: int, dtype: torch.dtype, pad_value: float = 0.0,
+                        out: Optional[Tensor] = None) -> Tensor:
+    """Packed store `src` (1-D uint8 or fp32; sample n = the sizes[n, 0] x sizes[n, 1] plane at element offsets[n]) and sample indices
+    idx int32 [B] -> [B, 1, H, W] in `dtype` (fp32 / bf16): the samples (uint8: / 255) in the top-left corners, pad_value elsewhere
+    (csrc/batch_gather.hip).  offsets int64 [N], sizes int32 [N, 2], idx: all on src's device.  out: write there ([B, 1, H, W])."""
+    require_cuda(src, offsets, sizes, idx)
+    assert src.dim() == 1 and src.is_contiguous() and src.dtype in _GATHER_SRC_CODE, f"expected a flat uint8 / float32 store, got {src.dtype} {tuple(src.shape)}"
+    N = offsets.numel()
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.device == src.device, \
+        f"offsets must be int64 [N] on the device of src, got {offsets.dtype} {tuple(offsets.shape)} on {offsets.device}"
+    assert sizes.dtype == torch.int32 and sizes.is_contiguous() and tuple(sizes.shape) == (N, 2) and sizes.device == src.device, \
+        f"sizes must be int32 [N, 2] on the device of src, got {sizes.dtype} {tuple(sizes.shape)} on {sizes.device}"
+    assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous() and idx.device == src.device, \
+        f"idx must be int32 [B] on the device of src, got {idx.dtype} {tuple(idx.shape)} on {idx.device}"
+    B = idx.numel()
+    if out is None:
+        out = torch.empty((B, 1, H, W), dtype=dtype, device=src.device)
+    assert out.is_contiguous() and tuple(out.shape) == (B, 1, H, W) and out.dtype == dtype and out.device == src.device
+    lib().call("omr_gather_ragged_batch", _GATHER_SRC_CODE[src.dtype], ptr(src), ptr(offsets), ptr(sizes), N, ptr(idx), dtype_code(dtype), ptr(out), B, H, W,
+               float(pad_value), cur_stream())
+    return out
+
+
 def add_layernorm_fwd(x: Tensor, res: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float = 1e-5, drop_p: float = 0.0, drop_seed: int = 0):
     """LayerNorm(dropout(x) + res); drop_p = 0 is the plain residual add."""
     require_cuda(x, res, gamma, beta)
