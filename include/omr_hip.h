@@ -409,6 +409,14 @@ typedef struct omr_decode_linear_args {
     const unsigned char* w8; const float* w8_scale;
 } omr_decode_linear_args;
 int omr_decode_linear(const omr_decode_linear_args* args, void* stream);
+/* omr_decode_linear for rows that each sit at their OWN position (the linears omr_decode_steps_rows issues; continuous
+ * batching has no counterpart in the reference's one-input loop, src/transformer/model.py:171-199): row m is at position
+ * row_pos[m] (device int32 [M], must not be NULL).  Prologue 2 then adds the positional row pe_row + row_pos[m] * K, so pe_row
+ * is the whole table, and the out1 part of row m (the K|V projection's cache row) lands at
+ * out1 + m * ld1 + row_pos[m] * out1_pos_ld.  Everything else as in omr_decode_linear, to the bit.  The contents of row_pos
+ * are NOT range-checked here: the caller keeps them inside its table and cache, as omr_decode_steps_rows does by clamping them
+ * on the device before its first linear. */
+int omr_decode_linear_rows(const omr_decode_linear_args* args, const int* row_pos, long out1_pos_ld, void* stream);
 int omr_decode_steps(const omr_decode_desc* desc, long* tokens, int t0, int n_steps, long* out_tokens, float* out_top1, float* last_logits,
                      void* stream);
 /* omr_decode_steps over memories of different lengths in one batch (validation at batch size > 1; the reference's greedy loop,

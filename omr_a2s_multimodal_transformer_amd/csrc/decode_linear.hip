@@ -224,7 +224,8 @@ __global__ __launch_bounds__(64) void decode_pick_kernel(const float* __restrict
         const float v = __shfl_xor(best, o, 64); const int ii = __shfl_xor(bi, o, 64);
         if (v > best || (v == best && ii < bi)) { best = v; bi = ii; }
     }
-    if (lane == 0) { idx_out[blockIdx.x] = bi; if (val_out) val_out[blockIdx.x] = best; }
+    // no comparison won (the row is all NaN, or all -inf: `v > best` alone in the first half): index 0, as argmax_kernel and torch.argmax
+    if (lane == 0) { idx_out[blockIdx.x] = bi == 0x7fffffff ? 0 : bi; if (val_out) val_out[blockIdx.x] = best; }
 }
 
 // Per-row positions (omr_decode_steps_rows): ONE launch per host call turns pos[B] into the tables every kernel of position s
@@ -303,4 +304,9 @@ Position position_at(const Model& m, const int* pos, int t, int s) {
 extern "C" int omr_decode_linear(const omr_decode_linear_args* ap, void* stream) {
     if (!ap) return OMR_ERR_ARG;
     return omr_dec::decode_linear_impl(*ap, nullptr, 0, stream);
+}
+
+extern "C" int omr_decode_linear_rows(const omr_decode_linear_args* ap, const int* row_pos, long out1_pos_ld, void* stream) {
+    if (!ap || !row_pos || out1_pos_ld < 0) return OMR_ERR_ARG;
+    return omr_dec::decode_linear_impl(*ap, row_pos, out1_pos_ld, stream);
 }

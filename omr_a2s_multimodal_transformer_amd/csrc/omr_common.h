@@ -155,7 +155,10 @@ int attn_fwd_split_partials_rows(int dtype, const void* q, const void* k, const 
 // Top-k log-probabilities of ONE row by a group of 256 threads (tid 0..255; every thread of the WORKGROUP must call it: it
 // synchronises with __syncthreads): emit(j, index, log_softmax(x)[index]) for the j-th largest, j < k, ties towards the smaller
 // index, with the same values in every thread.  A max / sum-exp pass, then k selection passes over the candidates that come
-// after the previous pick in (value descending, index ascending) order.  sv / si: 256 entries of LDS each, the group's own.
+// after the previous pick in (value descending, index ascending) order.  A pass in which no candidate wins a comparison emits
+// index j, always inside [0, n): a row that is ALL NaN yields 0 .. k - 1 with NaN values, the indices a row of -inf gets by the
+// tie rule.  (A row with f < k comparable entries and NaN elsewhere yields those f, then f .. k - 1, which may name one of them
+// again; its values are NaN.)  sv / si: 256 entries of LDS each, the group's own.
 // One definition for topk_logprob_kernel (elementwise.hip) and the beam selection (decode_beam.hip): the on-device beam search has
 // to rank the very floats the host route reads back.
 template <typename Emit>
@@ -192,7 +195,7 @@ __device__ __forceinline__ void topk_logprob_row(const float* __restrict__ x, in
             __syncthreads();
         }
         last_v = sv[0]; last_i = si[0];
-        emit(j, last_i, last_v - lse);
+        emit(j, last_i < n ? last_i : (j < n ? j : 0), last_v - lse);      // no candidate (a row of NaN): pick j is index j, never past the row
         __syncthreads();
     }
 }
@@ -253,7 +256,7 @@ __device__ __forceinline__ void weighted_topk_logprob_row(const float* __restric
             __syncthreads();
         }
         last_v = sa[0]; last_i = si[0];
-        emit(j, last_i, logf(last_v));
+        emit(j, last_i < n ? last_i : (j < n ? j : 0), logf(last_v));      // no candidate (a row of NaN): pick j is index j, never past the row
         __syncthreads();
     }
 }

@@ -90,56 +90,93 @@ class _DecodeLinearArgs(ctypes.Structure):
                 ("w8", ctypes.c_void_p), ("w8_scale", ctypes.c_void_p)]
 
 
-def decode_linear(w: Tensor, bias: Optional[Tensor], *, x: Optional[Tensor] = None, res: Optional[Tensor] = None, ln=None, tokens: Optional[Tensor] = None,
-                  emb: Optional[Tensor] = None, pe_row: Optional[Tensor] = None, part: Optional[Tensor] = None, heads: int = 0, relu: bool = False,
-                  n0: Optional[int] = None, want32: bool = False, want_argmax: bool = False):
+def _view_ptr(t: Tensor) -> int:
+    """Address of a view's first element, also where the view is empty (data_ptr() of a tensor without elements is NULL)."""
+    return t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size()
+
+
+def decode_linear(w: Optional[Tensor], bias: Optional[Tensor], *, x: Optional[Tensor] = None, res: Optional[Tensor] = None, ln=None,
+                  tokens: Optional[Tensor] = None, emb: Optional[Tensor] = None, pe_row: Optional[Tensor] = None, part: Optional[Tensor] = None,
+                  heads: int = 0, relu: bool = False, n0: Optional[int] = None, want32: bool = False, want_argmax: bool = False,
+                  w8: Optional[Tensor] = None, w8_scale: Optional[Tensor] = None, dtype: Optional[torch.dtype] = None,
+                  out0: Optional[Tensor] = None, out1: Optional[Tensor] = None, out32: Optional[Tensor] = None, built: Optional[Tensor] = None,
+                  row_pos: Optional[Tensor] = None, out1_pos_ld: int = 0):
     """One linear of a decode position with the preceding element-wise step folded into its input rows (omr_decode_linear):
     x alone -> plain rows; x + res + ln=(gamma, beta, eps) -> LayerNorm(x + res); tokens + emb + pe_row -> embedding row + pe;
     part [M*heads, nsplit, hd+2] + heads -> merged key-split attention.  Returns (out0 [M, n0], out1 [M, N-n0] or None,
-    built rows [M, K] or None, fp32 copy or None) and, with want_argmax, (first index of the row maximum int64 [M], its value fp32 [M])."""
-    require_cuda(w, bias, x, res, tokens, emb, pe_row, part)
-    N, K = w.shape
-    dt = w.dtype
+    built rows [M, K] or None, fp32 copy or None) and, with want_argmax, (first index of the row maximum int64 [M], its value fp32 [M]).
+    w8 (uint8 e4m3 codes [N, K]) + w8_scale (fp32 [N]) replace `w`; `dtype` then names the row type (w may be None).
+    out0 / out1 / out32 (row-major 2-D views, unit inner stride; their row strides become ld0 / ld1 / ld32) and built
+    (contiguous [M, K]) are written in place of fresh tensors.  row_pos (int32 [M]) selects omr_decode_linear_rows: pe_row is
+    then the whole table [positions, K] and row m's out1 part lands row_pos[m] * out1_pos_ld elements further."""
+    require_cuda(w, bias, x, res, tokens, emb, pe_row, part, w8, w8_scale, out0, out1, out32, built, row_pos)
+    if w8 is not None:
+        assert w8.dtype == torch.uint8 and w8.dim() == 2 and w8.is_contiguous() and w8_scale is not None
+        assert w8_scale.dtype == torch.float32 and w8_scale.is_contiguous() and w8_scale.numel() == w8.shape[0]
+        N, K = w8.shape
+        assert dtype is not None or w is not None, "with w8, name the row type with `dtype` (or pass a `w` of that type)"
+        dt = dtype if dtype is not None else w.dtype
+    else:
+        N, K = w.shape
+        dt = w.dtype
+        assert dtype is None or dtype == dt
+    dev = w8.device if w8 is not None else w.device
     a = _DecodeLinearArgs()
-    built = None
+    if built is not None:
+        assert built.dtype == dt and built.is_contiguous() and built.shape[1] == K
     if part is not None:
         pro, M = 3, part.shape[0] // heads
         assert part.dtype == torch.float32 and part.is_contiguous() and part.shape[2] - 2 == K // heads
         a.part, a.nsplit, a.H, a.hd = part.data_ptr(), part.shape[1], heads, K // heads
     elif tokens is not None:
         pro, M = 2, tokens.numel()
-        assert tokens.dtype == torch.int64 and emb.dtype == dt and emb.is_contiguous() and pe_row.dtype == torch.float32 and pe_row.numel() == K
-        built = torch.empty((M, K), dtype=dt, device=w.device)
+        assert tokens.dtype == torch.int64 and emb.dtype == dt and emb.is_contiguous() and pe_row.dtype == torch.float32 and pe_row.is_contiguous()
+        assert pe_row.numel() == K if row_pos is None else (pe_row.dim() == 2 and pe_row.shape[1] == K)
+        built = torch.empty((M, K), dtype=dt, device=dev) if built is None else built
         a.tokens, a.emb, a.pe_row, a.vocab, a.xn_out = tokens.data_ptr(), emb.data_ptr(), pe_row.data_ptr(), emb.shape[0], built.data_ptr()
     elif ln is not None:
         pro, M = 1, x.shape[0]
         gamma, beta, eps = ln
         assert x.dtype == res.dtype == dt and x.stride(1) == res.stride(1) == 1 and gamma.dtype == beta.dtype == torch.float32
-        built = torch.empty((M, K), dtype=dt, device=w.device)
+        built = torch.empty((M, K), dtype=dt, device=dev) if built is None else built
         a.x, a.ldx, a.res, a.ldres, a.gamma, a.beta, a.eps, a.xn_out = x.data_ptr(), x.stride(0), res.data_ptr(), res.stride(0), gamma.data_ptr(), beta.data_ptr(), eps, built.data_ptr()
     else:
         pro, M = 0, x.shape[0]
         assert x.dtype == dt and x.stride(1) == 1 and x.shape[1] == K
         a.x, a.ldx = x.data_ptr(), x.stride(0)
+    assert built is None or built.shape[0] == M
     n0 = N if n0 is None else n0
-    out0 = torch.empty((M, n0), dtype=dt, device=w.device)
-    out1 = torch.empty((M, N - n0), dtype=dt, device=w.device) if n0 < N else None
-    out32 = torch.empty((M, N), dtype=torch.float32, device=w.device) if want32 else None
-    assert w.is_contiguous() and (bias is None or (bias.dtype == torch.float32 and bias.numel() == N))
+    if out0 is None:
+        out0 = torch.empty((M, max(n0, 1)), dtype=dt, device=dev)[:, :n0]      # n0 = 0: the entry still wants a pointer
+    if out1 is None and n0 < N:
+        out1 = torch.empty((M, N - n0), dtype=dt, device=dev)
+    if out32 is None and want32:
+        out32 = torch.empty((M, N), dtype=torch.float32, device=dev)
+    for t, cols, tdt in ((out0, n0, dt), (out1 if n0 < N else None, N - n0, dt), (out32, N, torch.float32)):
+        assert t is None or (t.dtype == tdt and t.dim() == 2 and tuple(t.shape) == (M, cols) and (t.stride(1) == 1 or cols <= 1)), "output view"
+    assert (w is None or w.is_contiguous()) and (bias is None or (bias.dtype == torch.float32 and bias.numel() == N))
     a.dtype, a.pro, a.M, a.N, a.K, a.relu, a.n0 = dtype_code(dt), pro, M, N, K, int(relu), n0
-    a.w, a.bias, a.out0, a.ld0 = w.data_ptr(), (bias.data_ptr() if bias is not None else None), out0.data_ptr(), n0
-    if out1 is not None:
-        a.out1, a.ld1 = out1.data_ptr(), N - n0
+    a.w, a.bias, a.out0, a.ld0 = (w.data_ptr() if w is not None else None), (bias.data_ptr() if bias is not None else None), _view_ptr(out0), out0.stride(0)
+    if w8 is not None:
+        a.w8, a.w8_scale = w8.data_ptr(), w8_scale.data_ptr()
+    if n0 < N:
+        a.out1, a.ld1 = _view_ptr(out1), out1.stride(0)
+    else:
+        out1 = None
     if out32 is not None:
-        a.out32, a.ld32 = out32.data_ptr(), N
+        a.out32, a.ld32 = _view_ptr(out32), out32.stride(0)
     amax = None
     if want_argmax:
-        idx = torch.empty(M, dtype=torch.int64, device=w.device)
-        val = torch.empty(M, dtype=torch.float32, device=w.device)
-        part = torch.empty(2 * M * ((N + 15) // 16), dtype=torch.float32, device=w.device)
+        idx = torch.empty(M, dtype=torch.int64, device=dev)
+        val = torch.empty(M, dtype=torch.float32, device=dev)
+        part = torch.empty(2 * M * ((N + 15) // 16), dtype=torch.float32, device=dev)
         a.amax_idx, a.amax_val, a.amax_part = idx.data_ptr(), val.data_ptr(), part.data_ptr()
         amax = (idx, val)
-    lib().call("omr_decode_linear", ctypes.byref(a), cur_stream())
+    if row_pos is not None:
+        assert row_pos.dtype == torch.int32 and row_pos.is_contiguous() and row_pos.numel() == M
+        lib().call("omr_decode_linear_rows", ctypes.byref(a), row_pos.data_ptr(), int(out1_pos_ld), cur_stream())
+    else:
+        lib().call("omr_decode_linear", ctypes.byref(a), cur_stream())
     return (out0, out1, built, out32) if amax is None else (out0, out1, built, out32, amax)
 
 
