@@ -200,6 +200,24 @@ template <int CI, bool DG> __device__ __forceinline__ void stat_reduce(unsigned 
     }
 }
 
+// The workgroup's bias gradient (called by all 1024 threads at the end of the tile loop).  Waves 4-7 of the weight-gradient half each hold a
+// quarter of it in column 0 of their second accumulator and have laid it out as bsum[quarter][row] (FOLD: rows 16-31 are the second pixel
+// half of the same 16 channels); one wave adds the quarters and leaves with ONE atomic instruction.  Every workgroup of a launch adds into
+// the same one or two 64-byte lines of db and float atomics are serialised per line at the memory side: flushed straight from the
+// accumulators (64 instructions of two lanes per workgroup, 16 384 per launch onto those lines) the bias sums cost 75-125 us per LAUNCH
+// whatever the batch, 40-120 us of it exposed at B = 32 (DESIGN.md "Batch windows", measured with tools/window_chain.py).
+template <bool WG, int NB, bool FOLD> __device__ __forceinline__ void bias_flush(const float* bsum, float* db, int wave, int lane) {
+    __syncthreads();
+    if constexpr (WG) {
+        if (wave == 0 && db != nullptr && lane < NB) {
+            float v = 0.f;
+#pragma unroll
+            for (int qr = 0; qr < 4; ++qr) v += bsum[qr * 32 + lane] + (FOLD ? bsum[qr * 32 + 16 + lane] : 0.f);
+            atomicAdd(&db[lane], v);
+        }
+    }
+}
+
 // One tile loop, compiled twice: DG = the data-gradient waves (0-7), !DG = the weight-gradient / DMA waves (8-15).  Both meet at the
 // same barriers; each keeps only its own accumulators in registers.
 // Measured alternatives (B = 32, 256 x 2048, 32 -> 32 channels; this form: 1 076 us plain, 1 172-1 212 us with the InstanceNorm apply):
@@ -210,7 +228,7 @@ template <int CI, bool DG> __device__ __forceinline__ void stat_reduce(unsigned 
 //   * register-staged tiles, two 8-wave workgroups per CU (the conv3x3_mfma.h pipeline): 1 042 us plain, but the apply needs the
 //     second tensor in staging registers too and spills at 128 registers.
 template <int CO, int CI, bool APPLY, bool XN, int NSLOT, bool DG>
-__device__ __forceinline__ void tile_loop(const FusedArgs& a, unsigned char* smem, const float* cst) {
+__device__ __forceinline__ void tile_loop(const FusedArgs& a, unsigned char* smem, const float* cst, float* bsum) {
     typedef Tile<CO> GT;
     typedef Tile<CI> XT;
     typedef Lds<CO, CI, APPLY, NSLOT> L;
@@ -454,12 +472,10 @@ __device__ __forceinline__ void tile_loop(const FusedArgs& a, unsigned char* sme
         }
         if (third_bias && a.db != nullptr && (lane & 31) == 0) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = acc_row(r, lane);
-                if (PAIR || co < CO) atomicAdd(&a.db[co & (PAIR ? 15 : 31)], wacc[1][r]);       // PAIR: rows 16-31 hold the second pixel half
-            }
+            for (int r = 0; r < 16; ++r) bsum[(wave - 4) * 32 + acc_row(r, lane)] = wacc[1][r];
         }
     }
+    bias_flush<WG, PAIR ? 16 : CO, PAIR>(bsum, a.db, wave, lane);
 }
 
 template <int CO, int CI, bool APPLY, bool XN, int NSLOT>
@@ -468,6 +484,7 @@ __global__ __launch_bounds__(1024) void conv_bwd_fused_kernel(FusedArgs a) {
     constexpr int GCPP = CO / 8, WP = L::WP;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ __attribute__((aligned(16))) float cst[3 * 32];    // APPLY: G = cA * Ghat + cB * Y + cC per channel
+    __shared__ float bsum[4 * 32];                                 // bias_flush: four quarters of the bias gradient
     const int tid = threadIdx.x, b = blockIdx.z;
     unsigned char* Ws = smem + L::OFF_WS;                          // flipped weights [32 rows ci][9][CO], rows >= CI zero
     for (int c = tid; c < 32 * 9 * GCPP; c += 1024) {
@@ -498,8 +515,8 @@ __global__ __launch_bounds__(1024) void conv_bwd_fused_kernel(FusedArgs a) {
         }
     }
     __syncthreads();
-    if (tid < NDG) tile_loop<CO, CI, APPLY, XN, NSLOT, true>(a, smem, cst);
-    else tile_loop<CO, CI, APPLY, XN, NSLOT, false>(a, smem, cst);
+    if (tid < NDG) tile_loop<CO, CI, APPLY, XN, NSLOT, true>(a, smem, cst, bsum);
+    else tile_loop<CO, CI, APPLY, XN, NSLOT, false>(a, smem, cst, bsum);
 }
 
 // Blocks per image: one workgroup per CU, split evenly over the images; never more than the image has tiles nor (with_stats: every block
@@ -561,7 +578,7 @@ struct S2 {
 };
 
 template <bool DG>
-__device__ __forceinline__ void tile_loop_s2(const FusedArgs& a, unsigned char* smem, const float* cst) {
+__device__ __forceinline__ void tile_loop_s2(const FusedArgs& a, unsigned char* smem, const float* cst, float* bsum) {
     typedef Tile<32> T32;
     constexpr int NSLOT = S2::NSLOT, GW = S2::GW, WP = S2::WP, XCPP = 4;
     constexpr bool WG = !DG;
@@ -749,14 +766,16 @@ __device__ __forceinline__ void tile_loop_s2(const FusedArgs& a, unsigned char* 
         }
         if (third_bias && a.db != nullptr && (lane & 31) == 0) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) atomicAdd(&a.db[acc_row(r, lane)], wacc[1][r]);
+            for (int r = 0; r < 16; ++r) bsum[(wave - 4) * 32 + acc_row(r, lane)] = wacc[1][r];
         }
     }
+    bias_flush<WG, 32, false>(bsum, a.db, wave, lane);
 }
 
 __global__ __launch_bounds__(1024) void conv_bwd_fused_s2_kernel(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ __attribute__((aligned(16))) float cst[2 * 32];
+    __shared__ float bsum[4 * 32];                                 // bias_flush: four quarters of the bias gradient
     const int tid = threadIdx.x, b = blockIdx.z;
     unsigned char* Ws = smem + S2::OFF_WS;
     for (int c = tid; c < 32 * 9 * 4; c += 1024) {
@@ -768,8 +787,8 @@ __global__ __launch_bounds__(1024) void conv_bwd_fused_s2_kernel(FusedArgs a) {
         cst[tid] = rs; cst[32 + tid] = -mu * rs;
     }
     __syncthreads();
-    if (tid < NDG) tile_loop_s2<true>(a, smem, cst);
-    else tile_loop_s2<false>(a, smem, cst);
+    if (tid < NDG) tile_loop_s2<true>(a, smem, cst, bsum);
+    else tile_loop_s2<false>(a, smem, cst, bsum);
 }
 
 }  // namespace
