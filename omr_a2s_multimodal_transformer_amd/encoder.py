@@ -143,24 +143,23 @@ class ConvBlock(nn.Module):
         if extents is not None:
             return self._nhwc_ragged(x, extents[0], extents[1]), 1.0
         pos = random.randint(1, 3)  # encoder.py:160 (drawn in eval mode too)
-        c1, c2, c3 = self.conv1, self.conv2, self.conv3
-        d1 = self._drop() if pos == 1 else None
-        if d1 is not None and x.shape[-1] == 1:      # 1-channel first layer: direct kernel without the fused dropout
-            x = Fn.Conv3x3Fn.apply(x, c1.weight, c1.bias, (1, 1), True, None, False, in_mask, in_scale, None, False)
-            x = Fn.DropoutFn.apply(x, d1[0], d1[1], d1[2], True)
-        else:
-            x = Fn.Conv3x3Fn.apply(x, c1.weight, c1.bias, (1, 1), True, None, False, in_mask, in_scale, d1, False)
-        s1 = 1.0 / (1.0 - d1[0]) if d1 is not None else 1.0
-        d2 = self._drop() if pos == 2 else None
+        x, s1 = self._conv(x, self.conv1, pos == 1, stride=(1, 1), mask_own=False, mask_input=in_mask, in_scale=in_scale)
         # conv2 <- InstanceNorm <- conv3 in backward: where the one-pass conv backward exists (bf16, 16 / 32 channels), conv3 hands its
-        # un-applied gradient on and conv2's backward applies the InstanceNorm backward while it loads (functional.FUSED_BWD)
-        hand_on = bool(Fn.FUSED_BWD & 2) and torch.is_grad_enabled() and x.requires_grad and x.dtype == torch.bfloat16 and x.shape[-1] in Fn.FUSED_NORM_CHANNELS
-        x, mean, rstd = Fn.Conv3x3Fn.apply(x, c2.weight, c2.bias, (1, 1), True, None, False, True, s1, d2, True, 2 if hand_on else 0)
-        s2 = 1.0 / (1.0 - d2[0]) if d2 is not None else 1.0
-        d3 = self._drop() if pos == 3 else None
-        x = Fn.Conv3x3Fn.apply(x, c3.weight, c3.bias, self.stride, True, (mean, rstd), not defer_out, True, s2, d3, False, 1 if hand_on else 0)
-        s3 = 1.0 / (1.0 - d3[0]) if d3 is not None else 1.0
-        return x, s3
+        # un-applied gradient on and conv2's backward applies the InstanceNorm backward while it loads (conv_plan.hands_on)
+        link = Fn.norm_link(x)
+        (x, mean, rstd), s2 = self._conv(x, self.conv2, pos == 2, stride=(1, 1), mask_own=False, mask_input=True, in_scale=s1, want_stats=True, link=link)
+        return self._conv(x, self.conv3, pos == 3, stride=self.stride, in_stats=(mean, rstd), mask_own=not defer_out, mask_input=True, in_scale=s2, link=link)
+
+    def _conv(self, x: torch.Tensor, conv: Conv2d, drop_here: bool, **kw):
+        """conv -> ReLU [-> the MixDropout of this position, in the conv's epilogue]: (result, 1/(1-p) of that dropout, else 1).
+        1-channel first layer: the direct kernel has no fused dropout, a dropout kernel follows it; whoever applies the conv's ReLU
+        backward (mask_own: the conv itself, else its consumer) applies the dropout's with it."""
+        d = self._drop() if drop_here else None
+        if d is not None and x.shape[-1] == 1:
+            y = Fn.DropoutFn.apply(Fn.conv3x3(x, conv, relu=True, **kw), d[0], d[1], d[2], not kw["mask_own"])
+        else:
+            y = Fn.conv3x3(x, conv, relu=True, drop=d, **kw)
+        return y, (1.0 / (1.0 - d[0]) if d is not None else 1.0)
 
     def _nhwc_ragged(self, x: torch.Tensor, ext_in: torch.Tensor, ext_out: torch.Tensor) -> torch.Tensor:
         """Ragged batch: x [B, H, W, C] is zero outside ext_in [B, 2] (each sample's rows / columns at this resolution) and the
@@ -171,14 +170,9 @@ class ConvBlock(nn.Module):
         pos = random.randint(1, 3)  # encoder.py:160 (drawn in eval mode too)
         convs = ((self.conv1, (1, 1), ext_in), (self.conv2, (1, 1), ext_in), (self.conv3, self.stride, ext_out))
         for i, (c, stride, ext) in enumerate(convs, start=1):
-            d = self._drop() if pos == i else None
             if i == 3:
                 x = Fn.InstNormExtentFn.apply(x, ext_in)
-            if d is not None and x.shape[-1] == 1:       # 1-channel first layer: direct kernel without the fused dropout
-                x = Fn.Conv3x3Fn.apply(x, c.weight, c.bias, stride, True, None, True, False, 1.0, None, False)
-                x = Fn.DropoutFn.apply(x, d[0], d[1], d[2], False)
-            else:
-                x = Fn.Conv3x3Fn.apply(x, c.weight, c.bias, stride, True, None, True, False, 1.0, d, False)
+            x, _ = self._conv(x, c, pos == i, stride=stride, mask_own=True, mask_input=False, in_scale=1.0)
             x = Fn.ExtentZeroFn.apply(x, ext)
         return x
 

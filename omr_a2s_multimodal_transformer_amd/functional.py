@@ -20,6 +20,7 @@ import torch
 from torch.autograd import Function
 
 from . import kernels as K
+from .conv_plan import GIVES, NO_LINK, TAKES, NormLink, NormRecord, hands_on, plan_conv3x3_bwd
 from .runtime import WgradStream, note_relu
 
 Tensor = torch.Tensor
@@ -39,12 +40,6 @@ TWO_PASS_NORM_BWD = False
 FUSED_BWD = int(os.environ.get("OMR_FUSED_BWD", "15"))
 FUSED_NORM_CHANNELS = tuple(int(c) for c in os.environ.get("OMR_FUSED_NORM_CHANNELS", "16,32").split(",") if c)   # conv2 widths that take the hand-on
 FUSED_MIN_COUT = int(os.environ.get("OMR_FUSED_MIN_COUT", "16"))
-_PENDING_NORM = {}        # data_ptr of a handed-on gradient -> (y, mean, rstd, ws, slots, relu_mask, relu_scale); consumed by the producer conv's backward
-
-
-def clear_pending_norm() -> None:
-    """Drop hand-ons a failed backward left behind (FlatParams.zero_grad)."""
-    _PENDING_NORM.clear()
 
 
 def wt(p: Tensor, dtype: torch.dtype) -> Tensor:
@@ -76,9 +71,9 @@ class Conv3x3Fn(Function):
     InstanceNorm statistics of the (dropped) output, reduced inside the same kernel."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, relu, in_stats, mask_own, mask_input, in_scale, drop, want_stats, norm_bwd=0):
-        """norm_bwd: 1 = this conv normalises on load and its producer's backward applies the InstanceNorm backward (this one hands its
-        un-applied gradient on); 2 = this conv's output feeds such a consumer (its backward expects the hand-on)."""
+    def forward(ctx, x, weight, bias, stride, relu, in_stats, mask_own, mask_input, in_scale, drop, want_stats, link):
+        """link: the NormLink of a hand-on (norm_link) or None.  The conv that normalises on load gives -- its producer's backward
+        applies the InstanceNorm backward, this one hands its un-applied gradient on --, the other conv takes."""
         dt = x.dtype
         B = x.shape[0]
         cout = weight.shape[0]
@@ -92,7 +87,7 @@ class Conv3x3Fn(Function):
             note_relu(y)
         own_scale = 1.0 / (1.0 - drop[0]) if drop is not None else 1.0
         ctx.cfg = (stride, relu, mask_own, mask_input, in_scale, own_scale)
-        ctx.norm_bwd = norm_bwd
+        ctx.link, ctx.role = link, NO_LINK if link is None else GIVES if in_stats is not None else TAKES
         ctx.weight, ctx.bias, ctx.stats = weight, bias, in_stats
         ctx.save_for_backward(x, y if (relu and mask_own) else None)
         if want_stats:
@@ -103,72 +98,66 @@ class Conv3x3Fn(Function):
 
     @staticmethod
     def backward(ctx, gy, *unused):
+        """Read the flags, plan (conv_plan.plan_conv3x3_bwd), then run the plan's steps top to bottom."""
         stride, relu, mask_own, mask_input, in_scale, own_scale = ctx.cfg
         x, y = ctx.saved_tensors
         weight, bias, stats = ctx.weight, ctx.bias, ctx.stats
         g = gy.contiguous()
-        pend = _PENDING_NORM.pop(g.data_ptr(), None) if ctx.norm_bwd == 2 else None
-        if ctx.norm_bwd == 2 and pend is None:
-            raise RuntimeError("Conv3x3Fn: the consumer's backward did not hand on its InstanceNorm gradient")
-        one_pass = stats is None and ctx.needs_input_grad[0] and K.conv3x3_bwd_fused_ok(x, g, stride)
-        if pend is not None and not (one_pass and pend[5]):
-            # nobody to apply it on load: the stand-alone pass
-            g = K.instnorm_bwd_apply(g, pend[0], pend[1], pend[2], pend[3], pend[4], relu_mask=pend[5], relu_scale=pend[6])
-            pend = None
-        if relu and mask_own:
+        taken = ctx.link.take(g) if ctx.role == TAKES else None
+        plan = plan_conv3x3_bwd(x.dtype == torch.bfloat16, x.shape[-1], g.shape[-1], stride, stats is not None, ctx.needs_input_grad[0], relu, mask_own,
+                                ctx.role, taken is not None and taken.relu_mask, FUSED_BWD, FUSED_MIN_COUT, TWO_PASS_NORM_BWD)
+        if plan.pre_apply:
+            g = K.instnorm_bwd_apply(g, *taken)
+        if plan.own_relu:
             g = K.relu_bwd(g, y, own_scale)        # y is the stored (dropped) output: (y > 0) * 1/(1-p) is ReLU + dropout backward
-        flat = getattr(weight, "omr_flat", None)        # flipped copies are re-laid once per optimizer step (params.FlatParams.refresh_flips)
-        if one_pass and (pend is not None or (FUSED_BWD & 1 and g.shape[3] >= FUSED_MIN_COUT)):
-            # one pass: data gradient (masked by the ReLU / dropout of the layer below), weight gradient, bias gradient
-            wd = flat.flipped(weight, x.dtype) if flat is not None else K.conv3x3_weight_flip(wt(weight, x.dtype))
-            if pend is not None:
-                K.instnorm_reduce_sums(pend[3], pend[4], x.shape[0], g.shape[3])
-            dx = K.conv3x3_bwd_fused(g, x, wd, weight.omr_grad, bias.omr_grad, mask_input, in_scale, norm=pend)
-            return (dx,) + (None,) * 11
-        # the normalise-on-load conv of the 16-channel block (stride 1): its one-pass form also normalises x in LDS and reduces the
-        # InstanceNorm-backward sums
-        one_pass_norm = (bool(FUSED_BWD & 4) and stats is not None and ctx.needs_input_grad[0] and tuple(stride) == (1, 1)
-                         and x.shape[-1] == 16 and g.shape[-1] == 16 and K.conv3x3_bwd_fused_ok(x, g, stride))
-        # ... and of the 32-channel one with stride (2, 2) (ConvBlock 1's conv3)
-        one_pass_s2 = (bool(FUSED_BWD & 8) and stats is not None and ctx.needs_input_grad[0] and tuple(stride) == (2, 2) and x.dtype == torch.bfloat16
-                       and x.shape[-1] == 32 and g.shape[-1] == 32)
-        one_pass_norm = one_pass_norm or one_pass_s2
-        # one workgroup per CU with a full LDS ring: little can run beside it, but its ramp-up / drain overlaps the data gradient's
-        # (28.37 -> 28.17 ms per C2 step; a shallower ring that leaves LDS for the neighbour loses more than it gains: 28.4)
-        if not one_pass_norm:
+        if plan.wgrad_separate:
+            # one workgroup per CU with a full LDS ring: little can run beside it, but its ramp-up / drain overlaps the data gradient's
+            # (28.37 -> 28.17 ms per C2 step; a shallower ring that leaves LDS for the neighbour loses more than it gains: 28.4)
             WgradStream.run("conv", lambda: K.conv3x3_wgrad(x, g, weight.omr_grad, stride=stride, in_stats=stats, db=bias.omr_grad), x, g, *(stats or ()))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            wd = flat.flipped(weight, x.dtype) if flat is not None else K.conv3x3_weight_flip(wt(weight, x.dtype))
-            H, W = x.shape[1], x.shape[2]
-            if stats is None:
-                dx = K.conv3x3(g, wd, None, stride=(1, 1), dil=stride, out_hw=(H, W), out_mask=x if mask_input else None, mask_scale=in_scale)
-            else:
-                # data gradient w.r.t. the normalised input with the InstanceNorm-backward sums reduced in its epilogue, then the
-                # apply pass (or, TWO_PASS_NORM_BWD, the recomputing form: see the switch's comment)
-                ws, slots = K.conv_stat_ws(x.shape[0], H, W, x.shape[3], x.device)
-                kw = dict(stride=(1, 1), dil=stride, out_hw=(H, W), stat_ws=ws, stat_slots=slots, stat_x=x, stat_stats=stats)
-                if ctx.norm_bwd == 1 or one_pass_norm:
-                    if one_pass_s2:
-                        dxh = K.conv3x3_bwd_fused_s2(g, x, wd, weight.omr_grad, bias.omr_grad, stats[0], stats[1], ws, slots)
-                    elif one_pass_norm:
-                        dxh = K.conv3x3_bwd_fused(g, x, wd, weight.omr_grad, bias.omr_grad, False, 1.0, xnorm=(stats[0], stats[1], ws, slots))
-                    else:
-                        dxh = K.conv3x3(g, wd, None, stat_mode=2, **kw)
-                    if ctx.norm_bwd == 1:
-                        # the producer conv's one-pass backward applies it on load: hand on dL/dxhat with what the apply needs
-                        dx = dxh
-                        _PENDING_NORM[dx.data_ptr()] = (x, stats[0], stats[1], ws, slots, mask_input, in_scale)
-                    else:
-                        dx = K.instnorm_bwd_apply(dxh, x, stats[0], stats[1], ws, slots, relu_mask=mask_input, relu_scale=in_scale)
-                elif TWO_PASS_NORM_BWD:
-                    K.conv3x3(g, wd, None, stat_mode=4, **kw)
-                    K.instnorm_reduce_sums(ws, slots, x.shape[0], x.shape[3])
-                    dx = K.conv3x3(g, wd, None, stat_mode=5, relu=mask_input, mask_scale=in_scale, **kw)
-                else:
-                    dxh = K.conv3x3(g, wd, None, stat_mode=2, **kw)
-                    dx = K.instnorm_bwd_apply(dxh, x, stats[0], stats[1], ws, slots, relu_mask=mask_input, relu_scale=in_scale)
+        if plan.dgrad == "none":
+            return (None,) * 12
+        flat = getattr(weight, "omr_flat", None)        # flipped copies are re-laid once per optimizer step (params.FlatParams.refresh_flips)
+        wd = flat.flipped(weight, x.dtype) if flat is not None else K.conv3x3_weight_flip(wt(weight, x.dtype))
+        B, H, W, cin = x.shape
+        if plan.dgrad == "conv":
+            dx = K.conv3x3(g, wd, None, stride=(1, 1), dil=stride, out_hw=(H, W), out_mask=x if mask_input else None, mask_scale=in_scale)
+        elif plan.dgrad == "fused":
+            # one pass: data gradient (masked by the ReLU / dropout of the layer below), weight gradient, bias gradient
+            dx = K.conv3x3_bwd_fused(g, x, wd, weight.omr_grad, bias.omr_grad, mask_input, in_scale)
+        elif plan.dgrad == "fused_apply":
+            # ... with the InstanceNorm backward of the layer above applied while the kernel loads its tile
+            K.instnorm_reduce_sums(taken.ws, taken.slots, B, g.shape[3])
+            dx = K.conv3x3_bwd_fused(g, x, wd, weight.omr_grad, bias.omr_grad, mask_input, in_scale, norm=taken)
+        else:
+            # data gradient w.r.t. the normalised input with the InstanceNorm-backward sums reduced into ws
+            ws, slots = K.conv_stat_ws(B, H, W, cin, x.device)
+            kw = dict(stride=(1, 1), dil=stride, out_hw=(H, W), stat_ws=ws, stat_slots=slots, stat_x=x, stat_stats=stats)
+            if plan.dgrad == "conv_stat2":
+                dx = K.conv3x3(g, wd, None, stat_mode=2, **kw)
+            elif plan.dgrad == "fused_xn":          # the one-pass form also normalises x in LDS
+                dx = K.conv3x3_bwd_fused(g, x, wd, weight.omr_grad, bias.omr_grad, False, 1.0, xnorm=(stats[0], stats[1], ws, slots))
+            elif plan.dgrad == "fused_s2":
+                dx = K.conv3x3_bwd_fused_s2(g, x, wd, weight.omr_grad, bias.omr_grad, stats[0], stats[1], ws, slots)
+            else:                                   # two_pass: sums only, then again with the apply in the epilogue (see the switch's comment)
+                K.conv3x3(g, wd, None, stat_mode=4, **kw)
+                K.instnorm_reduce_sums(ws, slots, B, cin)
+                dx = K.conv3x3(g, wd, None, stat_mode=5, relu=mask_input, mask_scale=in_scale, **kw)
+            if plan.finish == "apply":
+                dx = K.instnorm_bwd_apply(dx, x, stats[0], stats[1], ws, slots, relu_mask=mask_input, relu_scale=in_scale)
+            elif plan.finish == "hand_on":
+                # the producer conv's backward applies it: hand on dL/dxhat with what the apply needs
+                ctx.link.give(dx, NormRecord(x.detach(), stats[0], stats[1], ws, slots, mask_input, in_scale))
         return (dx,) + (None,) * 11
+
+
+def norm_link(x: Tensor) -> Optional[NormLink]:
+    """ConvBlock.nhwc, x = conv2's input: the link for conv3 -> conv2 where conv3 hands its InstanceNorm gradient on, else None."""
+    ok = hands_on(x.dtype == torch.bfloat16, x.shape[-1], torch.is_grad_enabled() and x.requires_grad, FUSED_BWD, FUSED_NORM_CHANNELS)
+    return NormLink() if ok else None
+
+
+def conv3x3(x, conv, *, stride, relu, in_stats=None, mask_own, mask_input, in_scale, drop=None, want_stats=False, link=None):
+    return Conv3x3Fn.apply(x, conv.weight, conv.bias, stride, relu, in_stats, mask_own, mask_input, in_scale, drop, want_stats, link)
 
 
 class DwConv3x3Fn(Function):

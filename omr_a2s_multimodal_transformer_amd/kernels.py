@@ -759,9 +759,14 @@ def conv3x3_wgrad(x: Tensor, dy: Tensor, dw_phys: Tensor, stride=(1, 1), in_stat
                Ho, Wo, cur_stream())
 
 
-def conv3x3_bwd_fused_ok(x: Tensor, g: Tensor, stride=(1, 1)) -> bool:
+def conv3x3_bwd_fused_covers(bf16: bool, cin: int, cout: int, stride=(1, 1)) -> bool:
     """Shapes omr_conv3x3_bwd_fused covers: bf16, stride 1, (COUT, CIN) in {(32, 32), (32, 16), (16, 16)}."""
-    return (x.dtype == torch.bfloat16 and tuple(stride) == (1, 1) and x.dim() == 4 and (g.shape[-1], x.shape[-1]) in ((32, 32), (32, 16), (16, 16)))
+    return bf16 and tuple(stride) == (1, 1) and (cout, cin) in ((32, 32), (32, 16), (16, 16))
+
+
+def conv3x3_bwd_fused_ok(x: Tensor, g: Tensor, stride=(1, 1)) -> bool:
+    """conv3x3_bwd_fused_covers of an NHWC input x and output gradient g."""
+    return x.dim() == 4 and conv3x3_bwd_fused_covers(x.dtype == torch.bfloat16, x.shape[-1], g.shape[-1], stride)
 
 
 def conv3x3_bwd_fused(g: Tensor, x: Tensor, w_flipped: Tensor, dw_phys: Tensor, db: Optional[Tensor], mask_input: bool, mask_scale: float = 1.0,

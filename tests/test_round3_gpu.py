@@ -357,6 +357,7 @@ def test_two_pass_instancenorm_backward_equals_the_stored_form(dtype, tol):
     x, xl, y_in, y_out = syn.synthetic_unimodal_batch(3, 80, 200, 12, V, w2i["<sos>"], w2i["<eos>"], seed=4)
     x, y_out = x.to(DEV), y_out.to(DEV)
     grads = {}
+    old = Fn.TWO_PASS_NORM_BWD
     try:
         for two_pass in (False, True):
             Fn.TWO_PASS_NORM_BWD = two_pass
@@ -366,7 +367,7 @@ def test_two_pass_instancenorm_backward_equals_the_stored_form(dtype, tol):
             torch.cuda.synchronize()
             grads[two_pass] = m._flat.grad.clone()
     finally:
-        Fn.TWO_PASS_NORM_BWD = True
+        Fn.TWO_PASS_NORM_BWD = old
     for n, (o, c) in m._flat.offsets.items():
         a, b = grads[False][o:o + c], grads[True][o:o + c]
         if a.abs().max() == 0:
