@@ -308,6 +308,24 @@ int omr_attn_bwd_ws(int dtype, const void* q, const void* k, const void* v, cons
                     long bsk, long bsv, long bso, long bsdo, long bsdq, long bsdk, long bsdv, int B, int H, int T, int S, int head_dim,
                     int causal, int window, const float* key_bias, const int* blk_lq, const int* blk_lkv, float dropout_p,
                     unsigned long long seed, const unsigned long long* drop_words, float* ws, long ws_floats, void* stream);
+/* Attention map: the head-averaged attention weights of CrossAttention (model.py:323, `attn_output, attn_weights = ...`), which
+ * torch's multi_head_attention_forward returns with need_weights = True, average_attn_weights = True -- recomputed from the `lse`
+ * omr_attn_fwd* wrote for the same operands (same layout [B][H][T], natural log):
+ *   w[b][t][s] (+)= out_scale * sum_h c * m_bhts * exp(score_bhts - lse_bht),      w fp32 [B][T][ldw], batch stride bsw
+ * score is what omr_attn_fwd scores (q.k / sqrt(hd) + key_bias, -inf under causal / window / the block mask / s >= kv_len[b]);
+ * m is the keep bit of drop_words (omr_attn_dropout_words) and c = 1 / (1 - p) when dropout_p > 0 -- torch returns the
+ * post-dropout weights in train mode -- else m = c = 1.  out_scale = 1 / H is torch's head average; 1 / (H L) with accumulate = 1
+ * on all but the first call averages L layers into one buffer.  Every s < S of every row is written (hidden keys: exactly 0; a
+ * row whose lse is -inf: zeros), columns S .. ldw - 1 are not touched.  kv_len: device int32 [B] or NULL.  No atomics: two runs
+ * give the same bits.  fp32 / bf16 operands, head_dim 32 or 64 (else OMR_ERR_UNSUPPORTED); q, k 16-byte aligned with row and
+ * batch strides that are multiples of 16 bytes. */
+int omr_attn_weights(int dtype, const void* q, const void* k, const float* lse, float* w, long ldq, long ldk, long ldw, long bsq, long bsk,
+                     long bsw, int B, int H, int T, int S, int head_dim, int causal, int window, const float* key_bias, const int* blk_lq,
+                     const int* blk_lkv, const int* kv_len, float dropout_p, const unsigned long long* drop_words, float out_scale,
+                     int accumulate, void* stream);
+/* keys one workgroup of omr_attn_weights walks for (B, T, S): a multiple of 64, the launcher's own plan (tests assert that their
+ * shapes give a workgroup more than one 64-key tile); 0 for a non-positive size */
+long omr_attn_weights_range(int B, int T, int S);
 /* omr_attn_fwd for ONE block of at most 32 query rows (KV-cached decode: T = 1) with the keys split over workgroups of 256 keys
  * (partial softmaxes merged by a second small kernel): a single query row would otherwise keep each (batch, head) on one
  * workgroup walking all S keys.  No causal / block masks (a decode step sees every cached key), no dropout.

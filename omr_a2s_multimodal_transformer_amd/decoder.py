@@ -112,11 +112,23 @@ class MultiheadAttention(nn.Module):
         d = self.embed_dim
         return Fn.linear(memory, self.in_proj_weight, self.in_proj_bias, rows=(d, 3 * d))
 
-    def cross_attention(self, x, kv, key_bias, training: bool, blk_lq=None, blk_lkv=None):
+    def cross_attention(self, x, kv, key_bias, training: bool, blk_lq=None, blk_lkv=None, weights=None):
+        """weights (None, or a dict of kernels.attn_weights keywords: out / out_scale / accumulate): also write the head-averaged
+        attention map of this call -- post-dropout in training, from the words the forward read -- and leave it in weights["out"].
+        The attention itself is launched exactly as without it."""
         d = self.embed_dim
         q = Fn.linear(x, self.in_proj_weight, self.in_proj_bias, rows=(0, d))
         p = self.dropout if training else 0.0
-        o = Fn.AttentionFn.apply(q, kv, self.num_heads, False, -1, key_bias, blk_lq, blk_lkv, p, next_seed("attn", p) if p > 0 else 0)
+        seed = next_seed("attn", p) if p > 0 else 0
+        if weights is None:
+            o = Fn.AttentionFn.apply(q, kv, self.num_heads, False, -1, key_bias, blk_lq, blk_lkv, p, seed)
+        else:
+            tap = []
+            o = Fn.AttentionFn.apply(q, kv, self.num_heads, False, -1, key_bias, blk_lq, blk_lkv, p, seed, tap)
+            qt, kt, lse, words = tap[0]
+            weights["out"] = K.attn_weights(qt.detach(), kt.detach(), lse, self.num_heads, key_bias=key_bias, blk_lq=blk_lq, blk_lkv=blk_lkv,
+                                            dropout_p=p, drop_words=words, out=weights.get("out"), out_scale=weights.get("out_scale"),
+                                            accumulate=bool(weights.get("accumulate", False)))
         return Fn.linear(o, self.out_proj.weight, self.out_proj.bias)
 
 
@@ -134,10 +146,12 @@ class TransformerDecoderLayer(nn.Module):
 
     fused_node = True       # one autograd node per layer (functional.DecoderLayerFn) instead of one per operation: same kernels, same bits
 
-    def forward(self, x, memory, window: int, self_key_bias, mem_key_bias, kv=None):
-        """kv: this layer's cross-attention K|V of `memory` when the decoder projected all layers at once."""
+    def forward(self, x, memory, window: int, self_key_bias, mem_key_bias, kv=None, per_op: bool = False, weights=None):
+        """kv: this layer's cross-attention K|V of `memory` when the decoder projected all layers at once.  per_op: take the
+        per-operation path whatever `fused_node` says; weights: see MultiheadAttention.cross_attention (per-operation path only)."""
         tr, p = self.training, self.dropout_p
-        if self.fused_node and kv is not None and x.is_contiguous():
+        assert weights is None or per_op
+        if self.fused_node and kv is not None and x.is_contiguous() and not per_op:
             pp = p if tr else 0.0
             # the seeds of the layer's six dropout sites, drawn in the order the per-operation path draws them
             seeds = tuple(next_seed(kind, pp) for kind in ("attn", "rows", "attn", "rows", "rows", "rows")) if pp > 0.0 else (0,) * 6
@@ -147,7 +161,7 @@ class TransformerDecoderLayer(nn.Module):
         x = Fn.AddLayerNormFn.apply(sa, x, self.norm1.weight, self.norm1.bias, drop())
         if kv is None:
             kv = self.multihead_attn.project_kv(memory)
-        ca = self.multihead_attn.cross_attention(x, kv, mem_key_bias, tr)
+        ca = self.multihead_attn.cross_attention(x, kv, mem_key_bias, tr, weights=weights)
         x = Fn.AddLayerNormFn.apply(ca, x, self.norm2.weight, self.norm2.bias, drop())
         h = Fn.linear(x, self.linear1.weight, self.linear1.bias, relu=True, mask_own=True, drop=drop())     # FFN dropout in the GEMM epilogue
         ff = Fn.linear(h, self.linear2.weight, self.linear2.bias)
@@ -333,6 +347,35 @@ class Decoder(nn.Module):
         return st.run(token, n_steps)
 
     def forward(self, tgt: torch.Tensor, memory: torch.Tensor, memory_len: Optional[torch.Tensor]) -> torch.Tensor:
+        return self._run(tgt, memory, memory_len)
+
+    @torch.no_grad()
+    def cross_attention_maps(self, tgt: torch.Tensor, memory: torch.Tensor, memory_len: Optional[torch.Tensor],
+                             layers=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`forward` in eval mode plus where it looked: -> (logits [B, V, T], maps fp32 [B, T, S]).  maps[b, t] is the cross-attention
+        distribution over the S memory rows of the position that predicts token t, averaged over the heads (what
+        nn.MultiheadAttention returns with need_weights=True) and over the decoder layers `layers` (an iterable of layer indices;
+        default: all).  The layers run on the per-operation path -- the kernels of the fused node, so the logits are `forward`'s bit
+        for bit -- and each selected layer adds its map into one buffer (omr_attn_weights, out_scale 1 / (H * len(layers))).  Keys a
+        memory mask hides get exactly 0.  Training mode raises: the decoder's dropout draws are not replayed."""
+        return self._cross_attention_maps(tgt, memory, memory_len, layers, True)
+
+    def _cross_attention_maps(self, tgt, memory, memory_len, layers, tgt_padding_bias: bool):
+        """cross_attention_maps; tgt_padding_bias=False (model._align only) leaves out the +1.0 `forward` adds on target keys equal
+        to 0 when there is a memory mask (reference quirk 1), as in a decode without a memory mask: a row of a padded batch then
+        equals its batch-size-1 pass also when its words contain token 0.  The logits are then not `forward`'s."""
+        if self.training:
+            raise ValueError("cross_attention_maps runs in eval mode: the decoder's dropout draws are not replayed")
+        L = len(self.transformer_decoder.layers)
+        sel = sorted(set(range(L) if layers is None else (int(i) for i in layers)))
+        if not sel or sel[0] < 0 or sel[-1] >= L:
+            raise ValueError(f"layers must name at least one of the decoder's {L} layers, got {layers}")
+        H = self.transformer_decoder.layers[0].multihead_attn.num_heads
+        maps = dict(layers=sel, out=None, out_scale=1.0 / (H * len(sel)), accumulate=False)
+        logits = self._run(tgt, memory, memory_len, maps=maps, tgt_padding_bias=tgt_padding_bias)
+        return logits, maps["out"]
+
+    def _run(self, tgt: torch.Tensor, memory: torch.Tensor, memory_len: Optional[torch.Tensor], maps=None, tgt_padding_bias: bool = True) -> torch.Tensor:
         emb_w, dt = self.embedding.weight, self._compute_dtype()
         memory = self._in_compute_dtype(memory)
         B, T = tgt.shape
@@ -347,7 +390,7 @@ class Decoder(nn.Module):
         mem_mask = None if mem_full else self.get_memory_key_padding_mask(memory, None if memory_len is None else _to_dev(memory_len, memory.device))
         mem_bias = self._as_key_bias(mem_mask)
         # tgt_key_padding_mask = (tgt == 0).float() is ADDED (+1.0); dropped when there is no memory mask (decoder.py:131-132)
-        self_bias = None if (memory_len is None or tgt_no_pad) else (tgt == 0).to(torch.float32).contiguous()
+        self_bias = None if (memory_len is None or tgt_no_pad or not tgt_padding_bias) else (tgt == 0).to(torch.float32).contiguous()
         window = self.attn_window if self.attn_window > 0 else -1
         layers = self.transformer_decoder.layers
         pack = self._cross_kv_pack(dt)
@@ -357,8 +400,16 @@ class Decoder(nn.Module):
             kvs = Fn.FusedCrossKVFn.apply(memory, pack, sink)
             for li, kv in enumerate(kvs):
                 kv.omr_grad_sink = (sink, li)
-        for layer, kv in zip(layers, kvs):
-            x = layer(x, memory, window, self_bias, mem_bias, kv)
+        for li, (layer, kv) in enumerate(zip(layers, kvs)):
+            if maps is None:
+                x = layer(x, memory, window, self_bias, mem_bias, kv)
+                continue
+            weights = None
+            if li in maps["layers"]:
+                weights = dict(out=maps["out"], out_scale=maps["out_scale"], accumulate=maps["out"] is not None)
+            x = layer(x, memory, window, self_bias, mem_bias, kv, per_op=True, weights=weights)
+            if weights is not None:
+                maps["out"] = weights["out"]
         V = self.output_size
         logits = Fn.linear(x, self.out_layer.weight, self.out_layer.bias, out_ld=K.round_up(V, 8))  # [B,T,V], row pitch round_up(V,8)
         return logits.permute(0, 2, 1)  # [B, V, T] (decoder.py:145-146)

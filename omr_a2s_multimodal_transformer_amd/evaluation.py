@@ -7,7 +7,10 @@ from __future__ import annotations
 
 import contextvars
 import functools
-from typing import Callable, List, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Callable, List, Optional, Sequence, Tuple
+
+import numpy as np
 
 from .decoder import takes_ragged_state
 
@@ -185,3 +188,89 @@ def beam_results(beam: int, positions: int, eos: int, scores, best_score, best_r
             raise RuntimeError(f"beam search: input {n} has neither a finished nor a live hypothesis")
         out.append((seq, score))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ alignment (attention maps)
+
+ALIGN_MAP_BYTES = 1 << 30   # `align` cuts its groups so that the fp32 map buffer B * Tmax * Smax * 4 of a group stays under this
+GRID_ROW_PIXELS, GRID_COL_PIXELS = 16, 8      # encoder.HEIGHT_REDUCTION / WIDTH_REDUCTION: one memory row covers 16 x 8 input pixels
+
+
+@dataclass
+class Alignment:
+    """Where the decoder looked for each token of one input (`Transformer.align` / `MultimodalTransformer.align`): token t of
+    `words` leaned most on memory row index[t], with head- and layer-averaged cross-attention weight weight[t]; that row is
+    cell[t] = (row, column) of the encoder grid of its source[t] ("image" / "audio") and covers box[t] = (top, left, bottom,
+    right) input pixels (bottom / right exclusive, clipped to the input).  maps: the whole distributions, fp32 [n, S] on the
+    device, when asked for."""
+    words: List[str]
+    index: np.ndarray            # int64 [n]
+    weight: np.ndarray           # float32 [n]
+    cell: np.ndarray             # int64 [n, 2]
+    box: np.ndarray              # int64 [n, 4]
+    source: List[str]
+    maps: Optional[object] = None
+
+
+def grid_of(height: int, width: int) -> Tuple[int, int]:
+    """The encoder grid (h', w') = (ceil(h / 16), ceil(w / 8)) of an input of height x width pixels."""
+    return -(-int(height) // GRID_ROW_PIXELS), -(-int(width) // GRID_COL_PIXELS)
+
+
+def cells_and_boxes(index, sizes, split: Optional[int] = None):
+    """Memory row -> encoder cell, input pixels and source.  index: the memory rows, int [n].  sizes: one (source, height, width)
+    per grid the memory is made of, in memory order -- one entry for a single encoder's memory (or an attention mixer's, whose
+    memory lives on the query grid), two for a concatenated memory, whose first grid holds rows [0, split) and whose second
+    grid starts at row `split` (the image memory's length; checked against the first grid).  -> (cell int64 [n, 2] = (s // w',
+    s % w') on that grid, box int64 [n, 4] = (top, left, bottom, right) in that input's pixels clipped to its size, source
+    [n]).  Pure host arithmetic."""
+    idx = np.asarray(index, dtype=np.int64).reshape(-1)
+    sizes = [(str(src), int(h), int(w)) for src, h, w in sizes]
+    if len(sizes) not in (1, 2):
+        raise ValueError(f"a memory is one grid or two concatenated ones, got {len(sizes)} sizes")
+    grids = [grid_of(h, w) for _, h, w in sizes]
+    if len(sizes) == 2:
+        first = grids[0][0] * grids[0][1]
+        if split is None:
+            split = first
+        if split != first:
+            raise ValueError(f"split {split} is not the length {first} of the first grid {grids[0]}")
+    elif split is not None:
+        raise ValueError("split belongs to a memory of two grids")
+    starts = [0, split] if len(sizes) == 2 else [0]
+    total = sum(gh * gw for gh, gw in grids)
+    if idx.size and (idx.min() < 0 or idx.max() >= total):
+        raise ValueError(f"memory rows must lie in [0, {total}), got {int(idx.min())} .. {int(idx.max())}")
+    part = (idx >= split).astype(np.int64) if len(sizes) == 2 else np.zeros_like(idx)
+    cell = np.zeros((idx.size, 2), dtype=np.int64)
+    box = np.zeros((idx.size, 4), dtype=np.int64)
+    for g, ((_, h, w), (gh, gw)) in enumerate(zip(sizes, grids)):
+        sel = part == g
+        s = idx[sel] - starts[g]
+        r, c = s // gw, s % gw
+        cell[sel] = np.stack([r, c], axis=1)
+        box[sel] = np.stack([r * GRID_ROW_PIXELS, c * GRID_COL_PIXELS, np.minimum((r + 1) * GRID_ROW_PIXELS, h),
+                             np.minimum((c + 1) * GRID_COL_PIXELS, w)], axis=1)
+    return cell, box, [sizes[g][0] for g in part.tolist()]
+
+
+def plan_align_groups(targets: Sequence[int], memories: Sequence[int], batch_size: int, limit_bytes: Optional[int] = None) -> List[List[int]]:
+    """Consecutive groups of input indices for `align`: at most batch_size rows each, cut further so that the group's fp32 map
+    buffer rows * max(targets) * max(memories) * 4 stays within limit_bytes (default ALIGN_MAP_BYTES, read at call time); an input
+    that exceeds the limit alone is a group of its own."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    limit = ALIGN_MAP_BYTES if limit_bytes is None else limit_bytes
+    groups: List[List[int]] = []
+    cur: List[int] = []
+    tmax = smax = 0
+    for i, (t, s) in enumerate(zip(targets, memories)):
+        t2, s2 = max(tmax, t), max(smax, s)
+        if cur and (len(cur) >= batch_size or (len(cur) + 1) * t2 * s2 * 4 > limit):
+            groups.append(cur)
+            cur, t2, s2 = [], t, s
+        cur.append(i)
+        tmax, smax = t2, s2
+    if cur:
+        groups.append(cur)
+    return groups

@@ -406,10 +406,12 @@ class AddLayerNormFn(Function):
 class AttentionFn(Function):
     """Fused attention core over packed projections.
     self mode : qkv [B,T,3d] -> o [B,T,d]           (backward returns d(qkv) packed)
-    cross mode: q [B,T,d], kv [B,S,2d] -> o [B,T,d] (backward returns dq and d(kv) packed)"""
+    cross mode: q [B,T,d], kv [B,S,2d] -> o [B,T,d] (backward returns dq and d(kv) packed)
+    tap (optional eleventh argument, a list): receives (q, k, lse, dropout words) of this call, the operands an attention map is
+    recomputed from (kernels.attn_weights); the launches are the ones of a call without it."""
 
     @staticmethod
-    def forward(ctx, q_or_qkv, kv, nhead, causal, window, key_bias, blk_lq, blk_lkv, dropout_p, seed):
+    def forward(ctx, q_or_qkv, kv, nhead, causal, window, key_bias, blk_lq, blk_lkv, dropout_p, seed, tap=None):
         if kv is None:
             d = q_or_qkv.shape[-1] // 3
             q, k, v = q_or_qkv[..., :d], q_or_qkv[..., d:2 * d], q_or_qkv[..., 2 * d:]
@@ -424,8 +426,11 @@ class AttentionFn(Function):
             words = WgradStream.prepare(lambda: K.attn_dropout_words(B_, nhead, T_, S_, dropout_p, seed, dev_), dev_)
         o, lse = K.attn_fwd(q, k, v, nhead, causal=causal, window=window, key_bias=key_bias, blk_lq=blk_lq, blk_lkv=blk_lkv,
                             dropout_p=dropout_p, seed=seed, drop_words=words)
+        if tap is not None:
+            tap.append((q, k, lse, words))
         ctx.cfg = (nhead, causal, window, dropout_p, seed, kv is None, d)
         ctx.drop_words = words
+        ctx.extra_args = 8 if tap is None else 9
         ctx.kv_sink = getattr(kv, "omr_grad_sink", None) if kv is not None else None     # (KVGradSink, layer): see FusedCrossKVFn
         ctx.save_for_backward(q_or_qkv, kv, o, lse, key_bias, blk_lq, blk_lkv)
         return o
@@ -447,7 +452,7 @@ class AttentionFn(Function):
             dq, dk, dv = dqkv, dkv[..., :d], dkv[..., d:]
         K.attn_bwd(q, k, v, o, go, lse, dq, dk, dv, nhead, causal=causal, window=window, key_bias=key_bias, blk_lq=blk_lq, blk_lkv=blk_lkv,
                    dropout_p=dropout_p, seed=seed, drop_words=ctx.drop_words)
-        return dqkv, dkv, None, None, None, None, None, None, None, None
+        return (dqkv, dkv) + (None,) * ctx.extra_args
 
 
 class DecoderLayerFn(Function):

@@ -929,6 +929,36 @@ def attn_bwd(q, k, v, o, dout, lse, dq, dk, dv, nhead: int, *, causal=False, win
                ptr(key_bias), ptr(blk_lq), ptr(blk_lkv), float(dropout_p), int(seed) & (2**64 - 1), ptr(drop_words), ptr(ws), nws, cur_stream())
 
 
+def attn_weights(q: Tensor, k: Tensor, lse: Tensor, nhead: int, *, causal: bool = False, window: int = -1, key_bias: Optional[Tensor] = None,
+                 blk_lq: Optional[Tensor] = None, blk_lkv: Optional[Tensor] = None, kv_len: Optional[Tensor] = None, dropout_p: float = 0.0,
+                 drop_words: Optional[Tensor] = None, out: Optional[Tensor] = None, out_scale: Optional[float] = None,
+                 accumulate: bool = False) -> Tensor:
+    """Head-averaged attention weights (omr_attn_weights) of the attention whose forward wrote `lse` [B,H,T] for these q [B,T,d] /
+    k [B,S,d] and masks -> fp32 [B,T,S].  out_scale defaults to 1 / nhead (torch's head average); `out` (fp32 [B,T,S], unit inner
+    stride, any row pitch) with accumulate=True is added to instead of written.  A new buffer has its rows padded to 16 bytes;
+    the returned tensor is the [B,T,S] view of it.  dropout_p > 0 needs the forward's drop_words."""
+    require_cuda(q, k, lse, key_bias, blk_lq, blk_lkv, kv_len, drop_words, out)
+    B, T, d = q.shape
+    S = k.shape[1]
+    assert k.shape == (B, S, d) and d % nhead == 0 and q.dtype == k.dtype
+    assert lse.dtype == torch.float32 and tuple(lse.shape) == (B, nhead, T) and lse.is_contiguous()
+    if key_bias is not None:
+        assert key_bias.dtype == torch.float32 and tuple(key_bias.shape) == (B, S) and key_bias.is_contiguous()
+    for t in (blk_lq, blk_lkv, kv_len):
+        if t is not None:
+            assert t.dtype == torch.int32 and t.numel() == B and t.is_contiguous()
+    assert dropout_p == 0.0 or drop_words is not None, "the post-dropout weights need the keep words the forward read"
+    if out is None:
+        assert not accumulate, "accumulate adds to a buffer of the caller's"
+        out = torch.empty((B, T, round_up(S, 4)), dtype=torch.float32, device=q.device)[:, :, :S]
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, T, S)
+    (ldq, bsq), (ldk, bsk), (ldw, bsw) = _bts(q), _bts(k), _bts(out)
+    lib().call("omr_attn_weights", dtype_code(q.dtype), ptr(q), ptr(k), ptr(lse), ptr(out), ldq, ldk, ldw, bsq, bsk, bsw, B, nhead, T, S, d // nhead,
+               int(causal), int(window), ptr(key_bias), ptr(blk_lq), ptr(blk_lkv), ptr(kv_len), float(dropout_p), ptr(drop_words),
+               float(1.0 / nhead if out_scale is None else out_scale), int(accumulate), cur_stream())
+    return out
+
+
 def attn_dropout_mask(B: int, H: int, T: int, S: int, p: float, seed: int, device) -> Tensor:
     """uint8 [B,H,T,S] keep-mask of the attention-probability dropout for (p, seed): test / debug entry."""
     out = torch.empty((B, H, T, S), dtype=torch.uint8, device=device)

@@ -11,6 +11,7 @@ import math
 import random
 from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -20,7 +21,8 @@ from ._lib import lib
 from .config import ModelConfig
 from .decoder import MAX_BEAM, Decoder, MultiheadAttention, _to_dev, takes_ragged_state
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
-from .evaluation import WINDOW_BATCHES, decode_rows, decode_stream, plan_groups, refill_enabled, refill_option, stream_order
+from .evaluation import (WINDOW_BATCHES, Alignment, cells_and_boxes, decode_rows, decode_stream, grid_of, plan_align_groups, plan_groups, refill_enabled,
+                         refill_option, stream_order)
 from .lightning_shim import LightningModule
 from .metrics import compute_metrics, compute_metrics_sharded
 from .runtime import FlatModuleMixin
@@ -369,6 +371,57 @@ class _Base(FlatModuleMixin, LightningModule):
         return compute_metrics(y_true=truth, y_pred=preds)
 
     @torch.no_grad()
+    def _align(self, items: Iterable, sizes_of: Callable, words, batch_size: int, layers, return_maps: bool) -> List[Alignment]:
+        """`align` of both model classes.  Every input is encoded at batch size 1 (`_encode_input`, like `_predict`); its words
+        come from `_predict` (greedy) unless given; then ONE teacher-forced Decoder.cross_attention_maps pass per group of up to
+        batch_size inputs (evaluation.plan_align_groups: memories padded with zeros to the group's longest behind a bool key
+        mask, targets [<sos>] + ids[:-1] padded with the pad index) gives row t = the distribution of the position that predicts
+        token t, and omr_argmax over the row's own S_b keys (first index on ties) the memory row it leaned on.  sizes_of(item) ->
+        (sizes, split) of evaluation.cells_and_boxes."""
+        was_training = self.training
+        self.eval()
+        try:
+            items = list(items)
+            mems = [self._encode_input(x) for x in items]
+            if words is None:
+                words = self._predict(range(len(mems)), lambda i: mems[i], batch_size)
+            words = [list(w) for w in words]
+            if len(words) != len(items):
+                raise ValueError(f"align: {len(words)} word lists for {len(items)} inputs")
+            ids = [[self.w2i[w] for w in seq] for seq in words]
+            dev, sos, pad = mems[0].device if mems else None, self.w2i[SOS_TOKEN], self.padding_idx
+            out: List[Optional[Alignment]] = [None] * len(items)
+            for group in plan_align_groups([len(s) for s in ids], [m.shape[1] for m in mems], batch_size):
+                group = [i for i in group if ids[i]]               # no tokens: nothing to align (an empty Alignment below)
+                if not group:
+                    continue
+                tmax, smax = max(len(ids[i]) for i in group), max(mems[i].shape[1] for i in group)
+                tgt = torch.full((len(group), tmax), pad, dtype=torch.int64)
+                memory = torch.zeros((len(group), smax, mems[group[0]].shape[2]), dtype=mems[group[0]].dtype, device=dev)
+                lens = torch.tensor([mems[i].shape[1] for i in group], dtype=torch.int64)
+                for b, i in enumerate(group):
+                    tgt[b, :len(ids[i])] = torch.tensor([sos] + ids[i][:-1], dtype=torch.int64)
+                    memory[b, :mems[i].shape[1]] = mems[i][0]
+                mask = None if bool((lens == smax).all()) else _pad_mask(smax, lens.to(dev))
+                with torch.no_grad():
+                    _, maps = self.decoder._cross_attention_maps(tgt.to(dev), memory, mask, layers, False)
+                picks = [K.argmax(maps[b, :len(ids[i]), :mems[i].shape[1]]) for b, i in enumerate(group)]
+                for b, (i, (idx, val)) in enumerate(zip(group, picks)):
+                    sizes, split = sizes_of(items[i])
+                    index = idx.cpu().numpy()
+                    cell, box, source = cells_and_boxes(index, sizes, split)
+                    own = maps[b, :len(ids[i]), :mems[i].shape[1]].contiguous() if return_maps else None
+                    out[i] = Alignment(words=words[i], index=index, weight=val.cpu().numpy(), cell=cell, box=box, source=source, maps=own)
+            for i, a in enumerate(out):
+                if a is None:
+                    cell, box, source = cells_and_boxes([], *sizes_of(items[i]))
+                    out[i] = Alignment(words=words[i], index=np.zeros(0, np.int64), weight=np.zeros(0, np.float32), cell=cell, box=box,
+                                       source=source, maps=None)
+            return out
+        finally:
+            self.train(was_training)
+
+    @torch.no_grad()
     def beam_search(self, memory: torch.Tensor, beam: int = 4) -> Tuple[List[str], float]:
         """Beam-search decode of ONE input (BASELINE config C5; an extension -- the reference only decodes greedily).  The
         `beam` hypotheses are the batch rows of the KV-cached step; scores are sums of log-probabilities (no length
@@ -592,13 +645,26 @@ class Transformer(_Base):
         `refill_option`; greedy only): continuous batching (`_predict`), same metrics."""
         return self._evaluate(batches, lambda batch: batch[0], batch_size)
 
+    modality = "image"        # what this model's one encoder reads ("audio" for an A2S model): the `source` of its alignments
+
+    def align(self, xs: Iterable[torch.Tensor], words: Optional[List[List[str]]] = None, batch_size: int = 32, layers=None,
+              return_maps: bool = False) -> List[Alignment]:
+        """Where the decoder looked: one evaluation.Alignment per input [1, C, H_b, W_b], in input order -- per token of `words`
+        (default: `predict`'s greedy words of that input) the memory row with the largest cross-attention weight (heads and the
+        decoder layers `layers` averaged; default all), its cell of the encoder grid and its box in input pixels (`_align`)."""
+        return self._align(xs, lambda x: (((self.modality, x.shape[-2], x.shape[-1]),), None), words, batch_size, layers, return_maps)
+
 
 ##################################################################### MULTIMODAL TRANSFORMER
 
 
 class CrossAttention(nn.Module):
-    """model.py:268-355.  The attention-weights output of the reference (need_weights=True, discarded by every
-    caller) is not materialised: the second return value is None."""
+    """model.py:268-355.  The attention-weights output of the reference (need_weights=True, discarded by every caller) is
+    materialised on request only: with `need_weights` False (the default) the second return value is None and nothing extra is
+    launched; with True it is the head-averaged map, fp32 [B, len_a, len_b] -- the softmax average in eval, the post-dropout
+    average in training (the words the forward read) -- at the cost of one omr_attn_weights launch."""
+
+    need_weights = False
 
     def __init__(self, feature_dim: int, num_heads: int = 4, dropout: float = 0.1) -> None:
         super().__init__()
@@ -613,8 +679,9 @@ class CrossAttention(nn.Module):
             blk_lq = len_query.to(query.device, torch.int32).contiguous()
             blk_lkv = len_key_value.to(query.device, torch.int32).contiguous()
         kv = self.attention.project_kv(key_value.contiguous())
-        out = self.attention.cross_attention(query.contiguous(), kv, None, self.training, blk_lq, blk_lkv)
-        return out, None
+        weights = {} if self.need_weights else None
+        out = self.attention.cross_attention(query.contiguous(), kv, None, self.training, blk_lq, blk_lkv, weights=weights)
+        return out, (weights["out"] if weights is not None else None)
 
     def forward_key_lengths(self, query, key_value, len_key_value):
         """The attention of `forward` over a ragged batch's packed memories: sample b sees the first len_key_value[b] (int32 [B] on the
@@ -811,6 +878,25 @@ class MultimodalTransformer(_Base):
         batches.  Keyword `beam` (2 .. 8, `_beam_option`): the predictions are those of `beam_search`.  Keyword `refill` (default
         False, `refill_option`; greedy only): continuous batching (`_predict`), same metrics."""
         return self._evaluate(batches, lambda batch: (batch[0], batch[1]), batch_size)
+
+    def align(self, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], words: Optional[List[List[str]]] = None, batch_size: int = 32,
+              layers=None, return_maps: bool = False) -> List[Alignment]:
+        """`Transformer.align` for (image, audio) pairs.  The decoder attends over the MIXED memory: `concat` and `attn_both`
+        concatenate an image-grid part and an audio-grid part, split at the image memory's length -- `source` says which part a
+        token leaned on, and its cell / box are on that input's grid; `attn_img` (queries = audio) leaves the audio grid,
+        `attn_audio` the image grid."""
+        kind = self._mixer_kind
+
+        def sizes_of(pair):
+            img, aud = ("image", pair[0].shape[-2], pair[0].shape[-1]), ("audio", pair[1].shape[-2], pair[1].shape[-1])
+            if kind == "attn_img":
+                return (aud,), None
+            if kind == "attn_audio":
+                return (img,), None
+            gh, gw = grid_of(img[1], img[2])
+            return (img, aud), gh * gw
+
+        return self._align(pairs, sizes_of, words, batch_size, layers, return_maps)
 
     ##### MODALITY MIXERS (model.py:644-726)
 
