@@ -180,6 +180,38 @@ int omr_concat_memory_bwd(int dtype, const void* dout, const int* len_a, int La,
  * B < 1, B > 65535, N < 1, H * W > 2^31 - 1 or a null pointer: OMR_ERR_ARG; any other dtype code: OMR_ERR_UNSUPPORTED. */
 int omr_gather_ragged_batch(int src_dtype, const void* src, const long* offsets, const int* sizes, int N, const int* idx, int dst_dtype,
                             void* out, int B, int H, int W, float pad_value, void* stream);
+/* omr_gather_ragged_batch with a fresh distortion of every sample inside the same launch: what the reference can only offer as a second,
+ * pre-rendered copy of every score (`image_distorted`, src/data/ar_dataset.py:258-265,377) on the way into pad_batch_inputs
+ * (src/data/preprocessing.py:55-75).  aug: B records on the device, record b for batch row b (the same sample may occur twice with
+ * different records).  With n = idx[b], (h, w) = sizes[n] (the SOURCE plane: not clamped to H, W; h * w <= 2^31 - 1) and
+ * (oh, ow) = (out_h, out_w) clamped to [0, H] x [0, W], destination pixel (i, j) of row b is
+ *   pad_value (omr_gather_ragged_batch's rule, NaN included)               for i >= oh or j >= ow;
+ *   conv(fill)                                                             for i in a row band or j in a column band
+ *                                                                          (start <= . < start + length; length <= 0: no band);
+ *   otherwise, every step ONE rounded fp32 operation, no product fused into an add:
+ *   1. y = (m0 * i + m1 * j) + m2, x = (m3 * i + m4 * j) + m5; y = fminf(fmaxf(y, -1), h), x = fminf(fmaxf(x, -1), w) (a NaN becomes -1);
+ *   2. y0 = floorf(y), fy = y - y0, x0 = floorf(x), fx = x - x0;
+ *   3. lerp(v0, v1, f) = f == 0 ? v0 : v0 * (1 - f) + v1 * f (v1 is not read for f == 0);
+ *      g = lerp(lerp(tap(y0, x0), tap(y0, x0 + 1), fx), lerp(tap(y0 + 1, x0), tap(y0 + 1, x0 + 1), fx), fy); a tap is the source element
+ *      as a float (a gray 0 .. 255 for OMR_DTYPE_U8), `fill` outside the plane: only elements of listed samples are read;
+ *   4. g = gain * g + bias unless gain == 1 and bias == 0;
+ *   5. noise != 0: g = g + noise * ((float)(hash32(seed_lo, seed_hi, i * ow + j) >> 8) * 2^-23 - 1), hash32 of csrc/omr_common.h, the
+ *      index in 32-bit unsigned arithmetic;
+ *   6. OMR_DTYPE_U8: g = fminf(fmaxf(g, 0), 255);   7. conv(g): g / 255 by the correctly rounded division (u8), g itself (fp32);
+ *   8. the output type's rounding (omr_cast's).
+ * The identity record (m = 1,0,0, 0,1,0; gain 1, bias 0, noise 0, no bands, out_h, out_w = h, w) gives omr_gather_ragged_batch's bits.
+ * Arguments are checked like omr_gather_ragged_batch's; aug == NULL: OMR_ERR_ARG. */
+typedef struct OmrAugment {
+    float m[6];                 /* source (y, x) of destination pixel (i, j): y = m0*i + m1*j + m2, x = m3*i + m4*j + m5 */
+    float gain, bias;           /* in source units (grays 0..255 for a u8 store, the value itself for f32) */
+    float noise;                /* amplitude in source units, 0 = off */
+    float fill;                 /* value of every tap outside the source plane, and of masked bands (255 = paper, 0 = silence) */
+    int out_h, out_w;           /* extent of the augmented sample in the output plane (clamped to H, W) */
+    unsigned seed_lo, seed_hi;  /* noise stream */
+    int rows[2][2], cols[2][2]; /* up to two row bands and two column bands (start, length); length <= 0 = none */
+} OmrAugment;
+int omr_gather_augmented_batch(int src_dtype, const void* src, const long* offsets, const int* sizes, int N, const int* idx,
+                               const OmrAugment* aug, int dst_dtype, void* out, int B, int H, int W, float pad_value, void* stream);
 
 /* ---- GEMM: C[M,N] (+)= act(opA(A) . opB(B)^T + bias) ------------------------------------------------------ */
 /* aten::linear/addmm/mm of the decoder layers (torch nn/modules/transformer.py:1158-1199), 1x1 point_conv

@@ -11,23 +11,14 @@
 // aligned (a fragment then never crosses a row), else one element.  Source rows start at any element offset (w_n is arbitrary), so
 // the source is loaded element by element -- neighbouring lanes read neighbouring bytes.  Positions inside a sample are 32-bit
 // (H * W <= 2^31 - 1, and h_n * w_n <= H * W after the clamp); only the batch offset and offsets[n] are 64-bit.  Of src exactly the
-// h_n * w_n elements of each listed sample are read.  No LDS, no atomics.
+// h_n * w_n elements of each listed sample are read.  No LDS, no atomics.  (batch_augment.hip: the same launch with a per-sample
+// augmentation; its identity record writes this kernel's bits.)
 #include "omr_common.h"
 #include "omr_hip.h"
 #include "instnorm_slots.h"      // Pack, clampi
+#include "batch_gather.h"        // gather_conv, gather_pad: shared with batch_augment.hip
 
 namespace {
-
-__device__ __forceinline__ float gather_conv(unsigned char v) { return __fdiv_rn((float)v, 255.0f); }
-__device__ __forceinline__ float gather_conv(float v) { return v; }
-// The pad value in the output type.  A NaN pad in bf16 is written as 0xFFFF, the pattern torch's host fp32 -> bf16 conversion writes for
-// every NaN, so that a batch equals the host collate followed by .to(bfloat16) to the bit with a NaN pad as well (a poison value for
-// debugging; what the hardware conversion makes of a NaN is another quiet NaN).  fp32 keeps the caller's bits.
-template <typename T> __device__ __forceinline__ T gather_pad(float v);
-template <> __device__ __forceinline__ float gather_pad<float>(float v) { return v; }
-template <> __device__ __forceinline__ bf16 gather_pad<bf16>(float v) {
-    return v != v ? __builtin_bit_cast(bf16, (unsigned short)0xFFFF) : from_f32<bf16>(v);
-}
 
 template <typename S, typename T, int VEC>
 __global__ __launch_bounds__(256) void gather_ragged_batch_kernel(const S* __restrict__ src, const long* __restrict__ offsets, const int* __restrict__ sizes,

@@ -635,6 +635,34 @@ def gather_ragged_batch(src: Tensor, offsets: Tensor, sizes: Tensor, idx: Tensor
     return out
 
 
+AUGMENT_RECORD_BYTES = 88            # sizeof(OmrAugment) (include/omr_hip.h); augment.AUG_DTYPE is its numpy mirror
+
+
+def gather_augmented_batch(src: Tensor, offsets: Tensor, sizes: Tensor, idx: Tensor, aug: Tensor, H: int, W: int, dtype: torch.dtype,
+                           pad_value: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """`gather_ragged_batch` with one OmrAugment record per batch row (csrc/batch_augment.hip; include/omr_hip.h states the value of
+    every pixel): aug uint8 [B, 88] on src's device, the bytes of `augment.AUG_DTYPE` records.  Row b holds sample idx[b] mapped,
+    blended, scaled and masked by record b inside its extent (out_h, out_w), pad_value outside.  out: write there ([B, 1, H, W])."""
+    require_cuda(src, offsets, sizes, idx, aug)
+    assert src.dim() == 1 and src.is_contiguous() and src.dtype in _GATHER_SRC_CODE, f"expected a flat uint8 / float32 store, got {src.dtype} {tuple(src.shape)}"
+    N = offsets.numel()
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.device == src.device, \
+        f"offsets must be int64 [N] on the device of src, got {offsets.dtype} {tuple(offsets.shape)} on {offsets.device}"
+    assert sizes.dtype == torch.int32 and sizes.is_contiguous() and tuple(sizes.shape) == (N, 2) and sizes.device == src.device, \
+        f"sizes must be int32 [N, 2] on the device of src, got {sizes.dtype} {tuple(sizes.shape)} on {sizes.device}"
+    assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous() and idx.device == src.device, \
+        f"idx must be int32 [B] on the device of src, got {idx.dtype} {tuple(idx.shape)} on {idx.device}"
+    B = idx.numel()
+    assert aug.dtype == torch.uint8 and aug.is_contiguous() and tuple(aug.shape) == (B, AUGMENT_RECORD_BYTES) and aug.device == src.device, \
+        f"aug must be uint8 [B, {AUGMENT_RECORD_BYTES}] on the device of src, got {aug.dtype} {tuple(aug.shape)} on {aug.device}"
+    if out is None:
+        out = torch.empty((B, 1, H, W), dtype=dtype, device=src.device)
+    assert out.is_contiguous() and tuple(out.shape) == (B, 1, H, W) and out.dtype == dtype and out.device == src.device
+    lib().call("omr_gather_augmented_batch", _GATHER_SRC_CODE[src.dtype], ptr(src), ptr(offsets), ptr(sizes), N, ptr(idx), ptr(aug), dtype_code(dtype),
+               ptr(out), B, H, W, float(pad_value), cur_stream())
+    return out
+
+
 def add_layernorm_fwd(x: Tensor, res: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float = 1e-5, drop_p: float = 0.0, drop_seed: int = 0):
     """LayerNorm(dropout(x) + res); drop_p = 0 is the plain residual add."""
     require_cuda(x, res, gamma, beta)

@@ -8,7 +8,7 @@ compute dtype.  What comes out is, to the bit, what `image.collate_ragged` / `co
 the `(x, sizes)` pairs of the ragged route of `Transformer.training_step` and `MultimodalTransformer.training_step`.
 
   ResidentStore      the packed buffer of one modality: append / freeze / gather
-  ResidentDataset    one or two stores plus the host token lists: batch(indices, dtype), eval_batches()
+  ResidentDataset    one or two stores plus the host token lists: batch(indices, dtype, records=None), eval_batches()
   plan_batches       which samples share a batch: shuffle, sort chunks by size, cut under a padded-pixel / padded-token budget
   shard_batches      the plan's batches of one rank; padded_ratio: real / padded pixels of a plan
   ResidentLoader     the training loader over a ResidentDataset (set_epoch / __len__ / __iter__: what lightning_shim.Trainer.fit uses)
@@ -18,9 +18,10 @@ from __future__ import annotations
 
 from typing import Iterator, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
-from . import kernels
+from . import augment, kernels
 
 Tensor = torch.Tensor
 
@@ -107,20 +108,36 @@ class ResidentStore:
             self._tables = (off, self.sizes.to(torch.int32).to(self.device))
         return self
 
-    def gather(self, indices: Sequence[int], dtype: torch.dtype, pad_value: float = 0.0) -> Tuple[Tensor, Tensor]:
+    def gather(self, indices: Sequence[int], dtype: torch.dtype, pad_value: float = 0.0, records=None) -> Tuple[Tensor, Tensor]:
         """-> (x [B, 1, Hmax, Wmax] in `dtype` on the device: sample indices[b] in the top-left corner of plane b, pad_value elsewhere;
         sizes int64 [B, 2] on the host): `image.collate_ragged` of those samples (pad 0).  The plane is the maximum over the batch,
-        taken from the host table: no device read-back; the index list goes up non-blocking from pinned memory."""
+        taken from the host table: no device read-back; the index list goes up non-blocking from pinned memory.
+
+        records: `augment.AUG_DTYPE` [B], one per index -- the batch is built by `omr_gather_augmented_batch` instead: row b is sample
+        indices[b] under record b, the plane is the maximum of the records' extents and `sizes` ARE those extents (what the ragged
+        route has to be told).  The records go up like the index list."""
         idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
         if idx.numel() == 0:
             raise ValueError("gather needs at least one index")
         if int(idx.min()) < 0 or int(idx.max()) >= len(self):
             raise IndexError(f"sample index out of range [0, {len(self)})")
         off, sizes_dev = self.freeze()._tables
-        sizes = self.sizes[idx]
-        H, W = int(sizes[:, 0].max()), int(sizes[:, 1].max())
         idx_dev = idx.to(torch.int32).pin_memory().to(self.device, non_blocking=True)
-        x = kernels.gather_ragged_batch(self.buf, off, sizes_dev, idx_dev, H, W, dtype, pad_value)
+        if records is None:
+            sizes = self.sizes[idx]
+            H, W = int(sizes[:, 0].max()), int(sizes[:, 1].max())
+            x = kernels.gather_ragged_batch(self.buf, off, sizes_dev, idx_dev, H, W, dtype, pad_value)
+            return x, sizes
+        records = np.ascontiguousarray(np.asarray(records).reshape(-1))
+        if records.dtype != augment.AUG_DTYPE or records.shape[0] != idx.numel():
+            raise ValueError(f"records must be augment.AUG_DTYPE [{idx.numel()}], got {records.dtype} {records.shape}")
+        sizes = torch.from_numpy(augment.extents(records))
+        if int(sizes.min()) < 1:
+            raise ValueError("a record's extent (out_h, out_w) must be at least 1 x 1")
+        H, W = int(sizes[:, 0].max()), int(sizes[:, 1].max())
+        raw = torch.from_numpy(records.view(np.uint8).reshape(idx.numel(), augment.AUG_DTYPE.itemsize))
+        aug_dev = raw.pin_memory().to(self.device, non_blocking=True)
+        x = kernels.gather_augmented_batch(self.buf, off, sizes_dev, idx_dev, aug_dev, H, W, dtype, pad_value)
         return x, sizes
 
 
@@ -158,14 +175,25 @@ class ResidentDataset:
         """Decoder positions per sample: len(y) - 1, the length of y_in and of y_out."""
         return [int(t.numel()) - 1 for t in self.targets]
 
-    def batch(self, indices: Sequence[int], dtype: torch.dtype):
+    def batch(self, indices: Sequence[int], dtype: torch.dtype, records=None):
         """-> (x, sizes, y_in, y_out) for one store, (xi, sizes_i, xa, sizes_a, y_in, y_out) for two: the ragged batch forms of
         `Transformer.training_step` / `MultimodalTransformer.training_step`.  y_in = y[:-1], y_out = y[1:], padded with 0 to the
-        batch's longest target, int64 on the host (`pad_batch_transcripts`, preprocessing.py:78-82)."""
+        batch's longest target, int64 on the host (`pad_batch_transcripts`, preprocessing.py:78-82).
+
+        records: per STORE -- a sequence of len(stores) entries, each `augment.AUG_DTYPE` [B] or None (that store is gathered
+        plainly); with one store the array itself will do.  The sizes returned for an augmented store are its records' extents."""
         indices = [int(i) for i in indices]
+        if records is None:
+            per_store = [None] * len(self.stores)
+        elif isinstance(records, np.ndarray):
+            per_store = [records]
+        else:
+            per_store = list(records)
+        if len(per_store) != len(self.stores):
+            raise ValueError(f"records for {len(per_store)} stores, the data set has {len(self.stores)}")
         out = []
-        for s in self.stores:
-            out.extend(s.gather(indices, dtype))
+        for s, r in zip(self.stores, per_store):
+            out.extend(s.gather(indices, dtype) if r is None else s.gather(indices, dtype, records=r))
         ys = [self.targets[i] for i in indices]
         T = max(int(y.numel()) for y in ys) - 1
         y_in = torch.zeros((len(ys), T), dtype=torch.int64)
@@ -272,13 +300,17 @@ class ResidentLoader:
     `dataset.batch(indices, dtype)` per step -- no host pixel work between two steps.  `lightning_shim.Trainer.fit` calls
     `set_epoch(e)` and passes the device floats and the host integer tensors through as they are.
 
+    augment / augment2 (`augment.ImageAugment`, `augment.SpecAugment` or anything with their `draw`): per-sample augmentation of the
+    first / second store inside the gather, drawn afresh every epoch from plan_kwargs["seed"]; each batch carries its samples'
+    records and its sizes are the augmented extents.  Both None: nothing new is launched, the loader is what it was.
+
     Data parallel: the batches of a plan differ in their number of tokens.  Each rank's loss is the mean over ITS batch's tokens
     and the gradient all-reduce averages the ranks' means, so a token of a short batch weighs more than one of a long batch in the
     same step (with equal-sized random batches the weights only differ by the targets' lengths).  Reweighting by token counts is
     not done."""
 
     def __init__(self, dataset: ResidentDataset, batch_size: int, dtype: torch.dtype, *, rank: Optional[int] = None, world: Optional[int] = None,
-                 **plan_kwargs):
+                 augment=None, augment2=None, **plan_kwargs):
         import torch.distributed as dist
         init = dist.is_available() and dist.is_initialized()
         self.dataset, self.batch_size, self.dtype = dataset, batch_size, dtype
@@ -287,18 +319,35 @@ class ResidentLoader:
         unknown = set(plan_kwargs) - {"max_padded_pixels", "max_padded_tokens", "chunk_batches", "seed"}
         if unknown:
             raise TypeError(f"unexpected plan arguments {sorted(unknown)}")
+        if augment2 is not None and len(dataset.stores) < 2:
+            raise ValueError("augment2 is for the second store; the data set has one")
         self.plan_kwargs = plan_kwargs
+        self.augments = [augment, augment2][:len(dataset.stores)]           # the arguments (in here `augment` is not the module)
         self.epoch = 0
         self._cached = None
+        self._records = None                # (epoch, [AUG_DTYPE [N] or None per store])
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
 
+    def records(self) -> List[Optional[np.ndarray]]:
+        """Per store: the records [N] of the current epoch (`augment.draw_all` with the plan's seed), None for a store without
+        augmentation.  Record n depends on (seed, epoch, n, h_n, w_n) alone, so every rank holds the same table."""
+        if self._records is None or self._records[0] != self.epoch:
+            seed = self.plan_kwargs.get("seed", 0)
+            self._records = (self.epoch, [None if a is None else augment.draw_all(a, seed, self.epoch, s.sizes)
+                                          for a, s in zip(self.augments, self.dataset.stores)])
+        return self._records[1]
+
     def plan(self) -> List[List[int]]:
-        """This rank's batches of the current epoch."""
+        """This rank's batches of the current epoch.  With augmentation the plan is made on the AUGMENTED sizes of that epoch: the
+        padded-pixel budget holds for the planes that are actually built."""
         if self._cached is None or self._cached[0] != self.epoch:
             stores = self.dataset.stores
-            full = plan_batches(stores[0].sizes, self.batch_size, sizes2=stores[1].sizes if len(stores) > 1 else None,
+            sizes = [s.sizes for s in stores]
+            if any(a is not None for a in self.augments):
+                sizes = [s if r is None else torch.from_numpy(augment.extents(r)) for s, r in zip(sizes, self.records())]
+            full = plan_batches(sizes[0], self.batch_size, sizes2=sizes[1] if len(stores) > 1 else None,
                                 target_lens=self.dataset.target_lens(), epoch=self.epoch, **self.plan_kwargs)
             self._cached = (self.epoch, shard_batches(full, self.rank, self.world))
         return self._cached[1]
@@ -307,5 +356,10 @@ class ResidentLoader:
         return len(self.plan())
 
     def __iter__(self):
-        for indices in self.plan():
-            yield self.dataset.batch(indices, self.dtype)
+        if all(a is None for a in self.augments):
+            for indices in self.plan():
+                yield self.dataset.batch(indices, self.dtype)
+            return
+        plan, records = self.plan(), self.records()
+        for indices in plan:
+            yield self.dataset.batch(indices, self.dtype, records=[None if r is None else r[indices] for r in records])
