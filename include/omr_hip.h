@@ -591,6 +591,19 @@ int omr_ce_fwd(int dtype, const void* logits, const long* target, float* lse, do
 /* grad_out (nullable): device pointer to the upstream scalar gradient dL/dloss (multiplies grad_scale). */
 int omr_ce_bwd(int dtype, const void* logits, const long* target, const float* lse, const double* acc2, void* dlogits, long M, int V,
                long ldv, int pad_idx, float grad_scale, const float* grad_out, void* stream);
+/* The same loss (model.py:109,166) with torch's label_smoothing = eps in [0, 1] (an extension: the reference trains with 0).  A row is
+ * live when its target is not pad and lies in [0, V).  Per live row, with S = sum of the row's logits over the columns < V:
+ *   objective = lse - (1 - eps) * logit[target] - (eps / V) * S,      nll = lse - logit[target].
+ * loss_out = mean objective, nll_out = mean nll (both fp32 [1]), acc3 = {objective sum, live rows, nll sum} (fp64), rowsum = S (fp32 [M],
+ * summed in a fixed order in the pass that computes lse).  A live row that holds -inf has objective +inf, as in torch.
+ * eps == 0 runs the kernels of omr_ce_fwd: loss_out, lse and acc3[0..1] have its bits, nll_out = loss_out, rowsum is not written (may be
+ * NULL).  eps outside [0, 1] (NaN included): OMR_ERR_ARG before any launch. */
+int omr_ce_smooth_fwd(int dtype, const void* logits, const long* target, float* lse, float* rowsum, double* acc3, float* loss_out,
+                      float* nll_out, long M, int V, long ldv, int pad_idx, float eps, void* stream);
+/* dlogits = (softmax - (1 - eps) * onehot - eps / V) * grad_scale * grad_out / acc3[1] on live rows, +0 on the others and in the columns
+ * >= V (model.py:109,166).  eps == 0 runs the kernel of omr_ce_bwd.  acc3: only the live-row count acc3[1] is read. */
+int omr_ce_smooth_bwd(int dtype, const void* logits, const long* target, const float* lse, const double* acc3, void* dlogits, long M, int V,
+                      long ldv, int pad_idx, float eps, float grad_scale, const float* grad_out, void* stream);
 
 /* ---- guarded optimizer step ------------------------------------------------------------------------------- */
 /* What the reference gets from Lightning: Trainer(precision="16-mixed") (src/train.py:153) puts every step behind GradScaler,

@@ -22,6 +22,7 @@ class ModelConfig:
     encoder_dropout: float = 0.5  # encoder.py:251
     compute_dtype: str = "fp32"   # "fp32" (parity mode) or "bf16" (fp32 master weights + Adam)
     fp8_decode: bool = False      # BASELINE config 5 (extension): greedy / beam decode with fp8 (e4m3) MFMA weights in the decoder
+    label_smoothing: float = 0.0  # extension: CrossEntropyLoss(label_smoothing=...) in training, torch's definition and range [0, 1]
 
     def to_dict(self) -> Dict[str, Any]:
         return asdict(self)

@@ -637,12 +637,41 @@ class CrossEntropyFn(Function):
         return dl, None, None, None
 
 
-def cross_entropy(logits_bvt: Tensor, target_bt: Tensor, pad_idx: int) -> Tensor:
+class SmoothCrossEntropyFn(Function):
+    """CrossEntropyFn with torch's label_smoothing = eps > 0 -> (loss, nll): the mean smoothed objective, and the mean un-smoothed
+    lse - logit[target] of the same rows as a second output that carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits2d, target, V, pad_idx, eps):
+        loss, nll, lse, _rowsum, acc3 = K.ce_smooth_fwd(logits2d, target, V, pad_idx, eps)
+        ctx.cfg = (V, pad_idx, eps)
+        ctx.save_for_backward(logits2d, target, lse, acc3)   # the row sums only feed the forward's objective: backward needs eps alone
+        nll = nll.view(())
+        ctx.mark_non_differentiable(nll)
+        return loss.view(()), nll
+
+    @staticmethod
+    def backward(ctx, g, _g_nll):
+        V, pad_idx, eps = ctx.cfg
+        logits2d, target, lse, acc3 = ctx.saved_tensors
+        dl = K.ce_smooth_bwd(logits2d, target, lse, acc3, V, pad_idx, eps, grad_out=g)
+        return dl, None, None, None, None
+
+
+def cross_entropy(logits_bvt: Tensor, target_bt: Tensor, pad_idx: int, label_smoothing: float = 0.0, return_nll: bool = False):
     """Loss on logits in the reference's [B, V, T] layout.  The decoder produces them as a stride
-    permutation of row-major [B*T, V], which is what the kernel consumes (no copy)."""
+    permutation of row-major [B*T, V], which is what the kernel consumes (no copy).
+    label_smoothing: torch's argument of that name, in [0, 1]; 0 (the reference) runs exactly the unsmoothed kernels.
+    return_nll: also return the un-smoothed mean of the same rows (no gradient; with label_smoothing = 0 it is the loss, detached)."""
+    eps = K.check_label_smoothing(label_smoothing)
     B, V, T = logits_bvt.shape
     rows = logits_bvt.permute(0, 2, 1)
     if rows.stride(2) != 1 or rows.stride(1) % 8 or rows.stride(0) != T * rows.stride(1):
         rows = rows.contiguous()
     l2 = rows.reshape(B * T, V)   # a view: rows of one batch follow each other at the same pitch
-    return CrossEntropyFn.apply(l2, target_bt.reshape(-1).contiguous(), V, pad_idx)
+    if eps > 0:
+        loss, nll = SmoothCrossEntropyFn.apply(l2, target_bt.reshape(-1).contiguous(), V, pad_idx, eps)
+    else:
+        loss = CrossEntropyFn.apply(l2, target_bt.reshape(-1).contiguous(), V, pad_idx)
+        nll = loss.detach()
+    return (loss, nll) if return_nll else loss

@@ -1020,5 +1020,45 @@ def ce_bwd(logits2d: Tensor, target: Tensor, lse: Tensor, acc2: Tensor, V: int, 
     return dl[:, :cols]
 
 
+def check_label_smoothing(eps) -> float:
+    """torch's range for label_smoothing; refused here, before anything is allocated or launched."""
+    eps = float(eps)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must be between 0.0 and 1.0, got {eps}")
+    return eps
+
+
+def ce_smooth_fwd(logits2d: Tensor, target: Tensor, V: int, pad_idx: int, eps: float):
+    """ce_fwd with label smoothing eps in [0, 1] -> (loss fp32 [1], nll fp32 [1], lse [M], rowsum [M] or None, acc3 fp64 [3]).
+    loss is the mean smoothed objective, nll the mean un-smoothed lse - logit[target], rowsum the per-row sum of the logits over the
+    columns < V, acc3 = {objective sum, live rows, nll sum}.  eps == 0 runs ce_fwd's kernels (same bits) and has no rowsum."""
+    eps = check_label_smoothing(eps)
+    require_cuda(logits2d, target)
+    M, cols, ldv = _rows2d(logits2d)
+    assert cols >= V and target.numel() == M and target.dtype == torch.int64 and target.is_contiguous()
+    dev = logits2d.device
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    rowsum = torch.empty(M, dtype=torch.float32, device=dev) if eps > 0 else None
+    acc3 = torch.empty(3, dtype=torch.float64, device=dev)
+    means = torch.empty(2, dtype=torch.float32, device=dev)
+    lib().call("omr_ce_smooth_fwd", dtype_code(logits2d.dtype), ptr(logits2d), ptr(target), ptr(lse), ptr(rowsum), ptr(acc3), ptr(means),
+               means.data_ptr() + 4, M, V, ldv, pad_idx, eps, cur_stream())
+    return means[:1], means[1:], lse, rowsum, acc3
+
+
+def ce_smooth_bwd(logits2d: Tensor, target: Tensor, lse: Tensor, acc3: Tensor, V: int, pad_idx: int, eps: float, grad_scale: float = 1.0,
+                  grad_out: Optional[Tensor] = None) -> Tensor:
+    """ce_bwd with label smoothing eps: (softmax - (1 - eps) onehot - eps / V) * grad_scale * grad_out / count.  eps == 0 runs ce_bwd's kernel."""
+    eps = check_label_smoothing(eps)
+    require_cuda(logits2d, target, grad_out)
+    if grad_out is not None:
+        assert grad_out.dtype == torch.float32 and grad_out.numel() == 1
+    M, cols, ldv = _rows2d(logits2d)
+    dl = torch.empty((M, ldv), dtype=logits2d.dtype, device=logits2d.device)
+    lib().call("omr_ce_smooth_bwd", dtype_code(logits2d.dtype), ptr(logits2d), ptr(target), ptr(lse), ptr(acc3), ptr(dl), M, V, ldv, pad_idx, eps,
+               float(grad_scale), ptr(grad_out), cur_stream())
+    return dl[:, :cols]
+
+
 def round_up(n: int, m: int) -> int:
     return (n + m - 1) // m * m

@@ -74,14 +74,21 @@ def _flatten_memory(x: torch.Tensor) -> torch.Tensor:
 
 
 class CrossEntropyLoss(nn.Module):
-    """CrossEntropyLoss(ignore_index) on [B, V, T] logits (model.py:109,166) through the HIP CE kernels."""
+    """CrossEntropyLoss(ignore_index) on [B, V, T] logits (model.py:109,166) through the HIP CE kernels.
+    label_smoothing: torch's argument of that name and range (the reference leaves it at 0).  After a forward `last_nll` holds the
+    un-smoothed mean of the same rows, a detached device scalar (no sync): the figure runs with different smoothing share."""
 
-    def __init__(self, ignore_index: int = 0):
+    def __init__(self, ignore_index: int = 0, label_smoothing: float = 0.0):
         super().__init__()
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f"label_smoothing must be between 0.0 and 1.0, got {label_smoothing}")
         self.ignore_index = ignore_index
+        self.label_smoothing = float(label_smoothing)
+        self.last_nll: Optional[torch.Tensor] = None
 
     def forward(self, logits_bvt: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        return Fn.cross_entropy(logits_bvt, target, self.ignore_index)
+        loss, self.last_nll = Fn.cross_entropy(logits_bvt, target, self.ignore_index, self.label_smoothing, return_nll=True)
+        return loss
 
 
 def _is_pixel_sizes(xl) -> bool:
@@ -143,7 +150,7 @@ class _Base(FlatModuleMixin, LightningModule):
         self.max_seq_len = max_seq_len
         self.teacher_forcing_prob = teacher_forcing_prob
         self.attn_window = attn_window
-        self.compute_loss = CrossEntropyLoss(ignore_index=self.padding_idx)
+        self.compute_loss = CrossEntropyLoss(ignore_index=self.padding_idx, label_smoothing=self.config.label_smoothing)
         self.Y: List[List[str]] = []
         self.YHat: List[List[str]] = []
 
@@ -598,6 +605,8 @@ class Transformer(_Base):
         yhat = self.forward(x=x, xl=xl, y_in=y_in)
         loss = self.compute_loss(yhat, _to_dev(y_out, yhat.device))
         self.log("train_loss", loss, prog_bar=True, logger=True, on_epoch=True)
+        if self.compute_loss.label_smoothing > 0:      # the un-smoothed mean: comparable between runs that smooth differently
+            self.log("train_nll", self.compute_loss.last_nll, prog_bar=True, logger=True, on_epoch=True)
         return loss
 
     @torch.no_grad()
@@ -843,6 +852,8 @@ class MultimodalTransformer(_Base):
         yhat = self.forward(xi=xi, xli=xli, xa=xa, xla=xla, y_in=y_in, apply_teacher_forcing_modality=True)
         loss = self.compute_loss(yhat, _to_dev(y_out, yhat.device))
         self.log("train_loss", loss, prog_bar=True, logger=True, on_epoch=True)
+        if self.compute_loss.label_smoothing > 0:      # the un-smoothed mean: comparable between runs that smooth differently
+            self.log("train_nll", self.compute_loss.last_nll, prog_bar=True, logger=True, on_epoch=True)
         return loss
 
     @torch.no_grad()
