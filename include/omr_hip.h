@@ -652,6 +652,33 @@ int omr_grad_norm(const float* g, long n, const long* range_begin, const long* r
 int omr_adam_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2,
                      float eps, float grad_scale, const omr_step_ctl* ctl, void* stream);
 
+/* ---- optimizer recipe in the step kernel (csrc/optim.hip): decoupled weight decay, EMA weights ----
+ * An extension: the reference trains with torch.optim.Adam(lr=1e-4) alone (model.py:134-139).  The definitions are torch's:
+ * optim/adamw.py single-tensor math (param.mul_(1 - lr * weight_decay) in front of the Adam update) and optim/swa_utils.py
+ * get_ema_multi_avg_fn (ema = d ema + (1 - d) p after the update).  ONE launch over n elements, per element, every rounded fp32
+ * operation named:
+ *   gi    = (g[i] * grad_scale) * clip            clip = ctl->clip, or 1.0f when ctl == NULL
+ *   p'    = p[i] * f                              f = (float)(1.0 - (double)lr * (double)weight_decay), formed on the host; ONLY
+ *                                                 where weight_decay != 0 and the element's block decays -- elsewhere p' = p[i]
+ *                                                 and no multiply touches it
+ *   m, v, denom, p_new = fma(-lr/bc1, m / denom, p')   exactly omr_adam's four roundings (csrc/adam_update.h)
+ *   ema_new = fma(d, ema[i], omd * p_new)         only when ema != NULL; d = ema_decay, omd = (float)(1.0 - (double)ema_decay).
+ *                                                 d = 0 leaves p_new's bits in ema, d = 1 leaves ema's bits (signed zeros aside)
+ *   p_bf16[i] = (bf16)p_new                       only when p_bf16 != NULL
+ * decay_blocks (nullable: every element decays): one byte per 64 elements, byte k for elements [64 k, 64 k + 64) counted from
+ * p; non-zero = decays; ceil(n / 64) bytes are read.  With ctl != NULL and ctl->apply == 0 the launch writes NOTHING: p, m, v,
+ * p_bf16 and ema keep their bits.  With weight_decay == 0, ema == NULL the results are omr_adam's (ctl == NULL) or
+ * omr_adam_guarded's bit for bit.  16-byte loads and stores with a scalar tail: any n >= 1, but p, g, m, v, p_bf16 and ema
+ * must be 16-byte aligned (ctl: 8); anything else, step < 1 or an ema_decay outside [0, 1] is refused with OMR_ERR_ARG.
+ * Error against exact arithmetic on the same inputs, u = 2^-24: omr_adam's bound plus one rounding of p for the decay;
+ * |ema_new - exact| <= 2 u max(|ema|, |p_new|) per step on top of what p_new carries. */
+int omr_adamw_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, const unsigned char* decay_blocks, long n,
+                  int step, float lr, float b1, float b2, float eps, float weight_decay, float ema_decay, float grad_scale,
+                  const omr_step_ctl* ctl, void* stream);
+/* Exchange two fp32 buffers in place (16-byte vectors, scalar tail): the EMA weights go in for evaluation and come out again
+ * without a third buffer.  a, b: 16-byte aligned; ranges that overlap (a == b included) are refused with OMR_ERR_ARG. */
+int omr_swap_f32(float* a, float* b, long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,9 +128,127 @@ __global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restri
         adam_update(p, m, v, p_lp, i, (g[i] * gscale) * clip, lr_over_bc1, b1, b2, eps, inv_sqrt_bc2);
 }
 
+// ---------------------------------------------------------------- AdamW + EMA in one pass (omr_adamw_ema)
+// The optimizer recipe around adam_update's four roundings (adam_update.h: adam_update_reg, ema_update): decoupled weight decay in
+// front, the exponential moving average of the new weights behind, the guard's record obeyed as in adam_guarded_kernel.
+// A pure streaming kernel: 16-byte loads and stores, four elements per thread per trip (g, p, m, v [, ema] in; p, m, v [, ema]
+// and 8 bytes of bf16 out), a grid-stride loop, no LDS, no atomics; the last n % 4 elements take the same update one at a time.
+// decay_blocks: one byte per AW_BLOCK_ELEMS elements, relative to p; a thread's four elements share a byte (4 | 64).
+// A block that does not decay takes p' = p through a select -- no multiply touches it -- so its bits are omr_adam's.
+constexpr int AW_THREADS = 256;
+constexpr int AW_MAX_GRID = 2048;                      // as omr_adam_guarded: 256 CUs x 8 workgroups
+constexpr int AW_BLOCK_SHIFT = 6;                      // 64 elements per decay byte (params.ALIGN)
+
+struct AwArgs {                                        // by value in the kernel arguments
+    float lr_over_bc1, b1, b2, eps, inv_sqrt_bc2, gscale;
+    float decay_f;                                     // (float)(1 - lr wd)
+    float ema_d, ema_omd;                              // (float)d, (float)(1 - d)
+};
+
+template <bool DECAY, bool EMA>
+__global__ __launch_bounds__(AW_THREADS) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, bf16* __restrict__ p_lp, float* __restrict__ ema,
+                                                              const unsigned char* __restrict__ decay_blocks, long n, AwArgs a,
+                                                              const omr_step_ctl* __restrict__ ctl) {
+    float clip = 1.0f;
+    if (ctl) {                                                           // uniform loads; a skipped step leaves before any access
+        if (ctl->apply == 0) return;
+        clip = ctl->clip;
+    }
+    const long gid = blockIdx.x * (long)AW_THREADS + threadIdx.x, stride = (long)gridDim.x * AW_THREADS;
+    const long nvec = n >> 2;
+    for (long j = gid; j < nvec; j += stride) {
+        const long i = j << 2;
+        const f32x4 g4 = *reinterpret_cast<const f32x4*>(g + i);
+        f32x4 p4 = *reinterpret_cast<const f32x4*>(p + i);
+        f32x4 m4 = *reinterpret_cast<const f32x4*>(m + i);
+        f32x4 v4 = *reinterpret_cast<const f32x4*>(v + i);
+        f32x4 e4;
+        if (EMA) e4 = *reinterpret_cast<const f32x4*>(ema + i);
+        bool dec = DECAY;
+        if (DECAY && decay_blocks) dec = decay_blocks[i >> AW_BLOCK_SHIFT] != 0;
+        bf16x4 lp4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float pi = p4[c], mi = m4[c], vi = v4[c];
+            if (DECAY) pi = dec ? pi * a.decay_f : pi;
+            adam_update_reg(pi, mi, vi, (g4[c] * a.gscale) * clip, a.lr_over_bc1, a.b1, a.b2, a.eps, a.inv_sqrt_bc2);
+            p4[c] = pi; m4[c] = mi; v4[c] = vi;
+            lp4[c] = (bf16)pi;
+            if (EMA) e4[c] = ema_update(e4[c], pi, a.ema_d, a.ema_omd);
+        }
+        *reinterpret_cast<f32x4*>(p + i) = p4;
+        *reinterpret_cast<f32x4*>(m + i) = m4;
+        *reinterpret_cast<f32x4*>(v + i) = v4;
+        if (EMA) *reinterpret_cast<f32x4*>(ema + i) = e4;
+        if (p_lp) *reinterpret_cast<bf16x4*>(p_lp + i) = lp4;
+    }
+    for (long i = (nvec << 2) + gid; i < n; i += stride) {               // at most three elements, on the grid's first threads
+        float pi = p[i], mi = m[i], vi = v[i];
+        if (DECAY && (!decay_blocks || decay_blocks[i >> AW_BLOCK_SHIFT] != 0)) pi = pi * a.decay_f;
+        adam_update_reg(pi, mi, vi, (g[i] * a.gscale) * clip, a.lr_over_bc1, a.b1, a.b2, a.eps, a.inv_sqrt_bc2);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        if (p_lp) p_lp[i] = (bf16)pi;
+        if (EMA) ema[i] = ema_update(ema[i], pi, a.ema_d, a.ema_omd);
+    }
+}
+
+__global__ __launch_bounds__(AW_THREADS) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+    const long gid = blockIdx.x * (long)AW_THREADS + threadIdx.x, stride = (long)gridDim.x * AW_THREADS;
+    const long nvec = n >> 2;
+    for (long j = gid; j < nvec; j += stride) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a + (j << 2));
+        const f32x4 y = *reinterpret_cast<const f32x4*>(b + (j << 2));
+        *reinterpret_cast<f32x4*>(a + (j << 2)) = y;
+        *reinterpret_cast<f32x4*>(b + (j << 2)) = x;
+    }
+    for (long i = (nvec << 2) + gid; i < n; i += stride) { const float x = a[i]; a[i] = b[i]; b[i] = x; }
+}
+
+inline int aw_grid(long n) {
+    const long blocks = ((n >> 2) + AW_THREADS - 1) / AW_THREADS;
+    return (int)(blocks < 1 ? 1 : (blocks > AW_MAX_GRID ? AW_MAX_GRID : blocks));
+}
+
 inline long gn_slots(long len) { return (len + GN_CHUNK - 1) / GN_CHUNK; }
 
 }  // namespace
+
+extern "C" int omr_adamw_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, const unsigned char* decay_blocks, long n,
+                             int step, float lr, float b1, float b2, float eps, float weight_decay, float ema_decay, float grad_scale,
+                             const omr_step_ctl* ctl, void* stream) {
+    if (n <= 0) return OMR_OK;
+    if (step < 1 || !p || !g || !m || !v) return OMR_ERR_ARG;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)p_bf16 | (uintptr_t)ema) & 15) || ((uintptr_t)ctl & 7))
+        return OMR_ERR_ARG;
+    if (ema && !(ema_decay >= 0.f && ema_decay <= 1.f)) return OMR_ERR_ARG;
+    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    AwArgs a;
+    a.lr_over_bc1 = (float)(lr / bc1); a.b1 = b1; a.b2 = b2; a.eps = eps; a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2)); a.gscale = grad_scale;
+    a.decay_f = (float)(1.0 - (double)lr * (double)weight_decay);
+    a.ema_d = ema_decay; a.ema_omd = (float)(1.0 - (double)ema_decay);
+    const bool decay = weight_decay != 0.f;
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = aw_grid(n);
+#define AW_LAUNCH(D, E)                                                                                                          \
+    hipLaunchKernelGGL((adamw_ema_kernel<D, E>), grid, AW_THREADS, 0, s, p, g, m, v, (bf16*)p_bf16, ema, decay_blocks, n, a, ctl)
+    if (decay && ema) AW_LAUNCH(true, true);
+    else if (decay) AW_LAUNCH(true, false);
+    else if (ema) AW_LAUNCH(false, true);
+    else AW_LAUNCH(false, false);
+#undef AW_LAUNCH
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+extern "C" int omr_swap_f32(float* a, float* b, long n, void* stream) {
+    if (n <= 0) return OMR_OK;
+    if (!a || !b || (((uintptr_t)a | (uintptr_t)b) & 15)) return OMR_ERR_ARG;
+    if (a < b + n && b < a + n) return OMR_ERR_ARG;                      // overlap (a == b included)
+    hipLaunchKernelGGL(swap_f32_kernel, aw_grid(n), AW_THREADS, 0, (hipStream_t)stream, a, b, n);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
 
 extern "C" long omr_grad_norm_workspace_bytes(long n, int n_ranges) {
     if (n < 1 || n_ranges < 1 || n_ranges > GN_MAXR) return OMR_ERR_ARG;

@@ -46,13 +46,13 @@ class GradReducer:
         self.shared_rng = None            # random.Random every rank seeds with rank 0's value (broadcast_state): rank-proof host decisions
 
     def broadcast_state(self) -> None:
-        """Rank 0's master parameters (and Adam moments, if an optimizer exists already) to every rank, then refresh the bf16
-        compute copy: what DistributedDataParallel does at construction, so replicas are equal whatever each rank seeded or
-        loaded."""
+        """Rank 0's master parameters (and Adam moments and EMA weights, if an optimizer exists already and keeps them) to every
+        rank, then refresh the bf16 compute copy: what DistributedDataParallel does at construction, so replicas are equal
+        whatever each rank seeded or loaded."""
         if self.world == 1:
             return
         src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
-        for t in (self.flat.master, self.flat.exp_avg, self.flat.exp_avg_sq):
+        for t in (self.flat.master, self.flat.exp_avg, self.flat.exp_avg_sq, getattr(self.flat, "ema", None)):
             if t is not None:
                 dist.broadcast(t, src=src, group=self.group)
         self.flat.sync_lowp()

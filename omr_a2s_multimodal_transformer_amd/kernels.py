@@ -378,6 +378,36 @@ def adam_step_guarded(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr:
                cur_stream())
 
 
+DECAY_BLOCK = 64        # elements per byte of omr_adamw_ema's decay_blocks (= params.ALIGN)
+
+
+def adamw_ema_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                   grad_scale: float = 1.0, p_lowp: Optional[Tensor] = None, *, weight_decay: float = 0.0, decay_blocks: Optional[Tensor] = None,
+                   ema: Optional[Tensor] = None, ema_decay: float = 0.0, ctl: Optional[Tensor] = None) -> None:
+    """adam_step / adam_step_guarded (ctl given) with decoupled weight decay in front and the EMA of the new weights behind, in one
+    launch (omr_adamw_ema).  decay_blocks: uint8, one byte per DECAY_BLOCK elements counted from p[0] (None: every element decays);
+    ema: fp32 like p (None: no average)."""
+    require_cuda(p, g, m, v, p_lowp, decay_blocks, ema, ctl)
+    n = p.numel()
+    for t in (p, g, m, v) + (() if ema is None else (ema,)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    if p_lowp is not None:
+        assert p_lowp.dtype == torch.bfloat16 and p_lowp.numel() == n
+    if decay_blocks is not None:
+        assert decay_blocks.dtype == torch.uint8 and decay_blocks.is_contiguous() and decay_blocks.numel() >= (n + DECAY_BLOCK - 1) // DECAY_BLOCK
+    if ctl is not None:
+        assert ctl.numel() * ctl.element_size() == ctypes.sizeof(StepCtl)
+    lib().call("omr_adamw_ema", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_lowp), ptr(ema), ptr(decay_blocks), n, step, lr, betas[0], betas[1], eps,
+               weight_decay, ema_decay, grad_scale, ptr(ctl), cur_stream())
+
+
+def swap_f32(a: Tensor, b: Tensor) -> None:
+    """Exchange the contents of two fp32 tensors in place (omr_swap_f32); overlapping tensors are refused."""
+    require_cuda(a, b)
+    assert a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
+    lib().call("omr_swap_f32", ptr(a), ptr(b), a.numel(), cur_stream())
+
+
 def argmax(x: Tensor) -> Tuple[Tensor, Tensor]:
     """x fp32 [n] or [rows, n] (unit inner stride) -> (indices int64 [rows], top-1 values fp32 [rows])."""
     require_cuda(x)

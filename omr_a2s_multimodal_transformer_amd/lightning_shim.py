@@ -4,6 +4,7 @@ train.py:115-158, test.py:62-76).  Only what the hot path's callers touch is pro
 """
 from __future__ import annotations
 
+import contextlib
 import inspect
 from typing import Any, Dict, Iterable, List, Optional
 
@@ -65,18 +66,26 @@ class Trainer:
     (Lightning-DDP semantics) and the evaluation loops shard their samples over the ranks and all-reduce the metric counts."""
 
     def __init__(self, max_epochs: int = 1, check_val_every_n_epoch: int = 1, reducer=None, log_every: int = 0,
-                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm", skip_nonfinite: bool = False, **_ignored):
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm", skip_nonfinite: bool = False,
+                 optim=None, ema_eval: bool = True, **_ignored):
         """gradient_clip_val / gradient_clip_algorithm: Lightning's arguments; clipping by the global L2 norm ("norm") is what the
         guarded optimizer step provides (FusedAdam.enable_guard), clipping by value is not built.  skip_nonfinite: skip an
         optimizer step whose gradient holds inf / NaN, as the reference's GradScaler does under precision="16-mixed" (train.py:153).
         Either one switches the guard on; with it, fit() logs `grad_norm` (one step late: the host never waits for the device)
-        and leaves the number of skipped steps in callback_metrics["skipped_steps"]."""
+        and leaves the number of skipped steps in callback_metrics["skipped_steps"].
+        optim (config.OptimConfig): fit() builds the optimizer through model.make_optimizer(optim=...) instead of
+        configure_optimizers() -- weight decay, learning-rate schedule, EMA weights -- and logs `lr` after every step.  ema_eval:
+        when the optimizer keeps EMA weights, the validation and test loops run inside optimizer.ema_weights().  fit() leaves the
+        optimizer on `self.optimizer`: save_checkpoint(extra=dict(optimizer=trainer.optimizer.state_dict())) keeps its state, and
+        save_checkpoint called inside `with trainer.optimizer.ema_weights():` writes the averaged weights."""
         if gradient_clip_algorithm != "norm":
             raise ValueError(f"gradient_clip_algorithm={gradient_clip_algorithm!r} is not supported: only \"norm\" (clipping by the global "
                              "L2 norm, torch.nn.utils.clip_grad_norm_) is")
         self.max_epochs, self.check_val_every_n_epoch, self.reducer, self.log_every = max_epochs, check_val_every_n_epoch, reducer, log_every
         self.gradient_clip_val = gradient_clip_val if gradient_clip_val else None       # Lightning: None and 0 both mean "no clipping"
         self.skip_nonfinite = bool(skip_nonfinite)
+        self.optim, self.ema_eval = optim, bool(ema_eval)
+        self.optimizer = None
         self.callback_metrics: Dict[str, Any] = {}
 
     @staticmethod
@@ -95,7 +104,8 @@ class Trainer:
         return self.reducer
 
     def fit(self, model, train_dataloaders: Iterable, val_dataloaders: Optional[Iterable] = None) -> None:
-        opt = model.configure_optimizers()
+        opt = model.configure_optimizers() if self.optim is None else model.make_optimizer(optim=self.optim)
+        self.optimizer = opt
         guarded = self.gradient_clip_val is not None or self.skip_nonfinite
         if guarded:
             opt.enable_guard(max_norm=self.gradient_clip_val, skip_nonfinite=True)
@@ -116,6 +126,8 @@ class Trainer:
                     opt.step()
                 if guarded and opt.settled_grad_norm is not None:
                     model.log("grad_norm", opt.settled_grad_norm)        # the previous step's: step() has just settled it
+                if self.optim is not None:
+                    model.log("lr", opt.param_groups[0]["lr"])
                 if self.log_every and i % self.log_every == 0:
                     print(f"epoch {epoch} step {i} train_loss {float(loss):.4f}")
             if val_dataloaders is not None and (epoch + 1) % self.check_val_every_n_epoch == 0:
@@ -132,7 +144,10 @@ class Trainer:
         world, rank = self._world(), self._rank()
         if world > 1:
             self._reducer_for(model)
-        with torch.no_grad():
+        opt = self.optimizer
+        flat = getattr(opt, "flat", None)           # the optimizer fit() built, if it is this model's and keeps EMA weights
+        averaged = self.ema_eval and flat is not None and flat is getattr(model, "_flat", None) and flat.ema is not None
+        with (opt.ema_weights() if averaged else contextlib.nullcontext()), torch.no_grad():
             for i, batch in enumerate(loader):
                 if i % world != rank:
                     continue

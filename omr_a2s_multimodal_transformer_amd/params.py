@@ -10,12 +10,14 @@ data-parallel gradient all-reduce runs over a few large contiguous buckets (ddp.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import kernels as K
+from .config import OptimConfig, lr_at
 
 ALIGN = 64  # elements; keeps every view 256-byte aligned in fp32 and 128-byte aligned in bf16
 
@@ -76,6 +78,7 @@ class FlatParams:
         self.lowp = torch.zeros(off, dtype=torch.bfloat16, device=device) if compute_dtype == torch.bfloat16 else None
         self.exp_avg: Optional[torch.Tensor] = None
         self.exp_avg_sq: Optional[torch.Tensor] = None
+        self.ema: Optional[torch.Tensor] = None          # EMA of the masters, same layout (FusedAdam.enable_ema)
         with torch.no_grad():
             for n, p in named_params:
                 o, cnt = self.offsets[n]
@@ -238,10 +241,37 @@ class _Guard:
         return bool(rec.apply)
 
 
+def decays(name: str, ndim: int, no_decay: Iterable[str]) -> bool:
+    """Does weight decay apply to this parameter?  Never to one with fewer than two dimensions (biases, norm gains), nor to one
+    whose name holds one of the `no_decay` substrings (OptimConfig.no_decay)."""
+    return ndim >= 2 and not any(s in name for s in no_decay)
+
+
+def decay_block_map(offsets: Dict[str, Tuple[int, int]], ndims: Dict[str, int], total: int, no_decay: Iterable[str]) -> List[int]:
+    """One entry per ALIGN elements of a flat buffer of `total` elements (omr_adamw_ema's decay_blocks): 1 where the block belongs
+    to a parameter that decays, else 0.  Every parameter starts on a block boundary, so a block never holds two parameters; the
+    unused end of a parameter's last block shares its entry (nothing reads those elements), and blocks no parameter touches
+    count as "no decay".  Host values only: a CPU test checks it against a hand-made table."""
+    no_decay = tuple(no_decay)
+    blocks = [0] * ((total + ALIGN - 1) // ALIGN)
+    for name, (off, count) in offsets.items():
+        if off % ALIGN:
+            raise ValueError(f"decay_block_map: {name} starts at {off}, not on a multiple of {ALIGN}")
+        if decays(name, ndims[name], no_decay):
+            for k in range(off // ALIGN, (off + count + ALIGN - 1) // ALIGN):
+                blocks[k] = 1
+    return blocks
+
+
 class FusedAdam:
     """torch.optim.Adam(lr=1e-4, amsgrad=False) semantics (model.py:134-139,475-483) as one kernel launch per top-level
     sub-module over the flat buffers (one launch in the common case that every sub-module has gradients).
     Interface subset of torch.optim.Optimizer: step / zero_grad / param_groups / state_dict.
+
+    optim (config.OptimConfig, optional): the recipe around that update -- decoupled weight decay (torch.optim.AdamW) that leaves
+    biases and norm gains alone, a learning-rate schedule (config.lr_at, indexed by step() CALLS) and an exponential moving
+    average of the weights (enable_ema / ema_weights).  A config that asks for none of them launches what no config launches;
+    otherwise every range goes through omr_adamw_ema, behind the guard's record when the guard is on.
 
     Parameters WITHOUT a gradient are skipped like torch.optim.Adam skips `p.grad is None` (Lightning zeroes with
     set_to_none): no update from stale momentum, no moment decay, no step count.  In MultimodalTransformer the modality-drop
@@ -251,7 +281,8 @@ class FusedAdam:
     seed with rank 0's value -- model.MultimodalTransformer._draw_modality, ddp.GradReducer.broadcast_state -- so all ranks
     skip the same slices; tests/test_ddp_cpu.py runs it with ranks seeded differently.)"""
 
-    def __init__(self, flat: FlatParams, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, touched_fn=None):
+    def __init__(self, flat: FlatParams, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, touched_fn=None,
+                 optim: Optional[OptimConfig] = None):
         self.flat = flat
         self.param_groups = [dict(params=flat.params, lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False)]
         self.ranges = flat.module_ranges()
@@ -261,6 +292,71 @@ class FusedAdam:
         if flat.exp_avg is None:
             flat.exp_avg = torch.zeros_like(flat.master)
             flat.exp_avg_sq = torch.zeros_like(flat.master)
+        self.calls = 0                                     # step() calls so far: the schedule's index (a skipped step counts)
+        self.optim: Optional[OptimConfig] = None
+        self.ema_decay: Optional[float] = None
+        self._decay_blocks: Optional[torch.Tensor] = None
+        self._in_ema = False
+        if optim is not None:
+            self._configure(optim)
+
+    # ---- recipe: decoupled weight decay, schedule, EMA weights (config.OptimConfig; omr_adamw_ema in csrc/optim.hip)
+    def _configure(self, optim: OptimConfig) -> None:
+        f, g = self.flat, self.param_groups[0]
+        self.optim = optim
+        g.update(lr=optim.lr, betas=optim.betas, eps=optim.eps, weight_decay=optim.weight_decay)
+        self._decay_blocks = None
+        if optim.weight_decay != 0:                        # built once: the placement never changes
+            ndims = {n: p.dim() for n, p in zip(f.names, f.params)}
+            self._decay_blocks = torch.tensor(decay_block_map(f.offsets, ndims, f.total, optim.no_decay), dtype=torch.uint8).to(f.device)
+        if optim.ema_decay is not None:
+            self.enable_ema(optim.ema_decay)
+
+    @property
+    def _recipe(self) -> bool:
+        """Does step() go through omr_adamw_ema?  Not with a config that asks for nothing new and no EMA: then it launches
+        omr_adam / omr_adam_guarded exactly as without a config."""
+        return self.flat.ema is not None or (self.optim is not None and not self.optim.plain)
+
+    def enable_ema(self, decay: float) -> None:
+        """Keep an exponential moving average of the weights in `flat.ema` (fp32, laid out like `flat.master`):
+        ema = decay * ema + (1 - decay) * p after every applied step, inside the step kernel.
+        The average starts as a COPY of the current `flat.master` -- torch.optim.swa_utils.AveragedModel's first update.
+        Only the ranges a step touches are averaged: a sub-module the modality drop left without gradients keeps its average,
+        as it keeps its moments and its step count; so does everything when the guard skips the step.
+        Calling it again changes the decay and keeps the average."""
+        if not 0 <= decay <= 1:
+            raise ValueError(f"enable_ema: decay must lie in [0, 1] (got {decay})")
+        if self._in_ema:
+            raise RuntimeError("enable_ema: not inside ema_weights()")
+        self.ema_decay = float(decay)
+        if self.flat.ema is None:
+            self.flat.ema = self.flat.master.clone()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Scope in which the model computes with the averaged weights: settles the last guarded step, exchanges `flat.master`
+        and `flat.ema` in place (omr_swap_f32: no third buffer) and refreshes the bf16 copy and the conv flips; on exit -- also
+        when the body raised -- exchanges them back and refreshes again, which restores every buffer to the bit.  Inside,
+        the parameters (state_dict, save_checkpoint) ARE the averaged weights.  Not nestable; step() inside is refused."""
+        if self.flat.ema is None:
+            raise RuntimeError("ema_weights: no average is kept -- call enable_ema(decay) or give OptimConfig(ema_decay=...)")
+        if self._in_ema:
+            raise RuntimeError("ema_weights: already inside the scope (it does not nest)")
+        self.settle()
+        self._swap_ema()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
+            self._swap_ema()
+
+    def _swap_ema(self) -> None:
+        f = self.flat
+        K.swap_f32(f.master, f.ema)
+        f.updates += 1              # a weight update torch's version counter does not see
+        f.sync_lowp()
 
     @property
     def steps(self) -> Dict[str, int]:
@@ -335,6 +431,8 @@ class FusedAdam:
         """touched: names of the top-level sub-modules that received gradients this step (None = all; default: ask the model)."""
         g = self.param_groups[0]
         f = self.flat
+        if self._in_ema:
+            raise RuntimeError("FusedAdam.step: inside ema_weights() the masters hold the averaged weights; leave the scope first")
         if touched is None and self.touched_fn is not None:
             touched = self.touched_fn()
         names = list(self.ranges) if touched is None else [n for n in self.ranges if n in set(touched)]
@@ -360,7 +458,21 @@ class FusedAdam:
                 runs.append([b, e, self.steps[n]])
         if guard is not None:
             K.grad_norm(f.grad, [self.ranges[n] for n in names], grad_scale, guard.max_norm, guard.ws, guard.ctl)
-        for b, e, st in runs:
+        recipe = self._recipe
+        if recipe:
+            # The schedule is indexed by CALLS: a step the device skips still advances it, so no host decision waits for the guard.
+            cfg = self.optim
+            lr = g["lr"] if cfg is None else lr_at(cfg, self.calls)
+            wd = 0.0 if cfg is None else cfg.weight_decay
+            for b, e, st in runs:
+                K.adamw_ema_step(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, lr, g["betas"], g["eps"], grad_scale,
+                                 p_lowp=None if f.lowp is None else f.lowp[b:e], weight_decay=wd,
+                                 decay_blocks=None if self._decay_blocks is None else self._decay_blocks[b // ALIGN:],
+                                 ema=None if f.ema is None else f.ema[b:e], ema_decay=self.ema_decay or 0.0,
+                                 ctl=None if guard is None else guard.ctl)
+            g["lr"] = lr
+        self.calls += 1
+        for b, e, st in () if recipe else runs:
             if guard is None:
                 K.adam_step(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, g["lr"], g["betas"], g["eps"], grad_scale,
                             p_lowp=None if f.lowp is None else f.lowp[b:e])
@@ -377,11 +489,30 @@ class FusedAdam:
             {k: v for k, v in self.param_groups[0].items() if k != "params"}])
         if self._guard is not None:
             sd["skipped"] = self.skipped
+        sd["calls"] = self.calls
+        if self.optim is not None:
+            sd["optim"] = self.optim.to_dict()
+        if self.flat.ema is not None:
+            # inside ema_weights() the two buffers are exchanged: the average is what `master` holds there
+            sd["ema"] = self.flat.master.clone() if self._in_ema else self.flat.ema
+            sd["ema_decay"] = self.ema_decay
         return sd
 
     def load_state_dict(self, sd) -> None:
+        """Also takes a dict written before the recipe existed (no `calls`, `optim`, `ema`): the schedule then starts at the
+        number of applied steps, and configuration and average stay as they are."""
+        if self._in_ema:
+            raise RuntimeError("FusedAdam.load_state_dict: not inside ema_weights()")
         self.settle()
         self.steps = {g: int(sd.get("steps", {}).get(g, sd["step"])) for g in self.ranges}
         self._ledger.skipped = int(sd.get("skipped", 0))
         self.flat.exp_avg.copy_(sd["exp_avg"])
         self.flat.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self.calls = int(sd.get("calls", sd["step"]))
+        if sd.get("optim") is not None:
+            self._configure(OptimConfig.from_dict(sd["optim"]))
+        if sd.get("ema") is not None:
+            self.enable_ema(sd["ema_decay"])
+            self.flat.ema.copy_(sd["ema"])
+        if self._recipe and self.optim is not None and self.calls > 0:
+            self.param_groups[0]["lr"] = lr_at(self.optim, self.calls - 1)      # what the last step() left there

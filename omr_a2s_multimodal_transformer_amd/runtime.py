@@ -250,8 +250,10 @@ class FlatModuleMixin:
 
     _touched = None     # top-level sub-modules whose parameters took part in the last forward (None = all); see FusedAdam
 
-    def make_optimizer(self, lr: float = 1e-4) -> FusedAdam:
-        return FusedAdam(self.ensure_flat(), lr=lr, touched_fn=lambda: self._touched)
+    def make_optimizer(self, lr: float = 1e-4, optim=None) -> FusedAdam:
+        """optim (config.OptimConfig): weight decay, learning-rate schedule and EMA weights around the fused step; its lr, betas
+        and eps then replace `lr`.  None: the reference's Adam."""
+        return FusedAdam(self.ensure_flat(), lr=lr, touched_fn=lambda: self._touched, optim=optim)
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):  # type: ignore[override]
         out = nn.Module.load_state_dict(self, state_dict, strict=strict)
