@@ -584,6 +584,79 @@ int omr_weighted_beam_select(const float* logits_a, long lda, const float* logit
 int omr_weighted_beam_decode_steps(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b, const int* mem_len_b,
                                    const omr_beam_desc* beam_desc, void* self_kv2_b, float alpha, int t0, int n_steps, void* stream);
 
+/* ---- grammar-constrained decoding -------------------------------------------------------------------------------------- */
+/* An extension: the reference picks over the whole vocabulary at every position (argmax in Transformer.validation_step,
+ * src/transformer/model.py:182-193; the mixed argmax of src/multimodal/weighted_multimodal/test.py:50-61), so nothing keeps a
+ * transcript inside the token stream src/data/encoding.py `encode` produces.  Here a deterministic automaton over token ids
+ * (grammar.py of this package), compressed by token class, restricts every pick and every beam candidate ON THE DEVICE:
+ *   cls    uint8 [V]      class of every vocabulary entry, < C
+ *   next   int32 [S][C]   next[s][c] = the state after a token of class c in state s, or -1: forbidden there
+ *   state  int32 [rows]   each row's current state, advanced by the kernels below (rows = B; N * beam for a beam search)
+ * All three are device memory.  A forbidden token's logit is read as -inf BEFORE any comparison or expf (NaN / +inf there cannot
+ * reach a maximum, a sum or a pick), so log-probabilities are renormalised over the allowed tokens.  The host builder
+ * guarantees that every reachable state allows a token and that state values stay inside [0, S); the kernels clamp a state into
+ * that range and never write a value outside it.  Every entry below refuses (OMR_ERR_ARG) a NULL descriptor, a NULL cls / next /
+ * state, C outside 1..OMR_GRAMMAR_MAX_CLASSES and S < 1. */
+#define OMR_GRAMMAR_MAX_CLASSES 256
+typedef struct omr_grammar_desc {
+    const unsigned char* cls; const int* next; int S, C; int* state;
+} omr_grammar_desc;
+/* omr_argmax (model.py:187,253) over the allowed tokens of each row's state: idx_out[r] = first index of the largest allowed
+ * logit of logits [rows][ld] (n entries read), val_out[r] (nullable) that logit, tokens_out[r] (nullable) a second copy of
+ * the index, and state[r] <- next[state[r]][cls[idx]].  Equal, bit for bit, to omr_argmax on logits the host masked with -inf. */
+int omr_grammar_pick(const float* logits, long ld, int rows, int n, const omr_grammar_desc* grammar, long* idx_out, float* val_out,
+                     long* tokens_out, void* stream);
+/* omr_weighted_argmax_rows (weighted_multimodal/test.py:50-61) the same way: both logit rows are masked before their softmax
+ * statistics; ONE state per row drives both models. */
+int omr_weighted_grammar_pick(const float* logits_a, long lda, const float* logits_b, long ldb, int rows, int n, float alpha,
+                              const omr_grammar_desc* grammar, long* idx_out, float* prob_out, long* tokens_out, void* stream);
+/* omr_beam_select (the loop body of _Base.beam_search, model.py of this package) under the automaton; state: int32 [N * beam].
+ * Phase 1 ranks log_softmax over the allowed tokens of each row's state.  Phase 2: a candidate (parent, token) is live only if
+ * its parent is live AND next[state[parent]][cls[token]] >= 0 -- decided by the table, not by the value, so a forbidden token
+ * never becomes a survivor, a finished hypothesis or a history entry, also where fewer than `beam` tokens are allowed.  The
+ * input's `beam` old states are read before anything is written; survivor slot i gets next[old_state[parent_i]][cls[token_i]],
+ * dead padding rows the first survivor's.  The states of inputs that are done (before or by this launch) are left alone. */
+int omr_beam_select_grammar(const float* logits, long ld, int V, const omr_beam_desc* beam_desc, const omr_grammar_desc* grammar, int t,
+                            void* stream);
+/* omr_weighted_beam_select the same way (both rows masked before the mix's statistics). */
+int omr_weighted_beam_select_grammar(const float* logits_a, long lda, const float* logits_b, long ldb, int V, float alpha,
+                                     const omr_beam_desc* beam_desc, const omr_grammar_desc* grammar, int t, void* stream);
+/* omr_decode_steps (model.py:182-193) with the constrained pick, as do the two entries after it: per position the head runs without its fused
+ * pick and ONE omr_grammar_pick launch over the position's fp32 logits stands where the unconstrained pick's reduction (row
+ * kernel) or omr_argmax (generic widths) stood -- the launches per position are the unconstrained count.  grammar->state (B
+ * entries) advances across all n_steps without the host; out_top1 is the top-1 ALLOWED logit.  out_tokens must not be NULL. */
+int omr_decode_steps_grammar(const omr_decode_desc* desc, const omr_grammar_desc* grammar, long* tokens, int t0, int n_steps, long* out_tokens,
+                             float* out_top1, float* last_logits, void* stream);
+/* omr_decode_steps_varlen (ragged memories; the loop of model.py:171-199 at batch size > 1) with the constrained pick; mem_len must
+ * not be NULL. */
+int omr_decode_steps_varlen_grammar(const omr_decode_desc* desc, const int* mem_len, const omr_grammar_desc* grammar, long* tokens, int t0,
+                                    int n_steps, long* out_tokens, float* out_top1, float* last_logits, void* stream);
+/* omr_decode_steps_rows (rows at their own positions: continuous batching of the loop of model.py:171-199) with the constrained
+ * pick.  The host puts a refilled row's state to the start state, where it sets its token.  OMR_ERR_UNSUPPORTED (widths the
+ * row kernel does not take) is answered before the descriptor is looked at, as in omr_decode_steps_rows. */
+int omr_decode_steps_rows_grammar(const omr_decode_desc* desc, const int* mem_len, const int* pos, int t_max, const omr_grammar_desc* grammar,
+                                  long* tokens, int n_steps, long* out_tokens, float* out_top1, float* last_logits, void* stream);
+/* omr_weighted_decode_steps_varlen (weighted_multimodal/test.py:21-70 for B pairs) with omr_weighted_grammar_pick in place of
+ * omr_weighted_argmax_rows: same launches per position; grammar->state holds B entries. */
+int omr_weighted_decode_steps_varlen_grammar(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b,
+                                             const int* mem_len_b, const omr_grammar_desc* grammar, float alpha, long* tokens, int t0, int n_steps,
+                                             long* out_tokens, float* out_prob, float* logits_a, float* logits_b, void* stream);
+/* omr_weighted_decode_steps_rows (weighted_multimodal/test.py:21-70,154-172 with continuous batching) with
+ * omr_weighted_grammar_pick; one pos / t_max and one state per row for both models. */
+int omr_weighted_decode_steps_rows_grammar(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b,
+                                           const int* mem_len_b, const int* pos, int t_max, const omr_grammar_desc* grammar, float alpha,
+                                           long* tokens, int n_steps, long* out_tokens, float* out_prob, float* logits_a, float* logits_b,
+                                           void* stream);
+/* omr_beam_decode_steps (an extension of the greedy loop of model.py:182-193) with omr_beam_select_grammar as the selection;
+ * grammar->state: int32 [N * beam], every entry the start state before position 0. */
+int omr_beam_decode_steps_grammar(const omr_decode_desc* desc, const omr_beam_desc* beam_desc, const int* mem_len,
+                                  const omr_grammar_desc* grammar, int t0, int n_steps, void* stream);
+/* omr_weighted_beam_decode_steps (an extension of weighted_multimodal/test.py:21-70) with omr_weighted_beam_select_grammar; one
+ * state per row drives both models. */
+int omr_weighted_beam_decode_steps_grammar(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b,
+                                           const int* mem_len_b, const omr_beam_desc* beam_desc, void* self_kv2_b,
+                                           const omr_grammar_desc* grammar, float alpha, int t0, int n_steps, void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------------------------ */
 /* CrossEntropyLoss(ignore_index=pad) (model.py:109,166) on row-major logits [M][ldv]; acc2 = {sum, count} (fp64). */
 int omr_ce_fwd(int dtype, const void* logits, const long* target, float* lse, double* acc2, float* loss_out, long M, int V, long ldv,

@@ -301,13 +301,16 @@ extern "C" long omr_decode_workspace_bytes(const omr_decode_desc* d) {
 // ------------------------------------------------------------------------------------------------
 // Greedy driver.  Positions t0 .. t0 + n_steps - 1; pos (nullable, device int32 [B]): the per-row-position form
 // (omr_decode_steps_rows) -- row b runs positions pos[b] + s and t0 is the LARGEST of those first positions.
+// g (nullable; the *_grammar entries, checked there): the constrained pick -- the position runs without a pick (the head without
+// its pick halves, or no omr_argmax) and ONE omr_grammar_pick launch over its fp32 logits writes the same outputs and advances
+// g->state, so the launches per position are the unconstrained count.
 namespace {
 
 struct Run { int t0, n_steps; const int* pos; };
 
-int greedy_steps(const omr_decode_desc* dp, const int* mem_len, Run run, long* tokens, long* out_tokens, float* out_top1, float* last_logits,
-                 void* stream) {
-    if (!dp || !tokens) return OMR_ERR_ARG;
+int greedy_steps(const omr_decode_desc* dp, const int* mem_len, Run run, const omr_grammar_desc* g, long* tokens, long* out_tokens, float* out_top1,
+                 float* last_logits, void* stream) {
+    if (!dp || !tokens || (g && !out_tokens)) return OMR_ERR_ARG;
     OMR_TRY(check_model(*dp));
     OMR_TRY(check_steps(run.t0, run.n_steps, dp->max_len));
     if (run.n_steps > 1 && !out_tokens) return OMR_ERR_ARG;             // several steps need the token feedback
@@ -321,7 +324,8 @@ int greedy_steps(const omr_decode_desc* dp, const int* mem_len, Run run, long* t
     float* l32 = nullptr;
     for (int s = 0; s < run.n_steps; ++s) {
         const Pick pick = {out_tokens ? out_tokens + s * B : nullptr, (out_tokens && out_top1) ? out_top1 + s * B : nullptr};
-        OMR_TRY(run_position(m, position_at(m, run.pos, run.t0 + s, s), tok_in, pick, &l32, stream));
+        OMR_TRY(run_position(m, position_at(m, run.pos, run.t0 + s, s), tok_in, g ? Pick{nullptr, nullptr} : pick, &l32, stream));
+        if (g) OMR_TRY(omr_grammar_pick(l32, dp->ldv, dp->B, dp->V, g, pick.idx, pick.val, nullptr, stream));
         if (!out_tokens) break;                                         // one position without a pick
         if (row_kernel) tok_in = pick.idx;
         if (!row_kernel || s == run.n_steps - 1)
@@ -335,14 +339,14 @@ int greedy_steps(const omr_decode_desc* dp, const int* mem_len, Run run, long* t
 
 extern "C" int omr_decode_steps(const omr_decode_desc* dp, long* tokens, int t0, int n_steps, long* out_tokens, float* out_top1,
                                 float* last_logits, void* stream) {
-    return greedy_steps(dp, nullptr, Run{t0, n_steps, nullptr}, tokens, out_tokens, out_top1, last_logits, stream);
+    return greedy_steps(dp, nullptr, Run{t0, n_steps, nullptr}, nullptr, tokens, out_tokens, out_top1, last_logits, stream);
 }
 
 /* omr_decode_steps over a ragged batch of memories: desc->S is the padded memory length, row b attends over mem_len[b] of it */
 extern "C" int omr_decode_steps_varlen(const omr_decode_desc* dp, const int* mem_len, long* tokens, int t0, int n_steps, long* out_tokens,
                                        float* out_top1, float* last_logits, void* stream) {
     if (!mem_len) return OMR_ERR_ARG;
-    return greedy_steps(dp, mem_len, Run{t0, n_steps, nullptr}, tokens, out_tokens, out_top1, last_logits, stream);
+    return greedy_steps(dp, mem_len, Run{t0, n_steps, nullptr}, nullptr, tokens, out_tokens, out_top1, last_logits, stream);
 }
 
 /* omr_decode_steps_varlen for a state whose rows each sit at their own position (continuous batching of the reference's greedy
@@ -353,7 +357,29 @@ extern "C" int omr_decode_steps_rows(const omr_decode_desc* dp, const int* mem_l
     if (!dp) return OMR_ERR_ARG;
     if (!takes_row_kernel(*dp)) return OMR_ERR_UNSUPPORTED;
     if (!pos) return OMR_ERR_ARG;
-    return greedy_steps(dp, mem_len, Run{t_max, n_steps, pos}, tokens, out_tokens, out_top1, last_logits, stream);
+    return greedy_steps(dp, mem_len, Run{t_max, n_steps, pos}, nullptr, tokens, out_tokens, out_top1, last_logits, stream);
+}
+
+/* The three greedy entries under a token automaton (include/omr_hip.h "grammar-constrained decoding"; an extension of the loop of
+ * src/transformer/model.py:182-193): the same driver with the constrained pick; the descriptor is checked here. */
+extern "C" int omr_decode_steps_grammar(const omr_decode_desc* dp, const omr_grammar_desc* g, long* tokens, int t0, int n_steps, long* out_tokens,
+                                        float* out_top1, float* last_logits, void* stream) {
+    if (!grammar_desc_ok(g)) return OMR_ERR_ARG;
+    return greedy_steps(dp, nullptr, Run{t0, n_steps, nullptr}, g, tokens, out_tokens, out_top1, last_logits, stream);
+}
+
+extern "C" int omr_decode_steps_varlen_grammar(const omr_decode_desc* dp, const int* mem_len, const omr_grammar_desc* g, long* tokens, int t0,
+                                               int n_steps, long* out_tokens, float* out_top1, float* last_logits, void* stream) {
+    if (!mem_len || !grammar_desc_ok(g)) return OMR_ERR_ARG;
+    return greedy_steps(dp, mem_len, Run{t0, n_steps, nullptr}, g, tokens, out_tokens, out_top1, last_logits, stream);
+}
+
+extern "C" int omr_decode_steps_rows_grammar(const omr_decode_desc* dp, const int* mem_len, const int* pos, int t_max, const omr_grammar_desc* g,
+                                             long* tokens, int n_steps, long* out_tokens, float* out_top1, float* last_logits, void* stream) {
+    if (!dp) return OMR_ERR_ARG;
+    if (!takes_row_kernel(*dp)) return OMR_ERR_UNSUPPORTED;
+    if (!pos || !grammar_desc_ok(g)) return OMR_ERR_ARG;
+    return greedy_steps(dp, mem_len, Run{t_max, n_steps, pos}, g, tokens, out_tokens, out_top1, last_logits, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -364,12 +390,13 @@ extern "C" int omr_decode_steps_rows(const omr_decode_desc* dp, const int* mem_l
  * the same launch).  mem_len (nullable, independently per side): ragged memories of that model.  Rows never interact, so a row
  * equals the pair decoded alone (omr_weighted_decode_steps) whenever both of its memories take the key-split attention (> 64
  * tokens).  run.pos: one pos / t0 for both models (the two models of a pair are always at the same position); each model's
- * tables are filled per position, for that position alone. */
+ * tables are filled per position, for that position alone.  g (nullable; the *_grammar entries): omr_weighted_grammar_pick stands
+ * where omr_weighted_argmax_rows stood, one state per row for both models. */
 namespace {
 
 struct Side { const omr_decode_desc* d; const int* mem_len; float* logits; };
 
-int weighted_steps(const Side (&side)[2], Run run, float alpha, long* tokens, long* out_tokens, float* out_prob, void* stream) {
+int weighted_steps(const Side (&side)[2], Run run, const omr_grammar_desc* g, float alpha, long* tokens, long* out_tokens, float* out_prob, void* stream) {
     const omr_decode_desc *da = side[0].d, *db = side[1].d;
     if (!tokens || !out_tokens || !side[0].logits || !side[1].logits) return OMR_ERR_ARG;
     if (da->B < 1 || da->B != db->B || da->V != db->V) return OMR_ERR_ARG;
@@ -387,8 +414,12 @@ int weighted_steps(const Side (&side)[2], Run run, float alpha, long* tokens, lo
             OMR_TRY(run_position(m[k], position_at(m[k], run.pos, run.t0 + s, 0), tokens, Pick{nullptr, nullptr}, &l32, stream));
             OMR_TRY(copy_logits(m[k], side[k].logits, l32, stream));
         }
-        OMR_TRY(omr_weighted_argmax_rows(side[0].logits, da->ldv, side[1].logits, db->ldv, (int)B, da->V, alpha, out_tokens + s * B,
-                                     out_prob ? out_prob + s * B : nullptr, tokens, stream));
+        if (g)
+            OMR_TRY(omr_weighted_grammar_pick(side[0].logits, da->ldv, side[1].logits, db->ldv, (int)B, da->V, alpha, g, out_tokens + s * B,
+                                          out_prob ? out_prob + s * B : nullptr, tokens, stream));
+        else
+            OMR_TRY(omr_weighted_argmax_rows(side[0].logits, da->ldv, side[1].logits, db->ldv, (int)B, da->V, alpha, out_tokens + s * B,
+                                         out_prob ? out_prob + s * B : nullptr, tokens, stream));
     }
     return OMR_OK;
 }
@@ -400,7 +431,7 @@ extern "C" int omr_weighted_decode_steps_varlen(const omr_decode_desc* da, const
                                                 float* logits_b, void* stream) {
     if (!da || !db) return OMR_ERR_ARG;
     const Side side[2] = {{da, mem_len_a, logits_a}, {db, mem_len_b, logits_b}};
-    return weighted_steps(side, Run{t0, n_steps, nullptr}, alpha, tokens, out_tokens, out_prob, stream);
+    return weighted_steps(side, Run{t0, n_steps, nullptr}, nullptr, alpha, tokens, out_tokens, out_prob, stream);
 }
 
 /* omr_weighted_decode_steps_varlen over rows at their own positions.  As in omr_decode_steps_rows, whether both descriptors
@@ -412,7 +443,27 @@ extern "C" int omr_weighted_decode_steps_rows(const omr_decode_desc* da, const i
     if (!takes_row_kernel(*da) || !takes_row_kernel(*db)) return OMR_ERR_UNSUPPORTED;
     if (!pos) return OMR_ERR_ARG;
     const Side side[2] = {{da, mem_len_a, logits_a}, {db, mem_len_b, logits_b}};
-    return weighted_steps(side, Run{t_max, n_steps, pos}, alpha, tokens, out_tokens, out_prob, stream);
+    return weighted_steps(side, Run{t_max, n_steps, pos}, nullptr, alpha, tokens, out_tokens, out_prob, stream);
+}
+
+/* The two batched fusion entries under a token automaton (include/omr_hip.h "grammar-constrained decoding"; an extension of
+ * weighted_multimodal/test.py:21-70). */
+extern "C" int omr_weighted_decode_steps_varlen_grammar(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
+                                                        const omr_grammar_desc* g, float alpha, long* tokens, int t0, int n_steps, long* out_tokens,
+                                                        float* out_prob, float* logits_a, float* logits_b, void* stream) {
+    if (!da || !db || !grammar_desc_ok(g)) return OMR_ERR_ARG;
+    const Side side[2] = {{da, mem_len_a, logits_a}, {db, mem_len_b, logits_b}};
+    return weighted_steps(side, Run{t0, n_steps, nullptr}, g, alpha, tokens, out_tokens, out_prob, stream);
+}
+
+extern "C" int omr_weighted_decode_steps_rows_grammar(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
+                                                      const int* pos, int t_max, const omr_grammar_desc* g, float alpha, long* tokens, int n_steps,
+                                                      long* out_tokens, float* out_prob, float* logits_a, float* logits_b, void* stream) {
+    if (!da || !db) return OMR_ERR_ARG;
+    if (!takes_row_kernel(*da) || !takes_row_kernel(*db)) return OMR_ERR_UNSUPPORTED;
+    if (!pos || !grammar_desc_ok(g)) return OMR_ERR_ARG;
+    const Side side[2] = {{da, mem_len_a, logits_a}, {db, mem_len_b, logits_b}};
+    return weighted_steps(side, Run{t_max, n_steps, pos}, g, alpha, tokens, out_tokens, out_prob, stream);
 }
 
 /* bs = 1 like the reference (test.py:27): the one-row, full-memory case */

@@ -12,14 +12,22 @@ constexpr int BEAM_GROUPS = 4;         // rows of an input ranked side by side: 
 // Phase 2 of a selection kernel, one workgroup per input n (every thread calls it): the beam * beam (<= 64) candidates
 // (c_tok, c_val)[parent * beam + j] that phase 1 left in LDS get fp64 scores from the live rows, wave 0 ranks them by all-pairs
 // comparison, one candidate per lane, and walks them in order as ballots -- the host loop's walk (_Base.beam_search): finished
-// record, stop rule, survivors and dead padding (`put`).  One definition for both selection kernels.
-__device__ __forceinline__ void beam_rank_and_put(const omr_beam_desc& bd, int n, int t, const float* c_val, const int* c_tok) {
+// record, stop rule, survivors and dead padding (`put`).  One definition for the selection kernels.
+// g (absent in the unconstrained kernels; omr_grammar_desc of the constrained ones): a candidate is live only if its parent is
+// live AND the table allows its token in the parent's state -- decided by next[state[parent]][cls[token]], not by the value, so
+// a forbidden token (phase 1 emits them, at -inf, where a state allows fewer than `beam` tokens) is never a survivor, a finished
+// hypothesis or a history entry.  Every candidate's successor state is looked up from the input's OLD states here, before the
+// barriers that precede the first `put`; a survivor's slot gets its own, dead padding rows the first survivor's.
+__device__ __forceinline__ void beam_rank_and_put(const omr_beam_desc& bd, int n, int t, const float* c_val, const int* c_tok,
+                                                  const omr_grammar_desc* g = nullptr) {
     __shared__ double u_sc[64], o_sc[64];          // candidates as found / in order
     __shared__ int u_live[64], o_tok[64], o_par[64], o_ok[64];
+    __shared__ int old_state[OMR_MAX_BEAM], o_ns[64];
     const int beam = bd.beam, row0 = n * beam, lane = threadIdx.x;
+    if (g && lane < beam) old_state[lane] = min(max(g->state[row0 + lane], 0), g->S - 1);
     __syncthreads();
     const int nc = beam * beam;
-    double sc = 0.0; int par = 0, tok = 0; bool live = false;
+    double sc = 0.0; int par = 0, tok = 0, ns = 0; bool live = false;
     if (lane < 64) {
         o_ok[lane] = 0;
         if (lane < nc) {
@@ -27,6 +35,11 @@ __device__ __forceinline__ void beam_rank_and_put(const omr_beam_desc& bd, int n
             const double ps = bd.scores[row0 + par];
             live = ps > -INFINITY;                  // dead rows contribute no candidates
             sc = ps + (double)c_val[lane];
+            if (g) {
+                const int c = g->cls[tok];            // a class the table does not hold is forbidden, never an index past its row
+                ns = c < g->C ? g->next[(long)old_state[par] * g->C + c] : -1;
+                live = live && ns >= 0 && ns < g->S;
+            }
         }
         u_sc[lane] = sc; u_live[lane] = live;
     }
@@ -39,6 +52,7 @@ __device__ __forceinline__ void beam_rank_and_put(const omr_beam_desc& bd, int n
             if (s2 > sc || (s2 == sc && (p2 < par || (p2 == par && t2 < tok)))) ++rank;
         }
         o_sc[rank] = sc; o_tok[rank] = tok; o_par[rank] = par; o_ok[rank] = 1;
+        if (g) o_ns[rank] = ns;
     }
     __syncthreads();
     if (lane >= 64) return;
@@ -65,13 +79,14 @@ __device__ __forceinline__ void beam_rank_and_put(const omr_beam_desc& bd, int n
     }
     const int nsurv = min(__popcll(live_mask), beam);
     const long hrow = (long)t * bd.N * beam;
-    auto put = [&](int slot, int p_out, int t_out, double s_out) {
+    auto put = [&](int slot, int p_out, int t_out, double s_out, int rank) {
         const int r = row0 + slot;
         bd.parents[r] = p_out; bd.tokens[r] = t_out; bd.scores[r] = s_out;
         bd.hist_parent[hrow + r] = p_out; bd.hist_token[hrow + r] = t_out;
+        if (g) g->state[r] = o_ns[rank];
     };
-    if (surv) put(before, par, tok, sc);
-    if (lane >= nsurv && lane < beam) put(lane, o_par[first], o_tok[first], -INFINITY);      // dead padding rows: copies of the first survivor
+    if (surv) put(before, par, tok, sc, lane);
+    if (lane >= nsurv && lane < beam) put(lane, o_par[first], o_tok[first], -INFINITY, first);      // dead padding rows: copies of the first survivor
 }
 
 // One workgroup per input.  Phase 1: the top `beam` log-probabilities of each of its rows (topk_logprob_row, the row body of
@@ -115,6 +130,58 @@ __global__ __launch_bounds__(256 * BEAM_GROUPS) void weighted_beam_select_kernel
         });
     }
     beam_rank_and_put(bd, n, t, c_val, c_tok);
+}
+
+// The two selection kernels under a token automaton (include/omr_hip.h "grammar-constrained decoding").  Phase 1: each group
+// stages the `next` row of ITS row's state in LDS and ranks through the masked load, so the log-probabilities are renormalised
+// over the allowed tokens.  Phase 2: beam_rank_and_put with the descriptor.
+__global__ __launch_bounds__(256 * BEAM_GROUPS) void beam_select_grammar_kernel(const float* __restrict__ logits, long ld, int V, omr_beam_desc bd,
+                                                                                omr_grammar_desc gd, int t) {
+    __shared__ float sv[BEAM_GROUPS][256];
+    __shared__ int si[BEAM_GROUPS][256];
+    __shared__ int next_row[BEAM_GROUPS][256];
+    __shared__ float c_val[64];
+    __shared__ int c_tok[64];
+    const int n = blockIdx.x, beam = bd.beam, row0 = n * beam;
+    if (bd.done[n]) return;                         // frozen (uniform over the workgroup)
+    const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
+    for (int k0 = 0; k0 < beam; k0 += BEAM_GROUPS) {
+        const int k = k0 + g;
+        const bool real = k < beam;                 // a group without a row walks an empty one: the barriers stay uniform
+        const long r = row0 + (real ? k : 0);
+        __syncthreads();                            // the previous round's loads of next_row are over
+        stage_next_row(gd.next, gd.S, gd.C, gd.state[r], tid, next_row[g]);
+        __syncthreads();
+        topk_logprob_row(logits + r * ld, real ? V : 0, beam, tid, sv[g], si[g], [&](int j, int idx, float val) {
+            if (tid == 0 && real) { c_tok[k * beam + j] = idx; c_val[k * beam + j] = val; }
+        }, MaskedLoad{gd.cls, next_row[g]});
+    }
+    beam_rank_and_put(bd, n, t, c_val, c_tok, &gd);
+}
+
+__global__ __launch_bounds__(256 * BEAM_GROUPS) void weighted_beam_select_grammar_kernel(const float* __restrict__ la, long lda, const float* __restrict__ lb,
+                                                                                         long ldb, int V, float wa, float wb, omr_beam_desc bd,
+                                                                                         omr_grammar_desc gd, int t) {
+    __shared__ float sa[BEAM_GROUPS][256], sb[BEAM_GROUPS][256];
+    __shared__ int si[BEAM_GROUPS][256];
+    __shared__ int next_row[BEAM_GROUPS][256];
+    __shared__ float c_val[64];
+    __shared__ int c_tok[64];
+    const int n = blockIdx.x, beam = bd.beam, row0 = n * beam;
+    if (bd.done[n]) return;                         // frozen (uniform over the workgroup)
+    const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
+    for (int k0 = 0; k0 < beam; k0 += BEAM_GROUPS) {
+        const int k = k0 + g;
+        const bool real = k < beam;                 // a group without a row walks an empty one: the barriers stay uniform
+        const long r = row0 + (real ? k : 0);
+        __syncthreads();                            // the previous round's loads of next_row are over
+        stage_next_row(gd.next, gd.S, gd.C, gd.state[r], tid, next_row[g]);
+        __syncthreads();
+        weighted_topk_logprob_row(la + r * lda, lb + r * ldb, real ? V : 0, wa, wb, beam, tid, sa[g], sb[g], si[g], [&](int j, int idx, float val) {
+            if (tid == 0 && real) { c_tok[k * beam + j] = idx; c_val[k * beam + j] = val; }
+        }, MaskedLoad{gd.cls, next_row[g]});
+    }
+    beam_rank_and_put(bd, n, t, c_val, c_tok, &gd);
 }
 
 // Cache reorder: new row i of an input continues row parents[i] of it.  Positions [lo, t] of every layer and row move from the
@@ -174,14 +241,19 @@ bool beam_model_ok(const BeamModel& bm, const omr_beam_desc& b) {
 }
 
 // ---- launches
-void launch_select(const float* logits, long ld, int V, const omr_beam_desc& b, int t, void* stream) {
-    hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)b.N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, logits, ld, V, b, t);
+// g (nullable): the constrained kernel of each pair
+void launch_select(const float* logits, long ld, int V, const omr_beam_desc& b, const omr_grammar_desc* g, int t, void* stream) {
+    if (g) hipLaunchKernelGGL(beam_select_grammar_kernel, dim3((unsigned)b.N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, logits, ld, V, b, *g, t);
+    else hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)b.N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, logits, ld, V, b, t);
 }
 
 struct LogitRows { const float* logits; long ld; };
-void launch_weighted_select(LogitRows a, LogitRows b, int V, float alpha, const omr_beam_desc& bd, int t, void* stream) {
-    hipLaunchKernelGGL(weighted_beam_select_kernel, dim3((unsigned)bd.N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, a.logits, a.ld, b.logits, b.ld, V,
-                       alpha, (float)(1.0 - (double)alpha), bd, t);          // the weights as omr_weighted_argmax_rows rounds them
+void launch_weighted_select(LogitRows a, LogitRows b, int V, float alpha, const omr_beam_desc& bd, const omr_grammar_desc* g, int t, void* stream) {
+    const float wb = (float)(1.0 - (double)alpha);                           // the weights as omr_weighted_argmax_rows rounds them
+    if (g) hipLaunchKernelGGL(weighted_beam_select_grammar_kernel, dim3((unsigned)bd.N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, a.logits, a.ld,
+                              b.logits, b.ld, V, alpha, wb, bd, *g, t);
+    else hipLaunchKernelGGL(weighted_beam_select_kernel, dim3((unsigned)bd.N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, a.logits, a.ld, b.logits, b.ld,
+                            V, alpha, wb, bd, t);
 }
 
 // The reorder launch after position t of one model: position t + 1 reads keys [lo, t + 1] (the position's band), so positions
@@ -240,39 +312,88 @@ extern "C" long omr_beam_workspace_bytes(omr_beam_desc* b) {
     return (long)beam_carve(b);
 }
 
-extern "C" int omr_beam_select(const float* logits, long ld, int V, const omr_beam_desc* bp, int t, void* stream) {
+// ---- the four select / four decode entries: each pair (plain, grammar) is one definition with a nullable descriptor
+namespace {
+
+int beam_select(const float* logits, long ld, int V, const omr_beam_desc* bp, const omr_grammar_desc* g, int t, void* stream) {
     if (!logits || !bp || !beam_desc_ok(*bp)) return OMR_ERR_ARG;
     if (!beam_fits_vocab(*bp, V) || ld < V || t < 0 || t >= bp->max_len) return OMR_ERR_ARG;
-    launch_select(logits, ld, V, *bp, t, stream);
+    launch_select(logits, ld, V, *bp, g, t, stream);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }
 
-extern "C" int omr_weighted_beam_select(const float* logits_a, long lda, const float* logits_b, long ldb, int V, float alpha, const omr_beam_desc* bp, int t,
-                                        void* stream) {
+int weighted_beam_select(const float* logits_a, long lda, const float* logits_b, long ldb, int V, float alpha, const omr_beam_desc* bp,
+                         const omr_grammar_desc* g, int t, void* stream) {
     if (!logits_a || !logits_b || !bp || !beam_desc_ok(*bp)) return OMR_ERR_ARG;
     if (!beam_fits_vocab(*bp, V) || lda < V || ldb < V || t < 0 || t >= bp->max_len) return OMR_ERR_ARG;
-    launch_weighted_select(LogitRows{logits_a, lda}, LogitRows{logits_b, ldb}, V, alpha, *bp, t, stream);
+    launch_weighted_select(LogitRows{logits_a, lda}, LogitRows{logits_b, ldb}, V, alpha, *bp, g, t, stream);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }
 
 /* This entry wants the history exactly as long as the cache (the weighted one below: long enough for the run). */
-extern "C" int omr_beam_decode_steps(const omr_decode_desc* dp, const omr_beam_desc* bp, const int* mem_len, int t0, int n_steps, void* stream) {
+int beam_decode(const omr_decode_desc* dp, const omr_beam_desc* bp, const int* mem_len, const omr_grammar_desc* g, int t0, int n_steps, void* stream) {
     if (!dp || !bp || bp->max_len != dp->max_len) return OMR_ERR_ARG;
     const BeamModel bm = {dp, mem_len, bp->self_kv2};
-    auto select = [&](float* const* l32, int t) { launch_select(l32[0], (long)dp->ldv, dp->V, *bp, t, stream); };
+    auto select = [&](float* const* l32, int t) { launch_select(l32[0], (long)dp->ldv, dp->V, *bp, g, t, stream); };
     return beam_steps(&bm, 1, *bp, t0, n_steps, select, stream);
 }
 
 /* omr_beam_decode_steps over the weighted late fusion: ONE search state drives two models, and one weighted selection launch
  * ranks both models' logits.  bp->self_kv2 is model A's second cache, self_kv2_b model B's. */
-extern "C" int omr_weighted_beam_decode_steps(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
-                                              const omr_beam_desc* bp, void* self_kv2_b, float alpha, int t0, int n_steps, void* stream) {
+int weighted_beam_decode(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b, const omr_beam_desc* bp,
+                         void* self_kv2_b, const omr_grammar_desc* g, float alpha, int t0, int n_steps, void* stream) {
     if (!da || !db || !bp || da->V != db->V) return OMR_ERR_ARG;
     const BeamModel bm[2] = {{da, mem_len_a, bp->self_kv2}, {db, mem_len_b, self_kv2_b}};
     auto select = [&](float* const* l32, int t) {
-        launch_weighted_select(LogitRows{l32[0], (long)da->ldv}, LogitRows{l32[1], (long)db->ldv}, da->V, alpha, *bp, t, stream);
+        launch_weighted_select(LogitRows{l32[0], (long)da->ldv}, LogitRows{l32[1], (long)db->ldv}, da->V, alpha, *bp, g, t, stream);
     };
     return beam_steps(bm, 2, *bp, t0, n_steps, select, stream);
+}
+
+}  // namespace
+
+extern "C" int omr_beam_select(const float* logits, long ld, int V, const omr_beam_desc* bp, int t, void* stream) {
+    return beam_select(logits, ld, V, bp, nullptr, t, stream);
+}
+
+extern "C" int omr_weighted_beam_select(const float* logits_a, long lda, const float* logits_b, long ldb, int V, float alpha, const omr_beam_desc* bp, int t,
+                                        void* stream) {
+    return weighted_beam_select(logits_a, lda, logits_b, ldb, V, alpha, bp, nullptr, t, stream);
+}
+
+extern "C" int omr_beam_decode_steps(const omr_decode_desc* dp, const omr_beam_desc* bp, const int* mem_len, int t0, int n_steps, void* stream) {
+    return beam_decode(dp, bp, mem_len, nullptr, t0, n_steps, stream);
+}
+
+extern "C" int omr_weighted_beam_decode_steps(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
+                                              const omr_beam_desc* bp, void* self_kv2_b, float alpha, int t0, int n_steps, void* stream) {
+    return weighted_beam_decode(da, mem_len_a, db, mem_len_b, bp, self_kv2_b, nullptr, alpha, t0, n_steps, stream);
+}
+
+/* The same four under a token automaton (include/omr_hip.h "grammar-constrained decoding"; extensions of the host loop
+ * _Base.beam_search of this package's model.py): the descriptor is checked here, then the shared definition runs. */
+extern "C" int omr_beam_select_grammar(const float* logits, long ld, int V, const omr_beam_desc* bp, const omr_grammar_desc* g, int t, void* stream) {
+    if (!grammar_desc_ok(g)) return OMR_ERR_ARG;
+    return beam_select(logits, ld, V, bp, g, t, stream);
+}
+
+extern "C" int omr_weighted_beam_select_grammar(const float* logits_a, long lda, const float* logits_b, long ldb, int V, float alpha,
+                                                const omr_beam_desc* bp, const omr_grammar_desc* g, int t, void* stream) {
+    if (!grammar_desc_ok(g)) return OMR_ERR_ARG;
+    return weighted_beam_select(logits_a, lda, logits_b, ldb, V, alpha, bp, g, t, stream);
+}
+
+extern "C" int omr_beam_decode_steps_grammar(const omr_decode_desc* dp, const omr_beam_desc* bp, const int* mem_len, const omr_grammar_desc* g, int t0,
+                                             int n_steps, void* stream) {
+    if (!grammar_desc_ok(g)) return OMR_ERR_ARG;
+    return beam_decode(dp, bp, mem_len, g, t0, n_steps, stream);
+}
+
+extern "C" int omr_weighted_beam_decode_steps_grammar(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
+                                                      const omr_beam_desc* bp, void* self_kv2_b, const omr_grammar_desc* g, float alpha, int t0,
+                                                      int n_steps, void* stream) {
+    if (!grammar_desc_ok(g)) return OMR_ERR_ARG;
+    return weighted_beam_decode(da, mem_len_a, db, mem_len_b, bp, self_kv2_b, g, alpha, t0, n_steps, stream);
 }

@@ -171,24 +171,56 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 __global__ void argmax_kernel(const float* __restrict__ x0, int n, long ld, long* __restrict__ idx_out0, float* __restrict__ val_out0) {
     __shared__ float sv[256];
     __shared__ int si[256];
-    const float* x = x0 + (long)blockIdx.x * ld;
     long* idx_out = idx_out0 + blockIdx.x;
     float* val_out = val_out0 ? val_out0 + blockIdx.x : nullptr;
-    float best = -INFINITY; int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        float v = x[i];
-        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-    }
-    sv[threadIdx.x] = best; si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            float v2 = sv[threadIdx.x + o]; int i2 = si[threadIdx.x + o];
-            if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) { sv[threadIdx.x] = v2; si[threadIdx.x] = i2; }
-        }
-        __syncthreads();
-    }
+    argmax_row(x0 + (long)blockIdx.x * ld, n, threadIdx.x, sv, si);
     if (threadIdx.x == 0) { idx_out[0] = si[0] < n ? si[0] : 0; if (val_out) val_out[0] = sv[0]; }      // no comparison won (all NaN): index 0, as torch.argmax
+}
+
+// ---------------------------------------------------------------- grammar-constrained picks (omr_grammar_desc, include/omr_hip.h)
+// argmax_kernel over the tokens the automaton allows in the row's state: the row's `next` row is staged in LDS, every load is
+// masked (MaskedLoad), and the state advances by the picked token's class.  A pick the table forbids -- possible only where no
+// allowed logit compares greater than -inf, which the Grammar constructor's guarantee (every state allows a token) leaves to
+// rows of -inf / NaN -- leaves the state as it is: an invalid state is never written.
+__global__ __launch_bounds__(256) void grammar_pick_kernel(const float* __restrict__ x0, int n, long ld, omr_grammar_desc g, long* __restrict__ idx_out,
+                                                           float* __restrict__ val_out, long* __restrict__ tokens_out) {
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    __shared__ int next_row[256];
+    const int tid = threadIdx.x, row = blockIdx.x;
+    const int s = stage_next_row(g.next, g.S, g.C, g.state[row], tid, next_row);
+    __syncthreads();
+    argmax_row(x0 + (long)row * ld, n, tid, sv, si, MaskedLoad{g.cls, next_row});
+    if (tid == 0) {
+        const int pick = si[0] < n ? si[0] : 0;
+        idx_out[row] = pick;
+        if (val_out) val_out[row] = sv[0];
+        if (tokens_out) tokens_out[row] = pick;
+        const int ns = next_row[g.cls[pick]];
+        g.state[row] = ns >= 0 && ns < g.S ? ns : s;
+    }
+}
+
+// weighted_argmax_kernel the same way: BOTH logit rows are masked before their softmax statistics, one state per row drives both
+// models.
+__global__ __launch_bounds__(256) void weighted_grammar_pick_kernel(const float* __restrict__ la0, long lda, const float* __restrict__ lb0, long ldb, int n,
+                                                                    float wa, float wb, omr_grammar_desc g, long* __restrict__ idx_out,
+                                                                    float* __restrict__ prob_out, long* __restrict__ tokens_out) {
+    __shared__ float sa[256], sb[256];
+    __shared__ int si[256];
+    __shared__ int next_row[256];
+    const int tid = threadIdx.x, row = blockIdx.x;
+    const int s = stage_next_row(g.next, g.S, g.C, g.state[row], tid, next_row);
+    __syncthreads();
+    weighted_argmax_row(la0 + (long)row * lda, lb0 + (long)row * ldb, n, wa, wb, tid, sa, sb, si, MaskedLoad{g.cls, next_row});
+    if (tid == 0) {
+        const int pick = si[0] < n ? si[0] : 0;
+        idx_out[row] = pick;
+        if (prob_out) prob_out[row] = sa[0];
+        if (tokens_out) tokens_out[row] = pick;
+        const int ns = next_row[g.cls[pick]];
+        g.state[row] = ns >= 0 && ns < g.S ? ns : s;
+    }
 }
 
 // ---------------------------------------------------------------- weighted late fusion (weighted_multimodal/test.py:50-61)
@@ -202,23 +234,7 @@ __global__ void weighted_argmax_kernel(const float* __restrict__ la0, long lda, 
     __shared__ float sa[256], sb[256];
     __shared__ int si[256];
     const int tid = threadIdx.x, row = blockIdx.x;
-    const float* __restrict__ la = la0 + (long)row * lda;
-    const float* __restrict__ lb = lb0 + (long)row * ldb;
-    const MixStats st = weighted_mix_stats(la, lb, n, tid, sa, sb);
-    float best = -INFINITY; int bi = 0x7fffffff;
-    for (int i = tid; i < n; i += 256) {
-        const float v = weighted_mix(la[i], lb[i], st, wa, wb);
-        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-    }
-    sa[tid] = best; si[tid] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-            const float v2 = sa[tid + o]; const int i2 = si[tid + o];
-            if (v2 > sa[tid] || (v2 == sa[tid] && i2 < si[tid])) { sa[tid] = v2; si[tid] = i2; }
-        }
-        __syncthreads();
-    }
+    weighted_argmax_row(la0 + (long)row * lda, lb0 + (long)row * ldb, n, wa, wb, tid, sa, sb, si);
     if (tid == 0) {
         const int pick = si[0] < n ? si[0] : 0;      // no comparison won (all NaN): index 0, never past the row
         idx_out[row] = pick;
@@ -430,6 +446,30 @@ extern "C" int omr_weighted_argmax(const float* logits_a, const float* logits_b,
 extern "C" int omr_argmax(const float* x, int rows, int n, long ld, long* idx_out, float* val_out, void* stream) {
     if (n <= 0 || rows <= 0 || ld < n) return OMR_ERR_ARG;
     hipLaunchKernelGGL(argmax_kernel, rows, 256, 0, (hipStream_t)stream, x, n, ld, idx_out, val_out);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+// the descriptor check every grammar entry shares (declared in omr_common.h)
+bool grammar_desc_ok(const omr_grammar_desc* g) {
+    return g && g->cls && g->next && g->state && g->C >= 1 && g->C <= OMR_GRAMMAR_MAX_CLASSES && g->S >= 1;
+}
+
+extern "C" int omr_grammar_pick(const float* logits, long ld, int rows, int n, const omr_grammar_desc* g, long* idx_out, float* val_out,
+                                long* tokens_out, void* stream) {
+    if (!grammar_desc_ok(g)) return OMR_ERR_ARG;
+    if (n <= 0 || rows <= 0 || ld < n || !logits || !idx_out) return OMR_ERR_ARG;
+    hipLaunchKernelGGL(grammar_pick_kernel, rows, 256, 0, (hipStream_t)stream, logits, n, ld, *g, idx_out, val_out, tokens_out);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+extern "C" int omr_weighted_grammar_pick(const float* logits_a, long lda, const float* logits_b, long ldb, int rows, int n, float alpha,
+                                         const omr_grammar_desc* g, long* idx_out, float* prob_out, long* tokens_out, void* stream) {
+    if (!grammar_desc_ok(g)) return OMR_ERR_ARG;
+    if (rows < 1 || n < 1 || lda < n || ldb < n || !logits_a || !logits_b || !idx_out) return OMR_ERR_ARG;
+    hipLaunchKernelGGL(weighted_grammar_pick_kernel, rows, 256, 0, (hipStream_t)stream, logits_a, lda, logits_b, ldb, n, alpha,
+                       (float)(1.0 - (double)alpha), *g, idx_out, prob_out, tokens_out);      // the weights as omr_weighted_argmax_rows rounds them
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }

@@ -152,6 +152,51 @@ int attn_fwd_split_partials_rows(int dtype, const void* q, const void* k, const 
                                  long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
                                  const int* kv_len, const int* kv_start, float* split_ws, long split_ws_floats, int* nsplit, void* stream);
 
+// How a row body reads x[i].  PlainLoad: the value.  MaskedLoad (grammar-constrained decoding, omr_grammar_desc of include/omr_hip.h): -inf where the
+// token automaton forbids token i in the row's current state -- next_row[cls[i]] < 0, next_row being that state's row of the
+// transition table (C <= 256 ints, staged in LDS once per row by stage_next_row) and cls the class of every vocabulary entry
+// (V bytes of global memory, shared by all rows).  The value is replaced BEFORE any comparison or expf, so a NaN or +inf in a
+// forbidden column cannot reach a maximum, a sum or a pick.
+struct PlainLoad {
+    __device__ __forceinline__ float operator()(const float* __restrict__ x, int i) const { return x[i]; }
+};
+struct MaskedLoad {
+    const unsigned char* __restrict__ cls; const int* next_row;
+    __device__ __forceinline__ float operator()(const float* __restrict__ x, int i) const { return next_row[cls[i]] < 0 ? -INFINITY : x[i]; }
+};
+// Row `state` (clamped into [0, S)) of next [S][C] into next_row[256] (LDS; entries >= C: forbidden) by the 256 threads tid of a
+// group; the caller synchronises before the first masked load.  -> the clamped state.
+__device__ __forceinline__ int stage_next_row(const int* __restrict__ next, int S, int C, int state, int tid, int* next_row) {
+    const int s = min(max(state, 0), S - 1);
+    next_row[tid] = tid < C ? next[(long)s * C + tid] : -1;
+    return s;
+}
+
+// Arg-max of ONE row by a group of 256 threads (every thread of the WORKGROUP must call it): first index of the maximum
+// (torch.argmax's tie rule).  On return sv[0] holds the maximum and si[0] its index (0x7fffffff when no comparison was won: a row
+// of NaN or -inf), visible to every thread.  One definition for argmax_kernel and the constrained pick (elementwise.hip).
+template <typename Load = PlainLoad>
+__device__ __forceinline__ void argmax_row(const float* __restrict__ x, int n, int tid, float* sv, int* si, Load load = Load()) {
+    float best = -INFINITY; int bi = 0x7fffffff;
+    for (int i = tid; i < n; i += 256) {
+        float v = load(x, i);
+        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+    }
+    sv[tid] = best; si[tid] = bi;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+            float v2 = sv[tid + o]; int i2 = si[tid + o];
+            if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
+        }
+        __syncthreads();
+    }
+}
+
+// elementwise.hip -> decode.hip, decode_beam.hip: non-NULL tables and state, 1 <= C <= 256, S >= 1
+struct omr_grammar_desc;
+bool grammar_desc_ok(const omr_grammar_desc* g);
+
 // Top-k log-probabilities of ONE row by a group of 256 threads (tid 0..255; every thread of the WORKGROUP must call it: it
 // synchronises with __syncthreads): emit(j, index, log_softmax(x)[index]) for the j-th largest, j < k, ties towards the smaller
 // index, with the same values in every thread.  A max / sum-exp pass, then k selection passes over the candidates that come
@@ -161,17 +206,18 @@ int attn_fwd_split_partials_rows(int dtype, const void* q, const void* k, const 
 // again; its values are NaN.)  sv / si: 256 entries of LDS each, the group's own.
 // One definition for topk_logprob_kernel (elementwise.hip) and the beam selection (decode_beam.hip): the on-device beam search has
 // to rank the very floats the host route reads back.
-template <typename Emit>
-__device__ __forceinline__ void topk_logprob_row(const float* __restrict__ x, int n, int k, int tid, float* sv, int* si, Emit emit) {
+// load: how x[i] is read (PlainLoad; MaskedLoad renormalises over the allowed tokens).
+template <typename Emit, typename Load = PlainLoad>
+__device__ __forceinline__ void topk_logprob_row(const float* __restrict__ x, int n, int k, int tid, float* sv, int* si, Emit emit, Load load = Load()) {
     float mx = -INFINITY;
-    for (int i = tid; i < n; i += 256) mx = fmaxf(mx, x[i]);
+    for (int i = tid; i < n; i += 256) mx = fmaxf(mx, load(x, i));
     sv[tid] = mx;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) sv[tid] = fmaxf(sv[tid], sv[tid + o]); __syncthreads(); }
     mx = sv[0];
     __syncthreads();
     float se = 0.f;
-    for (int i = tid; i < n; i += 256) se += expf(x[i] - mx);
+    for (int i = tid; i < n; i += 256) se += expf(load(x, i) - mx);
     sv[tid] = se;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) sv[tid] += sv[tid + o]; __syncthreads(); }
@@ -181,7 +227,7 @@ __device__ __forceinline__ void topk_logprob_row(const float* __restrict__ x, in
     for (int j = 0; j < k; ++j) {
         float best = -INFINITY; int bi = 0x7fffffff;
         for (int i = tid; i < n; i += 256) {
-            const float v = x[i];
+            const float v = load(x, i);
             const bool cand = v < last_v || (v == last_v && i > last_i);
             if (cand && (v > best || (v == best && i < bi))) { best = v; bi = i; }
         }
@@ -205,16 +251,18 @@ __device__ __forceinline__ void topk_logprob_row(const float* __restrict__ x, in
 // strided partition and the halving trees of weighted_argmax_kernel (elementwise.hip), which calls it.  sa / sb: 256 entries
 // of LDS each, the group's own; free again on return.
 struct MixStats { float ma, mb, za, zb; };
-__device__ __forceinline__ MixStats weighted_mix_stats(const float* __restrict__ la, const float* __restrict__ lb, int n, int tid, float* sa, float* sb) {
+template <typename Load = PlainLoad>
+__device__ __forceinline__ MixStats weighted_mix_stats(const float* __restrict__ la, const float* __restrict__ lb, int n, int tid, float* sa, float* sb,
+                                                       Load load = Load()) {
     float ma = -INFINITY, mb = -INFINITY;
-    for (int i = tid; i < n; i += 256) { ma = fmaxf(ma, la[i]); mb = fmaxf(mb, lb[i]); }
+    for (int i = tid; i < n; i += 256) { ma = fmaxf(ma, load(la, i)); mb = fmaxf(mb, load(lb, i)); }
     sa[tid] = ma; sb[tid] = mb;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) { sa[tid] = fmaxf(sa[tid], sa[tid + o]); sb[tid] = fmaxf(sb[tid], sb[tid + o]); } __syncthreads(); }
     ma = sa[0]; mb = sb[0];
     __syncthreads();
     float ea = 0.f, eb = 0.f;
-    for (int i = tid; i < n; i += 256) { ea += expf(la[i] - ma); eb += expf(lb[i] - mb); }
+    for (int i = tid; i < n; i += 256) { ea += expf(load(la, i) - ma); eb += expf(load(lb, i) - mb); }
     sa[tid] = ea; sb[tid] = eb;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) { sa[tid] += sa[tid + o]; sb[tid] += sb[tid + o]; } __syncthreads(); }
@@ -228,21 +276,44 @@ __device__ __forceinline__ float weighted_mix(float la_i, float lb_i, const MixS
     return __fadd_rn(__fmul_rn(wa, expf(la_i - st.ma) / st.za), __fmul_rn(wb, expf(lb_i - st.mb) / st.zb));
 }
 
+// Arg-max of the mixed distribution of ONE pair of rows by a group of 256 threads (every thread of the WORKGROUP must call it):
+// on return sa[0] holds the largest weighted_mix and si[0] its first index (0x7fffffff: no comparison won).  One definition for
+// weighted_argmax_kernel and the constrained weighted pick (elementwise.hip); sa / sb / si: 256 entries of LDS each.
+template <typename Load = PlainLoad>
+__device__ __forceinline__ void weighted_argmax_row(const float* __restrict__ la, const float* __restrict__ lb, int n, float wa, float wb, int tid,
+                                                    float* sa, float* sb, int* si, Load load = Load()) {
+    const MixStats st = weighted_mix_stats(la, lb, n, tid, sa, sb, load);
+    float best = -INFINITY; int bi = 0x7fffffff;
+    for (int i = tid; i < n; i += 256) {
+        const float v = weighted_mix(load(la, i), load(lb, i), st, wa, wb);
+        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+    }
+    sa[tid] = best; si[tid] = bi;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+            const float v2 = sa[tid + o]; const int i2 = si[tid + o];
+            if (v2 > sa[tid] || (v2 == sa[tid] && i2 < si[tid])) { sa[tid] = v2; si[tid] = i2; }
+        }
+        __syncthreads();
+    }
+}
+
 // topk_logprob_row for the mixed distribution p = weighted_mix(la, lb) (beam search over the weighted late fusion; an
 // extension: the reference decodes greedily, weighted_multimodal/test.py:50-61): emit(j, index, logf(p[index])) for the j-th
 // largest p, j < k, ties towards the smaller index, the same values in every thread.  Every selection pass recomputes p by the
 // one expression above, so k = 1 is weighted_argmax_kernel's pick and a row's result does not depend on the grid.  p = 0
 // (both exponentials underflowed) is a candidate like any other and emits -inf.  One definition for weighted_topk_logprob_kernel
 // (elementwise.hip) and the weighted beam selection (decode_beam.hip).
-template <typename Emit>
+template <typename Emit, typename Load = PlainLoad>
 __device__ __forceinline__ void weighted_topk_logprob_row(const float* __restrict__ la, const float* __restrict__ lb, int n, float wa, float wb, int k,
-                                                          int tid, float* sa, float* sb, int* si, Emit emit) {
-    const MixStats st = weighted_mix_stats(la, lb, n, tid, sa, sb);
+                                                          int tid, float* sa, float* sb, int* si, Emit emit, Load load = Load()) {
+    const MixStats st = weighted_mix_stats(la, lb, n, tid, sa, sb, load);
     float last_v = INFINITY; int last_i = -1;
     for (int j = 0; j < k; ++j) {
         float best = -INFINITY; int bi = 0x7fffffff;
         for (int i = tid; i < n; i += 256) {
-            const float v = weighted_mix(la[i], lb[i], st, wa, wb);
+            const float v = weighted_mix(load(la, i), load(lb, i), st, wa, wb);
             const bool cand = v < last_v || (v == last_v && i > last_i);
             if (cand && (v > best || (v == best && i < bi))) { best = v; bi = i; }
         }

@@ -459,6 +459,8 @@ class DecodeState:
     Rows are independent: B same-sized inputs decode in lock-step (batched greedy), or B hypotheses share one memory (beam).
     rows_per_memory > 1 (BeamDecodeState): B = memories * rows_per_memory rows, those of a memory reading its one K|V slot."""
 
+    gstate = None          # grammar.GrammarState: the automaton the picks of this state are constrained by (None: unconstrained)
+
     LAYER_PARAMS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
                     "norm1.weight", "norm1.bias", "multihead_attn.in_proj_weight", "multihead_attn.in_proj_bias",
                     "multihead_attn.out_proj.weight", "multihead_attn.out_proj.bias", "norm2.weight", "norm2.bias",
@@ -584,8 +586,23 @@ class DecodeState:
         if self.t + n > self.max_len:
             raise RuntimeError("decode_step beyond max_seq_len (positional-encoding table exhausted)")
 
+    def constrain(self, grammar):
+        """Decode under `grammar` (grammar.Grammar; None: unconstrained) from here on: one automaton state per row of this
+        decode state, at the start state.  -> the GrammarState, or None."""
+        self.gstate = None if grammar is None else grammar.bind(self.B, self.tok.device)
+        return self.gstate
+
     def _steps(self, t0: int, n_steps: int, toks, top1, logits) -> None:
-        if self.mem_len is None:
+        if self.gstate is not None:
+            if toks is None:
+                raise RuntimeError("a constrained decode state picks its tokens itself: use run()")
+            if self.mem_len is None:
+                lib().call("omr_decode_steps_grammar", ctypes.byref(self.desc), self.gstate.byref(), ptr(self.tok), t0, n_steps, ptr(toks), ptr(top1),
+                           ptr(logits), cur_stream())
+            else:
+                lib().call("omr_decode_steps_varlen_grammar", ctypes.byref(self.desc), ptr(self.mem_len), self.gstate.byref(), ptr(self.tok), t0, n_steps,
+                           ptr(toks), ptr(top1), ptr(logits), cur_stream())
+        elif self.mem_len is None:
             lib().call("omr_decode_steps", ctypes.byref(self.desc), ptr(self.tok), t0, n_steps, ptr(toks), ptr(top1), ptr(logits), cur_stream())
         else:
             lib().call("omr_decode_steps_varlen", ctypes.byref(self.desc), ptr(self.mem_len), ptr(self.tok), t0, n_steps, ptr(toks), ptr(top1),
@@ -680,8 +697,12 @@ class SlotDecodeState(DecodeState):
         t_max = self.begin(n_steps)
         toks = torch.empty((n_steps, self.B), dtype=torch.int64, device=self.tok.device)
         top1 = torch.empty((n_steps, self.B), dtype=torch.float32, device=self.tok.device)
-        lib().call("omr_decode_steps_rows", ctypes.byref(self.desc), ptr(self.mem_len), ptr(self.pos), t_max, ptr(self.tok), n_steps, ptr(toks),
-                   ptr(top1), None, cur_stream())
+        if self.gstate is not None:
+            lib().call("omr_decode_steps_rows_grammar", ctypes.byref(self.desc), ptr(self.mem_len), ptr(self.pos), t_max, self.gstate.byref(),
+                       ptr(self.tok), n_steps, ptr(toks), ptr(top1), None, cur_stream())
+        else:
+            lib().call("omr_decode_steps_rows", ctypes.byref(self.desc), ptr(self.mem_len), ptr(self.pos), t_max, ptr(self.tok), n_steps, ptr(toks),
+                       ptr(top1), None, cur_stream())
         self.advance(n_steps)
         return toks, top1
 
@@ -789,7 +810,11 @@ class BeamDecodeState(DecodeState):
         """Run n_steps positions of every input (decode step, selection, cache reorder) without a host round trip."""
         if n_steps < 1 or self.t + n_steps > self.max_len:
             raise RuntimeError("beam decode beyond max_seq_len (positional-encoding table exhausted)")
-        lib().call("omr_beam_decode_steps", ctypes.byref(self.desc), ctypes.byref(self.bdesc), ptr(self.mem_len), self.t, n_steps, cur_stream())
+        if self.gstate is not None:
+            lib().call("omr_beam_decode_steps_grammar", ctypes.byref(self.desc), ctypes.byref(self.bdesc), ptr(self.mem_len), self.gstate.byref(), self.t,
+                       n_steps, cur_stream())
+        else:
+            lib().call("omr_beam_decode_steps", ctypes.byref(self.desc), ctypes.byref(self.bdesc), ptr(self.mem_len), self.t, n_steps, cur_stream())
         self.t += n_steps
 
     def done(self) -> List[bool]:
@@ -831,12 +856,23 @@ class WeightedBeamState:
         self.bdesc = self.search.bdesc
         self.bdesc.self_kv2, self.bdesc.last_logits = self.kv2_a.data_ptr(), None
 
+    gstate = None          # grammar.GrammarState over the N * beam rows: ONE automaton state per row drives both models
+
+    def constrain(self, grammar):
+        """DecodeState.constrain for the search both models share."""
+        self.gstate = None if grammar is None else grammar.bind(self.st_a.B, self.st_a.tok.device)
+        return self.gstate
+
     def run(self, n_steps: int) -> None:
         """n_steps positions of every pair (both models' steps, the weighted selection, both cache reorders), no host round trip."""
         if n_steps < 1 or self.t + n_steps > self.max_len:
             raise RuntimeError("weighted beam decode beyond a model's max_seq_len (positional-encoding table exhausted)")
-        lib().call("omr_weighted_beam_decode_steps", ctypes.byref(self.st_a.desc), ptr(self.st_a.mem_len), ctypes.byref(self.st_b.desc),
-                   ptr(self.st_b.mem_len), ctypes.byref(self.bdesc), ptr(self.kv2_b), self.alpha, self.t, n_steps, cur_stream())
+        if self.gstate is not None:
+            lib().call("omr_weighted_beam_decode_steps_grammar", ctypes.byref(self.st_a.desc), ptr(self.st_a.mem_len), ctypes.byref(self.st_b.desc),
+                       ptr(self.st_b.mem_len), ctypes.byref(self.bdesc), ptr(self.kv2_b), self.gstate.byref(), self.alpha, self.t, n_steps, cur_stream())
+        else:
+            lib().call("omr_weighted_beam_decode_steps", ctypes.byref(self.st_a.desc), ptr(self.st_a.mem_len), ctypes.byref(self.st_b.desc),
+                       ptr(self.st_b.mem_len), ctypes.byref(self.bdesc), ptr(self.kv2_b), self.alpha, self.t, n_steps, cur_stream())
         self.t += n_steps
 
     def done(self) -> List[bool]:
@@ -850,5 +886,7 @@ class WeightedBeamState:
         """Back to position 0 over the same pairs, with another alpha if given: the initial search block is uploaded again."""
         self.search.rewind()
         self.t = 0
+        if self.gstate is not None:
+            self.gstate.reset()
         if alpha is not None:
             self.alpha = float(alpha)

@@ -41,6 +41,37 @@ def refill_option(fn):
     return call
 
 
+_UNSET = object()
+_GRAMMAR = contextvars.ContextVar("omr_grammar", default=_UNSET)
+
+
+def grammar_option(fn):
+    """Gives a decode entry point the keyword `grammar` (a grammar.Grammar, or None: unconstrained), like `refill_option`: the
+    function's own parameter list stays as it is and the value holds for the duration of the call; the decode routes ask
+    `active_grammar`.  Without the keyword an outer call's choice holds, and with no outer call the model's `decode_grammar`."""
+    @functools.wraps(fn)
+    def call(*args, grammar=_UNSET, **kwargs):
+        if grammar is _UNSET:
+            return fn(*args, **kwargs)
+        token = _GRAMMAR.set(grammar)
+        try:
+            return fn(*args, **kwargs)
+        finally:
+            _GRAMMAR.reset(token)
+    return call
+
+
+def active_grammar(model):
+    """The automaton the decode under way is constrained by, or None: the `grammar` keyword of the evaluation call if one was
+    given (`grammar_option`), else `model.decode_grammar`; checked against the model's vocabulary."""
+    from .grammar import check_grammar
+    from .synthetic import EOS_TOKEN
+    g = _GRAMMAR.get()
+    if g is _UNSET:
+        g = getattr(model, "decode_grammar", None)
+    return check_grammar(g, len(model.w2i), model.w2i[EOS_TOKEN])
+
+
 def plan_groups(lengths: Sequence[int], batch_size: int, window: int = 0) -> Tuple[List[int], List[List[int]]]:
     """-> (singles, groups) over the indices of `lengths` (memory lengths in tokens).  singles: memories decoded alone at batch
     size 1 -- at most MIN_RAGGED_MEMORY tokens (such a row alone takes another attention kernel than the ragged batch) or
@@ -79,14 +110,18 @@ def plan_pair_groups(len_a: Sequence[int], len_b: Sequence[int], batch_size: int
 
 
 def decode_rows(step: Callable, rows: int, eos: int, budget: int, sync_every: int,
-                want_probs: bool = False) -> Tuple[List[List[int]], List[List[float]]]:
+                want_probs: bool = False, gstate=None) -> Tuple[List[List[int]], List[List[float]]]:
     """THE chunked read-back loop of every greedy decode (one model or two in lock-step, one row or a ragged batch): ->
     (token ids, top-1 values) per row, each row cut after its <eos> (`eos`, kept) or after `budget` positions.
     step(n) runs up to n further positions of all rows and returns (tokens, values) as host lists [m][rows], 1 <= m <= n
     -- values only with want_probs, else None; it raises when it cannot advance.  The chosen tokens reach the next position
     on the device, so the loop handles host lists only: the caller's `step` does the one read-back (two with values) per
     chunk.  What a finished row computed after its <eos> is dropped (at most sync_every - 1 positions in vain); `step` is
-    not asked again once every row is done.  Without want_probs the value lists stay empty."""
+    not asked again once every row is done.  Without want_probs the value lists stay empty.
+    gstate (grammar.GrammarState, or None): the automaton state `step` decodes under; every row is put to the start state here,
+    before the first position, and the device advances it from then on (a finished row sits in the sink state)."""
+    if gstate is not None:
+        gstate.reset()
     out: List[List[int]] = [[] for _ in range(rows)]
     values: List[List[float]] = [[] for _ in range(rows)]
     done = [False] * rows
@@ -111,7 +146,7 @@ def stream_order(lengths: Sequence[int]) -> List[int]:
 
 
 def decode_stream(step: Callable, admit: Callable, order: Sequence[int], rows: int, eos: int, budget: int, sync_every: int,
-                  want_probs: bool = False) -> Tuple[List[List[int]], List[List[float]]]:
+                  want_probs: bool = False, gstate=None) -> Tuple[List[List[int]], List[List[float]]]:
     """decode_rows with a QUEUE (continuous batching): `rows` slots decode the inputs `order` (a permutation of
     0 .. len(order) - 1, admitted in that order) -> (token ids, top-1 values) per INPUT index, each cut after its <eos> (kept)
     or after `budget` positions of that input.  After every chunk the finished rows are cut, and each freed slot goes to the
@@ -119,7 +154,9 @@ def decode_stream(step: Callable, admit: Callable, order: Sequence[int], rows: i
     admit(slot, index) hands `slot` to input `index`, which starts at position 0; admit(slot, None) leaves it idle (nothing
     waits; whatever it computes is dropped).  step(n) runs n further positions of all slots and returns (tokens, values) as host
     lists [m][rows], 1 <= m <= n -- values only with want_probs, else None; it raises when it cannot advance.  n never takes a
-    live row past its budget.  Like decode_rows this touches host lists and the two callbacks only."""
+    live row past its budget.  Like decode_rows this touches host lists and the two callbacks only -- and gstate
+    (grammar.GrammarState, or None), the automaton state `step` decodes under: a slot's entry is put to the start state at the
+    read-back that admits its next input, where `admit` sets its token."""
     n_in = len(order)
     if sorted(order) != list(range(n_in)):
         raise ValueError("decode_stream: `order` must be a permutation of the input indices")
@@ -137,6 +174,8 @@ def decode_stream(step: Callable, admit: Callable, order: Sequence[int], rows: i
         holds[b] = waiting.pop() if waiting else None
         used[b] = 0
         admit(b, holds[b])
+        if gstate is not None:
+            gstate.reset_row(b)
 
     for b in range(rows):
         refill(b)

@@ -21,8 +21,9 @@ from ._lib import lib
 from .config import ModelConfig
 from .decoder import MAX_BEAM, Decoder, MultiheadAttention, _to_dev, takes_ragged_state
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
-from .evaluation import (WINDOW_BATCHES, Alignment, cells_and_boxes, decode_rows, decode_stream, grid_of, plan_align_groups, plan_groups, refill_enabled,
-                         refill_option, stream_order)
+from .evaluation import (WINDOW_BATCHES, Alignment, active_grammar, cells_and_boxes, decode_rows, decode_stream, grammar_option, grid_of,
+                         plan_align_groups, plan_groups, refill_enabled, refill_option, stream_order)
+from .grammar import host_mask
 from .lightning_shim import LightningModule
 from .metrics import compute_metrics, compute_metrics_sharded
 from .runtime import FlatModuleMixin
@@ -135,6 +136,7 @@ def _beam_option(fn):
 class _Base(FlatModuleMixin, LightningModule):
     _decode_beam = 1          # beam width `_predict` decodes with (set by _beam_option for the duration of a call)
     _refill_sync_every = 8    # positions per read-back of a refilled decode (evaluation.decode_stream); results do not depend on it
+    decode_grammar = None     # grammar.Grammar every decode of this model is constrained by unless a call says `grammar=` (evaluation.grammar_option)
     _refill_state_hook = None  # called with every SlotDecodeState `_greedy_stream` creates, before its first admission (tests)
 
     def _common_init(self, w2i, i2w, ytest_i2w, max_seq_len, attn_window, teacher_forcing_prob, config: Optional[ModelConfig]):
@@ -219,6 +221,8 @@ class _Base(FlatModuleMixin, LightningModule):
         if use_cache:
             ids, top1 = self._greedy_state(self.decoder.init_decode(memory), chunk, want_probs)
             return [self._i2w(t) for t in ids[0]], top1[0]
+        if active_grammar(self) is not None:
+            raise ValueError("a grammar constrains the KV-cached decode only: the pick of the full re-run is not on the device")
         y_in = torch.full((1, 1), self.w2i[SOS_TOKEN], dtype=torch.int64, device=memory.device)
         yhat: List[str] = []
         probs: List[float] = []
@@ -237,6 +241,7 @@ class _Base(FlatModuleMixin, LightningModule):
             y_in = torch.cat([y_in, idx.view(1, 1)], dim=1)
         return yhat, probs
 
+    @grammar_option
     @torch.no_grad()
     def greedy_batch(self, memory, sync_every: int = 8) -> List[List[str]]:
         """KV-cached greedy decode of B inputs at once (the reference loops bs = 1,
@@ -244,7 +249,8 @@ class _Base(FlatModuleMixin, LightningModule):
         alone (tests/test_model_gpu.py).  `memory` [B, S, d]: same-sized inputs.  A LIST of memories ([1, S_b, d] or [S_b, d])
         of different lengths -- padding would change the encoder features, so the reference pads nothing at inference -- is
         decoded as one ragged state (tests/test_ragged_decode_gpu.py); memories of at most 64 tokens go through `_greedy`.
-        Returns one word list per memory, in input order.  The host reads the chosen tokens back every `sync_every` steps only."""
+        Returns one word list per memory, in input order.  The host reads the chosen tokens back every `sync_every` steps only.
+        Keyword `grammar` (evaluation.grammar_option): every pick is the best token the automaton allows (`_greedy_state`)."""
         if not isinstance(memory, (list, tuple)):
             return self._words(self._greedy_state(self.decoder.init_decode(memory), sync_every)[0])
         mems = self.decoder.memory_list(memory)
@@ -267,7 +273,11 @@ class _Base(FlatModuleMixin, LightningModule):
     def _greedy_state(self, state, sync_every: int, want_probs: bool = False):
         """Greedy decode of every row of a decode state at position 0 (evaluation.decode_rows): -> (token ids, top-1 logits)
         per row, each cut after its <eos> or max_seq_len tokens.  The logits (want_probs; else empty lists) are the floats
-        get_pred_seq_and_pred_prob_seq returns for that row alone."""
+        get_pred_seq_and_pred_prob_seq returns for that row alone.  Under a grammar (evaluation.active_grammar) every pick is
+        the largest logit among the tokens the automaton allows in the row's state, that logit is the value returned, and the
+        states advance on the device (DecodeState.constrain); a row that reaches max_seq_len before an accepting state returns a
+        valid prefix."""
+        gstate = state.constrain(active_grammar(self))
         tok = torch.full((state.B, 1), self.w2i[SOS_TOKEN], dtype=torch.int64, device=state.tok.device)
 
         def step(n: int):
@@ -277,7 +287,7 @@ class _Base(FlatModuleMixin, LightningModule):
             top1_h = top1.cpu().tolist() if want_probs else None
             return toks.cpu().tolist(), top1_h                        # one device sync for the whole chunk
 
-        return decode_rows(step, state.B, self.w2i[EOS_TOKEN], self.max_seq_len, sync_every, want_probs)
+        return decode_rows(step, state.B, self.w2i[EOS_TOKEN], self.max_seq_len, sync_every, want_probs, gstate)
 
     def _greedy_stream(self, mems: List[torch.Tensor], rows: int, want_probs: bool = False):
         """Greedy decode of memories that all take a ragged state through ONE decode state of `rows` slots, a finished row's
@@ -288,6 +298,7 @@ class _Base(FlatModuleMixin, LightningModule):
         state = self.decoder.init_slot_decode(min(rows, len(mems)), max(lens), mems[0].device, self.w2i[SOS_TOKEN])
         if self._refill_state_hook is not None:
             self._refill_state_hook(state)
+        gstate = state.constrain(active_grammar(self))
 
         def admit(slot: int, i: Optional[int]) -> None:
             state.admit(slot, None if i is None else mems[i])
@@ -297,7 +308,8 @@ class _Base(FlatModuleMixin, LightningModule):
             top1_h = top1.cpu().tolist() if want_probs else None
             return toks.cpu().tolist(), top1_h                        # one device sync for the whole chunk
 
-        return decode_stream(step, admit, stream_order(lens), state.B, self.w2i[EOS_TOKEN], self.max_seq_len, self._refill_sync_every, want_probs)
+        return decode_stream(step, admit, stream_order(lens), state.B, self.w2i[EOS_TOKEN], self.max_seq_len, self._refill_sync_every, want_probs,
+                             gstate)
 
     @torch.no_grad()
     def _predict(self, items: Iterable, encode: Callable[[object], torch.Tensor], batch_size: int, want_probs: bool = False):
@@ -309,7 +321,10 @@ class _Base(FlatModuleMixin, LightningModule):
         batch_size // beam inputs at a time (`beam_search_batch`: a group has at most batch_size rows).
         Called with refill=True (evaluation.refill_option; greedy only): the memories of a window that take a ragged state stream through ONE decode state of
         min(batch_size, count) slots (`_greedy_stream`) instead of running group by group until each group's longest row ends;
-        a decoder whose widths omr_decode_steps_rows does not take decodes in groups as without the flag."""
+        a decoder whose widths omr_decode_steps_rows does not take decodes in groups as without the flag.
+        Called with grammar= (evaluation.grammar_option), or on a model with `decode_grammar`: every route above decodes under
+        that automaton (grammar.Grammar); with None nothing is allocated or launched for it.  A prediction that reaches
+        max_seq_len before an accepting state is a valid prefix."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         beam = 1 if want_probs else self._decode_beam          # predict_with_probs takes no beam
@@ -428,12 +443,17 @@ class _Base(FlatModuleMixin, LightningModule):
         finally:
             self.train(was_training)
 
+    @grammar_option
     @torch.no_grad()
     def beam_search(self, memory: torch.Tensor, beam: int = 4) -> Tuple[List[str], float]:
         """Beam-search decode of ONE input (BASELINE config C5; an extension -- the reference only decodes greedily).  The
         `beam` hypotheses are the batch rows of the KV-cached step; scores are sums of log-probabilities (no length
-        normalisation); beam = 1 reproduces `_greedy` token for token.  Returns (words incl. <eos> if reached, score)."""
+        normalisation); beam = 1 reproduces `_greedy` token for token.  Returns (words incl. <eos> if reached, score).
+        Keyword `grammar` (evaluation.grammar_option): the logits of the tokens the automaton forbids in a hypothesis' state are
+        -inf before the log-softmax, and a candidate the table forbids is dropped whatever its value."""
         assert memory.shape[0] == 1 and beam >= 1
+        grammar = active_grammar(self)
+        gstates = [grammar.start] * beam if grammar is not None else None
         sos, eos = self.w2i[SOS_TOKEN], self.w2i[EOS_TOKEN]
         dev = memory.device
         state = self.decoder.init_decode(memory)
@@ -445,9 +465,14 @@ class _Base(FlatModuleMixin, LightningModule):
         exhausted = True                                     # the loop ran out of positions with hypotheses still alive
         for _ in range(self.max_seq_len):
             logits = self.decoder.decode_step(tok, state)
-            idx, val = K.topk_logprob((logits if logits.dim() == 2 else logits.view(1, -1)).contiguous(), beam)
+            logits = logits if logits.dim() == 2 else logits.view(1, -1)
+            if grammar is not None:
+                logits = logits.masked_fill(~host_mask(grammar, gstates, logits.device), float("-inf"))
+            idx, val = K.topk_logprob(logits.contiguous(), beam)
             idx_h, val_h = idx.cpu().tolist(), val.cpu().tolist()
             cands = [(scores[b] + val_h[b][j], b, idx_h[b][j]) for b in range(beam) if scores[b] > float("-inf") for j in range(beam)]
+            if grammar is not None:
+                cands = [c for c in cands if grammar.walk([c[2]], gstates[c[1]])[0] >= 0]
             cands.sort(key=lambda c: (-c[0], c[1], c[2]))
             parents, new_tok, new_scores, new_seqs = [], [], [], []
             for sc, b, t in cands:
@@ -467,17 +492,21 @@ class _Base(FlatModuleMixin, LightningModule):
             state.reorder_rows(pidx)
             tok = torch.tensor(new_tok, dtype=torch.int64, device=dev).view(beam, 1)
             scores, seqs = new_scores, new_seqs
+            if grammar is not None:
+                gstates = [grammar.walk([t], gstates[b])[0] for b, t in zip(parents, new_tok)]
         if exhausted and scores[0] > best_done[0]:
             best_done = (scores[0], seqs[0])                          # ran out of length: the best unfinished hypothesis wins
         return [self._i2w(t) for t in best_done[1]], best_done[0]
 
+    @grammar_option
     @torch.no_grad()
     def beam_search_batch(self, memories, beam: int = 4, sync_every: int = 8) -> List[Tuple[List[str], float]]:
         """`beam_search` of N inputs at once, on the device (Decoder.init_beam_decode; csrc/decode.hip omr_beam_decode_steps):
         -> [(words, score)] in input order, each exactly what `beam_search(memory, beam)` returns for that input alone
         (tests/test_beam_batch_gpu.py).  memories: a list of [1, S_b, d] / [S_b, d] of different lengths.  The selection, the
         scores and the cache reorder stay on the device; the host reads the `done` flags every `sync_every` positions only
-        and the whole state once at the end.  Memories of at most 64 or more than 16 384 tokens go through `beam_search`."""
+        and the whole state once at the end.  Memories of at most 64 or more than 16 384 tokens go through `beam_search`.
+        Keyword `grammar` (evaluation.grammar_option): the constrained selection (omr_beam_decode_steps_grammar)."""
         if not 1 <= beam <= MAX_BEAM:
             raise ValueError(f"beam must be in 1..{MAX_BEAM}, got {beam}")
         if sync_every < 1:
@@ -498,6 +527,7 @@ class _Base(FlatModuleMixin, LightningModule):
     def _beam_state(self, mems, beam: int, sync_every: int) -> List[Tuple[List[str], float]]:
         """The search of `beam_search_batch` over memories that all take a ragged state: one BeamDecodeState, run to the end."""
         state = self.decoder.init_beam_decode(mems, beam, sos=self.w2i[SOS_TOKEN], eos=self.w2i[EOS_TOKEN])
+        state.constrain(active_grammar(self))
         left = self.max_seq_len
         while left > 0:
             n = min(sync_every, left)
@@ -627,6 +657,7 @@ class Transformer(_Base):
         assert x.size(0) == 1, "predict takes inputs of batch size 1 ([1, C, H, W]); their sizes may differ"
         return self.encode(x)
 
+    @grammar_option
     @refill_option
     @_beam_option
     @torch.no_grad()
@@ -637,14 +668,17 @@ class Transformer(_Base):
         greedy only): continuous batching, a finished row's slot goes to the next input (`_predict`); same predictions."""
         return self._predict(xs, self._encode_input, batch_size)
 
+    @grammar_option
     @refill_option
     @torch.no_grad()
     def predict_with_probs(self, xs: Iterable[torch.Tensor], batch_size: int = 32) -> Tuple[List[List[str]], List[List[float]]]:
         """get_pred_seq_and_pred_prob_seq (model.py:226-262) of inputs [1, C, H_b, W_b] of any size, decoded batch_size
         memories at a time: (words, top-1 logits) per input, in input order, each equal to the batch-size-1 call's.
-        Keyword `refill` (default False, `refill_option`): continuous batching (`_predict`), same values."""
+        Keyword `refill` (default False, `refill_option`): continuous batching (`_predict`), same values.
+        Keyword `grammar` (evaluation.grammar_option): the values are the top-1 ALLOWED logits."""
         return self._predict(xs, self._encode_input, batch_size, want_probs=True)
 
+    @grammar_option
     @refill_option
     @_beam_option
     @torch.no_grad()
@@ -871,6 +905,7 @@ class MultimodalTransformer(_Base):
         x, _ = self.encoder_forward(xi=xi, xa=xa, xli=None, xla=None, apply_teacher_forcing_modality=False)
         return x
 
+    @grammar_option
     @refill_option
     @_beam_option
     @torch.no_grad()
@@ -881,6 +916,7 @@ class MultimodalTransformer(_Base):
         only): continuous batching (`_predict`), same predictions."""
         return self._predict(pairs, self._encode_input, batch_size)
 
+    @grammar_option
     @refill_option
     @_beam_option
     @torch.no_grad()

@@ -17,6 +17,9 @@ pair.  A sequence of alphas re-runs only the decode: encoders and cross-attentio
 Beam search over the mixed distribution (`weighted_beam_search`, `weighted_beam_search_batch`, `weighted_predict(beam=)`,
 `weighted_evaluate(beam=)`) is an extension: the reference decodes the fusion greedily.  It is `_Base.beam_search` of model.py
 with the log of the mixed probability in place of log_softmax; beam = 1 is the weighted greedy decode.
+
+Every entry point takes the keyword `grammar` (evaluation.grammar_option; default: img_model.decode_grammar): both models'
+logits are masked by ONE automaton state per row before the mix (omr_weighted_grammar_pick, omr_weighted_beam_select_grammar).
 """
 from __future__ import annotations
 
@@ -31,7 +34,9 @@ import torch
 from . import kernels as K
 from ._lib import cur_stream, lib, ptr
 from .decoder import MAX_BEAM, WeightedBeamState, takes_ragged_state
-from .evaluation import WINDOW_BATCHES, decode_rows, decode_stream, plan_pair_groups, refill_enabled, refill_option, stream_order
+from .evaluation import (WINDOW_BATCHES, active_grammar, decode_rows, decode_stream, grammar_option, plan_pair_groups, refill_enabled, refill_option,
+                         stream_order)
+from .grammar import host_mask
 from .metrics import compute_metrics
 from .synthetic import EOS_TOKEN, SOS_TOKEN
 
@@ -69,19 +74,25 @@ def _decode_lockstep(st_i, st_a, img_model, audio_model, alpha: float, sync_ever
     assert st_i.V == st_a.V and st_i.B == st_a.B, "both models share the vocabulary (test.py:62) and decode the same rows"
     B, dev = st_i.B, st_i.tok.device
     tok = torch.full((B,), img_model.w2i[SOS_TOKEN], dtype=torch.int64, device=dev)      # the picked tokens stay here, on the device
+    grammar = active_grammar(img_model)
+    gstate = None if grammar is None else grammar.bind(B, dev)
 
     def step(n: int):
         n = min(n, st_i.max_len - st_i.t, st_a.max_len - st_a.t)
         if n <= 0:                                     # a live row outgrew the shorter positional table
             raise RuntimeError(_EXHAUSTED)
         toks = torch.empty((n, B), dtype=torch.int64, device=dev)
-        lib().call("omr_weighted_decode_steps_varlen", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
-                   float(alpha), ptr(tok), st_i.t, n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
+        if gstate is not None:
+            lib().call("omr_weighted_decode_steps_varlen_grammar", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
+                       gstate.byref(), float(alpha), ptr(tok), st_i.t, n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
+        else:
+            lib().call("omr_weighted_decode_steps_varlen", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
+                       float(alpha), ptr(tok), st_i.t, n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
         st_i.t += n
         st_a.t += n
         return toks.cpu().tolist(), None               # one device sync per chunk
 
-    ids, _ = decode_rows(step, B, img_model.w2i[EOS_TOKEN], max(img_model.max_seq_len, audio_model.max_seq_len), sync_every)
+    ids, _ = decode_rows(step, B, img_model.w2i[EOS_TOKEN], max(img_model.max_seq_len, audio_model.max_seq_len), sync_every, gstate=gstate)
     return [[img_model._i2w(t) for t in seq] for seq in ids]
 
 
@@ -96,6 +107,8 @@ def _decode_lockstep_stream(mems_i, mems_a, img_model, audio_model, alpha: float
     st_a = audio_model.decoder.init_slot_decode(rows, max(m.shape[0] for m in mems_a), dev, sos)
     assert st_i.V == st_a.V, "both models share the vocabulary (test.py:62)"
     tok = torch.full((rows,), sos, dtype=torch.int64, device=dev)      # the picked tokens stay here, on the device
+    grammar = active_grammar(img_model)
+    gstate = None if grammar is None else grammar.bind(rows, dev)
 
     def admit(slot: int, k: Optional[int]) -> None:
         st_i.admit(slot, None if k is None else mems_i[k])
@@ -109,17 +122,23 @@ def _decode_lockstep_stream(mems_i, mems_a, img_model, audio_model, alpha: float
         t_max = st_i.begin(n)
         st_a.begin(n)
         toks = torch.empty((n, rows), dtype=torch.int64, device=dev)
-        lib().call("omr_weighted_decode_steps_rows", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
-                   ptr(st_i.pos), t_max, float(alpha), ptr(tok), n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
+        if gstate is not None:
+            lib().call("omr_weighted_decode_steps_rows_grammar", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
+                       ptr(st_i.pos), t_max, gstate.byref(), float(alpha), ptr(tok), n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
+        else:
+            lib().call("omr_weighted_decode_steps_rows", ctypes.byref(st_i.desc), ptr(st_i.mem_len), ctypes.byref(st_a.desc), ptr(st_a.mem_len),
+                       ptr(st_i.pos), t_max, float(alpha), ptr(tok), n, ptr(toks), None, ptr(st_i.logits), ptr(st_a.logits), cur_stream())
         st_i.advance(n)
         st_a.advance(n)
         return toks.cpu().tolist(), None               # one device sync per chunk
 
     order = stream_order([mi.shape[0] + ma.shape[0] for mi, ma in zip(mems_i, mems_a)])
-    ids, _ = decode_stream(step, admit, order, rows, img_model.w2i[EOS_TOKEN], max(img_model.max_seq_len, audio_model.max_seq_len), sync_every)
+    ids, _ = decode_stream(step, admit, order, rows, img_model.w2i[EOS_TOKEN], max(img_model.max_seq_len, audio_model.max_seq_len), sync_every,
+                           gstate=gstate)
     return [[img_model._i2w(t) for t in seq] for seq in ids]
 
 
+@grammar_option
 @torch.no_grad()
 def weighted_prediction(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_model, alpha: float = 0.5, chunk: int = 16) -> List[str]:
     """weighted_multimodal/test.py:21-70, same signature and return value (the predicted words, <eos> included when reached).
@@ -133,6 +152,7 @@ def weighted_prediction(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_mod
     return _decode_lockstep(st_i, st_a, img_model, audio_model, alpha, chunk)[0]
 
 
+@grammar_option
 @torch.no_grad()
 def weighted_beam_search(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_model, alpha: float = 0.5, beam: int = 4) -> Tuple[List[str], float]:
     """Beam search of ONE pair over the weighted late fusion (an extension: the reference decodes it greedily,
@@ -149,6 +169,8 @@ def weighted_beam_search(xi: torch.Tensor, xa: torch.Tensor, img_model, audio_mo
 def _beam_search_memories(mem_i: torch.Tensor, mem_a: torch.Tensor, img_model, audio_model, alpha: float, beam: int) -> Tuple[List[str], float]:
     """weighted_beam_search from the two encoded memories [1, S, d]."""
     assert beam >= 1
+    grammar = active_grammar(img_model)          # both models' logits masked by each hypothesis' state; forbidden candidates dropped by the table
+    gstates = [grammar.start] * beam if grammar is not None else None
     sos, eos = img_model.w2i[SOS_TOKEN], img_model.w2i[EOS_TOKEN]
     st_i, st_a = img_model.decoder.init_decode(mem_i), audio_model.decoder.init_decode(mem_a)
     st_i.share_memory_between(beam)                          # every hypothesis reads the same memory K|V; own self-attention cache rows
@@ -164,9 +186,14 @@ def _beam_search_memories(mem_i: torch.Tensor, mem_a: torch.Tensor, img_model, a
         if t >= min(st_i.max_len, st_a.max_len):            # a live hypothesis outgrew the shorter positional table
             raise RuntimeError(_EXHAUSTED)
         li, la = (m.decoder.decode_step(tok, st).view(beam, -1) for m, st in ((img_model, st_i), (audio_model, st_a)))
+        if grammar is not None:
+            forbidden = ~host_mask(grammar, gstates, li.device)
+            li, la = li.masked_fill(forbidden, float("-inf")).contiguous(), la.masked_fill(forbidden, float("-inf")).contiguous()
         idx, val = K.weighted_topk_logprob(li, la, alpha, beam)
         idx_h, val_h = idx.cpu().tolist(), val.cpu().tolist()
         cands = [(scores[b] + val_h[b][j], b, idx_h[b][j]) for b in range(beam) if scores[b] > float("-inf") for j in range(beam)]
+        if grammar is not None:
+            cands = [c for c in cands if grammar.walk([c[2]], gstates[c[1]])[0] >= 0]
         cands.sort(key=lambda c: (-c[0], c[1], c[2]))
         parents, new_tok, new_scores, new_seqs = [], [], [], []
         for sc, b, tk in cands:
@@ -187,6 +214,8 @@ def _beam_search_memories(mem_i: torch.Tensor, mem_a: torch.Tensor, img_model, a
         st_a.reorder_rows(pidx)
         tok = torch.tensor(new_tok, dtype=torch.int64, device=dev).view(beam, 1)
         scores, seqs = new_scores, new_seqs
+        if grammar is not None:
+            gstates = [grammar.walk([tk], gstates[b])[0] for b, tk in zip(parents, new_tok)]
     if exhausted and scores[0] > best_done[0]:
         best_done = (scores[0], seqs[0])                      # ran out of length: the best unfinished hypothesis wins
     return [img_model._i2w(t) for t in best_done[1]], best_done[0]
@@ -207,6 +236,7 @@ def _run_beam_state(state: WeightedBeamState, img_model, audio_model, sync_every
     return [([img_model._i2w(t) for t in seq], score) for seq, score in state.results()]
 
 
+@grammar_option
 @torch.no_grad()
 def weighted_beam_search_batch(mems_i, mems_a, img_model, audio_model, alpha: float = 0.5, beam: int = 4,
                                sync_every: int = 8) -> List[Tuple[List[str], float]]:
@@ -230,6 +260,7 @@ def weighted_beam_search_batch(mems_i, mems_a, img_model, audio_model, alpha: fl
     if batched:
         state = WeightedBeamState(img_model.decoder, [mi[i] for i in batched], audio_model.decoder, [ma[i] for i in batched], beam,
                                   img_model.w2i[SOS_TOKEN], img_model.w2i[EOS_TOKEN], alpha)
+        state.constrain(active_grammar(img_model))
         for i, result in zip(batched, _run_beam_state(state, img_model, audio_model, sync_every)):
             out[i] = result
     return out
@@ -256,6 +287,7 @@ def _beam_window(mems_i, mems_a, img_model, audio_model, alphas: List[float], ba
     for g in groups:
         state = WeightedBeamState(img_model.decoder, [mems_i[i] for i in g], audio_model.decoder, [mems_a[i] for i in g], beam,
                                   img_model.w2i[SOS_TOKEN], img_model.w2i[EOS_TOKEN])
+        state.constrain(active_grammar(img_model))
         for k, alpha in enumerate(alphas):
             state.rewind(alpha)
             for i, (seq, _) in zip(g, _run_beam_state(state, img_model, audio_model, sync_every)):
@@ -319,6 +351,7 @@ def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[floa
         del mems_i, mems_a
 
 
+@grammar_option
 @beam_option
 @refill_option
 def weighted_predict(pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], img_model, audio_model, alpha: Union[float, Sequence[float]] = 0.5,
@@ -337,6 +370,7 @@ def weighted_predict(pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], img_mod
     return dict(zip(alphas, preds)) if many else preds[0]
 
 
+@grammar_option
 @beam_option
 @refill_option
 def weighted_evaluate(batches: Iterable, img_model, audio_model, alpha: Union[float, Sequence[float]] = 0.5, batch_size: int = 32):
