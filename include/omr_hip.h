@@ -678,6 +678,25 @@ int omr_ce_smooth_fwd(int dtype, const void* logits, const long* target, float* 
 int omr_ce_smooth_bwd(int dtype, const void* logits, const long* target, const float* lse, const double* acc3, void* dlogits, long M, int V,
                       long ldv, int pad_idx, float eps, float grad_scale, const float* grad_out, void* stream);
 
+/* Knowledge distillation (an extension: the reference trains from hard labels alone): the loss above on student logits [M][ldv] plus the
+ * KL divergence to one or two teachers' logits [M][ldt] (teacher_b nullable; both of dtype tdtype, which may differ from the student's), at
+ * temperature tau > 0, distillation weight lam in [0, 1] and teacher mix alpha in [0, 1] (alpha on teacher_a; without teacher_b alpha must be 1).
+ * Per live row over the columns < V:  q = alpha softmax(a / tau) + (1 - alpha) softmax(b / tau),  pt = softmax(x / tau),
+ *   nll = lse - logit[target],   kd = tau^2 sum_v q_v (log q_v - log pt_v)  (terms with q_v = 0 are 0),   objective = (1 - lam) nll + lam kd.
+ * lse4 = fp32 [4][M]: lse(x), lse(x / tau), lse(a / tau), lse(b / tau) (zeros on ignored rows and for an absent teacher_b); rowkd = fp32 [M];
+ * acc4 = {objective sum, live rows, nll sum, kd sum} (fp64); means3 = {loss, nll, kd} (fp32).  No atomics: two calls give the same bits.
+ * lam == 0 runs the kernels of omr_ce_fwd and never reads the teachers: means3[0], lse4[0][.] and acc4[0..1] have its bits, rowkd and
+ * lse4[1..3] are not written.  OMR_ERR_ARG before any launch: tau <= 0 or not finite, lam or alpha outside [0, 1] (NaN included),
+ * teacher_b == NULL with alpha != 1, ldt < V, ldv < V. */
+int omr_ce_distill_fwd(int dtype, const void* logits, long ldv, int tdtype, const void* teacher_a, const void* teacher_b, long ldt,
+                       const long* target, float* lse4, float* rowkd, double* acc4, float* means3, long M, int V, int pad_idx, float alpha,
+                       float tau, float lam, void* stream);
+/* dlogits = ((1 - lam) (softmax(x) - onehot) + lam tau (pt - q)) * grad_scale * grad_out / acc4[1] on live rows, +0 on the others and in the
+ * columns >= V; the teachers get no gradient.  lam == 0 runs the kernel of omr_ce_bwd.  The same refusals as the forward. */
+int omr_ce_distill_bwd(int dtype, const void* logits, long ldv, int tdtype, const void* teacher_a, const void* teacher_b, long ldt,
+                       const long* target, const float* lse4, const double* acc4, void* dlogits, long M, int V, int pad_idx, float alpha,
+                       float tau, float lam, float grad_scale, const float* grad_out, void* stream);
+
 /* ---- guarded optimizer step ------------------------------------------------------------------------------- */
 /* What the reference gets from Lightning: Trainer(precision="16-mixed") (src/train.py:153) puts every step behind GradScaler,
  * which skips optimizer.step() when a gradient holds inf / NaN (torch/amp/grad_scaler.py, _maybe_opt_step), and

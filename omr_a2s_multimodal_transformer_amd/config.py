@@ -107,6 +107,37 @@ class OptimConfig:
         return cls(**{k: v for k, v in d.items() if k in names})
 
 
+@dataclass
+class DistillConfig:
+    """Knowledge distillation (distill.Distillation; an extension: the reference trains from hard labels alone).  The training loss is
+    (1 - weight) nll + weight temperature^2 KL(q || softmax(student / temperature)) with the teachers' mix
+    q = alpha softmax(a / temperature) + (1 - alpha) softmax(b / temperature); a single teacher is taken with alpha = 1."""
+    weight: float = 0.5                  # share of the distillation term; 0 is the plain loss
+    temperature: float = 2.0
+    alpha: float = 0.5                   # weight of the first teacher (the image model of a cross-modal pair), as in the weighted late fusion
+
+    def __post_init__(self) -> None:
+        for name in ("weight", "temperature", "alpha"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"DistillConfig: {name} must be a number (got {v!r})")
+            setattr(self, name, float(v))
+        if not 0.0 <= self.weight <= 1.0:
+            raise ValueError(f"DistillConfig: weight must lie in [0, 1] (got {self.weight})")
+        if not (math.isfinite(self.temperature) and self.temperature > 0):
+            raise ValueError(f"DistillConfig: temperature must be finite and > 0 (got {self.temperature})")
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError(f"DistillConfig: alpha must lie in [0, 1] (got {self.alpha})")
+
+    def to_dict(self) -> Dict[str, Any]:
+        return asdict(self)
+
+    @classmethod
+    def from_dict(cls, d: Dict[str, Any]) -> "DistillConfig":
+        names = {f.name for f in fields(cls)}
+        return cls(**{k: v for k, v in d.items() if k in names})
+
+
 def lr_at(cfg: OptimConfig, k: int) -> float:
     """Learning rate of the k-th step() CALL (k = 0, 1, ...), in fp64 on the host.  Calls, not applied steps: a step the guard
     skips on the device still advances the schedule, so the host never waits for the decision.

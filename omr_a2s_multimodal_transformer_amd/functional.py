@@ -658,6 +658,62 @@ class SmoothCrossEntropyFn(Function):
         return dl, None, None, None, None
 
 
+class DistillCrossEntropyFn(Function):
+    """Hard-label cross-entropy plus the KL divergence to one or two teachers on row-major logits [M, V] (kernels.ce_distill_fwd) ->
+    (loss, nll, kd): the mean objective (1 - weight) nll + weight kd, and its two parts as outputs that carry no gradient.  The teachers
+    get no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits2d, target, teacher_a, teacher_b, V, pad_idx, alpha, temperature, weight):
+        means, lse4, _rowkd, acc4 = K.ce_distill_fwd(logits2d, target, teacher_a, teacher_b, V, pad_idx, alpha, temperature, weight)
+        ctx.cfg = (V, pad_idx, alpha, temperature, weight)
+        ctx.teachers = (teacher_a, teacher_b)              # no graph behind them: plain references, as the backward re-reads them
+        ctx.save_for_backward(logits2d, target, lse4, acc4)
+        nll, kd = means[1].view(()), means[2].view(())
+        ctx.mark_non_differentiable(nll, kd)
+        return means[0].view(()), nll, kd
+
+    @staticmethod
+    def backward(ctx, g, _g_nll, _g_kd):
+        V, pad_idx, alpha, temperature, weight = ctx.cfg
+        logits2d, target, lse4, acc4 = ctx.saved_tensors
+        teacher_a, teacher_b = ctx.teachers
+        dl = K.ce_distill_bwd(logits2d, target, teacher_a, teacher_b, lse4, acc4, V, pad_idx, alpha, temperature, weight, grad_out=g)
+        return dl, None, None, None, None, None, None, None, None
+
+
+def _rows_of_bvt(logits_bvt: Tensor) -> Tensor:
+    """[B, V, T] logits as the row-major [B * T, V] view the loss kernels take; a copy only when the strides are not the decoder's."""
+    B, V, T = logits_bvt.shape
+    rows = logits_bvt.permute(0, 2, 1)
+    if rows.stride(2) != 1 or rows.stride(1) % 8 or rows.stride(0) != T * rows.stride(1):
+        rows = rows.contiguous()
+    return rows.reshape(B * T, V)
+
+
+def cross_entropy_distill(logits_bvt: Tensor, target_bt: Tensor, teachers_bvt, pad_idx: int, alpha: float = 1.0, temperature: float = 2.0,
+                          weight: float = 0.5):
+    """Distillation loss on logits in the reference's [B, V, T] layout (the decoder's stride permutation of row-major [B * T, V]: no copy)
+    -> (loss, nll, kd).  teachers_bvt: one or two teachers' logits of the same shape, detached here; alpha weighs the first
+    (1 with a single teacher).  loss = (1 - weight) nll + weight kd with kd = tau^2 KL(q || softmax(student / tau)),
+    q = alpha softmax(a / tau) + (1 - alpha) softmax(b / tau), tau = temperature."""
+    teachers = (teachers_bvt,) if isinstance(teachers_bvt, Tensor) else tuple(teachers_bvt)
+    if len(teachers) not in (1, 2):
+        raise ValueError(f"cross_entropy_distill takes one or two teachers' logits, got {len(teachers)}")
+    K.check_distill(alpha, temperature, weight, len(teachers) == 2)
+    for t in teachers:
+        if tuple(t.shape) != tuple(logits_bvt.shape):
+            raise ValueError(f"teacher logits {tuple(t.shape)} do not have the student's shape {tuple(logits_bvt.shape)}")
+    if len(teachers) == 2 and teachers[0].dtype != teachers[1].dtype:
+        raise ValueError("the two teachers' logits must share one dtype")
+    V = logits_bvt.shape[1]
+    rows = [_rows_of_bvt(t.detach()) for t in teachers]
+    if len(rows) == 2 and rows[0].stride(0) != rows[1].stride(0):
+        rows = [r.contiguous() for r in rows]
+    return DistillCrossEntropyFn.apply(_rows_of_bvt(logits_bvt), target_bt.reshape(-1).contiguous(), rows[0], rows[1] if len(rows) == 2 else None,
+                                       V, pad_idx, float(alpha), float(temperature), float(weight))
+
+
 def cross_entropy(logits_bvt: Tensor, target_bt: Tensor, pad_idx: int, label_smoothing: float = 0.0, return_nll: bool = False):
     """Loss on logits in the reference's [B, V, T] layout.  The decoder produces them as a stride
     permutation of row-major [B*T, V], which is what the kernel consumes (no copy).

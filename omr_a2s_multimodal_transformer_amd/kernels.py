@@ -1090,5 +1090,69 @@ def ce_smooth_bwd(logits2d: Tensor, target: Tensor, lse: Tensor, acc3: Tensor, V
     return dl[:, :cols]
 
 
+def check_distill(alpha, temperature, weight, two_teachers: bool) -> Tuple[float, float, float]:
+    """The ranges omr_ce_distill_fwd accepts; refused here, before anything is allocated or launched."""
+    alpha, tau, lam = float(alpha), float(temperature), float(weight)
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise ValueError(f"distillation temperature must be finite and > 0, got {tau}")
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"distillation weight must be between 0.0 and 1.0, got {lam}")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"distillation alpha must be between 0.0 and 1.0, got {alpha}")
+    if not two_teachers and alpha != 1.0:
+        raise ValueError(f"distillation with one teacher takes alpha = 1, got {alpha}")
+    return alpha, tau, lam
+
+
+def _distill_teachers(logits2d: Tensor, teacher_a: Optional[Tensor], teacher_b: Optional[Tensor], V: int, lam: float):
+    """-> (tdtype code, ldt).  weight == 0 never reads the teachers: they may be None."""
+    if lam == 0.0 and teacher_a is None:
+        return dtype_code(logits2d.dtype), V
+    M = logits2d.shape[0]
+    require_cuda(teacher_a, teacher_b)
+    Ma, cols, ldt = _rows2d(teacher_a)
+    assert Ma == M and cols >= V, "teacher logits must have the student's rows and at least its V columns"
+    if teacher_b is not None:
+        assert teacher_b.dtype == teacher_a.dtype and _rows2d(teacher_b) == (M, cols, ldt), "the two teachers share dtype, shape and pitch"
+    return dtype_code(teacher_a.dtype), ldt
+
+
+def ce_distill_fwd(logits2d: Tensor, target: Tensor, teacher_a: Optional[Tensor], teacher_b: Optional[Tensor], V: int, pad_idx: int, alpha: float,
+                   temperature: float, weight: float):
+    """Hard-label cross-entropy plus the KL divergence to one or two teachers (omr_ce_distill_fwd): student logits2d [M, ldv >= V],
+    teacher logits [M, ldt >= V] (teacher_b may be None, then alpha = 1) -> (means fp32 [3] = {loss, nll, kd}, lse4 fp32 [4, M],
+    rowkd fp32 [M] or None, acc4 fp64 [4]).  weight == 0 runs ce_fwd's kernels (same bits), reads no teacher and has no rowkd."""
+    alpha, tau, lam = check_distill(alpha, temperature, weight, teacher_b is not None)
+    require_cuda(logits2d, target)
+    M, cols, ldv = _rows2d(logits2d)
+    assert cols >= V and target.numel() == M and target.dtype == torch.int64 and target.is_contiguous()
+    tdtype, ldt = _distill_teachers(logits2d, teacher_a, teacher_b, V, lam)
+    dev = logits2d.device
+    lse4 = torch.empty((4, M), dtype=torch.float32, device=dev)
+    rowkd = torch.empty(M, dtype=torch.float32, device=dev) if lam > 0 else None
+    acc4 = torch.empty(4, dtype=torch.float64, device=dev)
+    means = torch.empty(3, dtype=torch.float32, device=dev)
+    lib().call("omr_ce_distill_fwd", dtype_code(logits2d.dtype), ptr(logits2d), ldv, tdtype, ptr(teacher_a), ptr(teacher_b), ldt, ptr(target),
+               ptr(lse4), ptr(rowkd), ptr(acc4), ptr(means), M, V, pad_idx, alpha, tau, lam, cur_stream())
+    return means, lse4, rowkd, acc4
+
+
+def ce_distill_bwd(logits2d: Tensor, target: Tensor, teacher_a: Optional[Tensor], teacher_b: Optional[Tensor], lse4: Tensor, acc4: Tensor, V: int,
+                   pad_idx: int, alpha: float, temperature: float, weight: float, grad_scale: float = 1.0,
+                   grad_out: Optional[Tensor] = None) -> Tensor:
+    """((1 - weight)(softmax - onehot) + weight tau (softmax(x / tau) - q)) * grad_scale * grad_out / count.  weight == 0 runs ce_bwd's kernel."""
+    alpha, tau, lam = check_distill(alpha, temperature, weight, teacher_b is not None)
+    require_cuda(logits2d, target, grad_out)
+    if grad_out is not None:
+        assert grad_out.dtype == torch.float32 and grad_out.numel() == 1
+    M, cols, ldv = _rows2d(logits2d)
+    tdtype, ldt = _distill_teachers(logits2d, teacher_a, teacher_b, V, lam)
+    assert lse4.dtype == torch.float32 and tuple(lse4.shape) == (4, M) and lse4.is_contiguous()
+    dl = torch.empty((M, ldv), dtype=logits2d.dtype, device=logits2d.device)
+    lib().call("omr_ce_distill_bwd", dtype_code(logits2d.dtype), ptr(logits2d), ldv, tdtype, ptr(teacher_a), ptr(teacher_b), ldt, ptr(target),
+               ptr(lse4), ptr(acc4), ptr(dl), M, V, pad_idx, alpha, tau, lam, float(grad_scale), ptr(grad_out), cur_stream())
+    return dl[:, :cols]
+
+
 def round_up(n: int, m: int) -> int:
     return (n + m - 1) // m * m

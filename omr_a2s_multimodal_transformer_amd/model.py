@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import functional as Fn
 from . import kernels as K
 from ._lib import lib
-from .config import ModelConfig
+from .config import DistillConfig, ModelConfig
 from .decoder import MAX_BEAM, Decoder, MultiheadAttention, _to_dev, takes_ragged_state
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
 from .evaluation import (WINDOW_BATCHES, Alignment, active_grammar, cells_and_boxes, decode_rows, decode_stream, grammar_option, grid_of,
@@ -89,6 +89,29 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, logits_bvt: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         loss, self.last_nll = Fn.cross_entropy(logits_bvt, target, self.ignore_index, self.label_smoothing, return_nll=True)
+        return loss
+
+
+class DistillationLoss(nn.Module):
+    """Hard-label cross-entropy plus the KL divergence to one or two teachers' logits, all [B, V, T], through the fused HIP kernels
+    (functional.cross_entropy_distill; an extension).  config: DistillConfig.  After a forward `last_nll` and `last_kd` hold the two parts
+    of the loss, detached device scalars (no sync)."""
+
+    def __init__(self, ignore_index: int = 0, config: Optional[DistillConfig] = None):
+        super().__init__()
+        if isinstance(config, dict):
+            config = DistillConfig.from_dict(config)
+        self.ignore_index = ignore_index
+        self.config = config if config is not None else DistillConfig()
+        self.last_nll: Optional[torch.Tensor] = None
+        self.last_kd: Optional[torch.Tensor] = None
+
+    def forward(self, logits_bvt: torch.Tensor, target: torch.Tensor, teachers_bvt) -> torch.Tensor:
+        teachers = (teachers_bvt,) if isinstance(teachers_bvt, torch.Tensor) else tuple(teachers_bvt)
+        c = self.config
+        loss, self.last_nll, self.last_kd = Fn.cross_entropy_distill(logits_bvt, target, teachers, self.ignore_index,
+                                                                     alpha=c.alpha if len(teachers) == 2 else 1.0,
+                                                                     temperature=c.temperature, weight=c.weight)
         return loss
 
 
@@ -629,7 +652,31 @@ class Transformer(_Base):
         out = out.to(y.dtype)
         return out.pin_memory() if (not y.is_cuda and torch.cuda.is_available()) else out.to(y.device)
 
+    _distillation = None      # distill.Distillation: the teachers `training_step` distils from (set_distillation); never a sub-module
+
+    def set_distillation(self, distillation) -> None:
+        """Attaches a distill.Distillation (training_step then trains towards its teachers) or, with None, detaches it.  The teachers do not
+        become sub-modules.  ValueError when a teacher's vocabulary differs or the model smooths its labels."""
+        if distillation is not None:
+            distillation.attach(self)
+        self._distillation = distillation
+
+    def _distillation_step(self, batch) -> torch.Tensor:
+        """training_step with teachers: y_in is noised once, and the student and every teacher decode from that same y_in."""
+        d = self._distillation
+        (x, xl), y_in, y_out, calls = d.split(batch)
+        y_in = self.apply_teacher_forcing(y_in)
+        teachers = d.teacher_logits(calls, y_in)          # before the student's forward: nothing of theirs runs between it and its backward
+        yhat = self.forward(x=x, xl=xl, y_in=y_in)
+        loss = d.loss(yhat, _to_dev(y_out, yhat.device), teachers)
+        self.log("train_loss", loss, prog_bar=True, logger=True, on_epoch=True)
+        self.log("train_nll", d.loss.last_nll, prog_bar=True, logger=True, on_epoch=True)
+        self.log("train_kd", d.loss.last_kd, prog_bar=True, logger=True, on_epoch=True)
+        return loss
+
     def training_step(self, batch, batch_idx) -> torch.Tensor:
+        if self._distillation is not None:
+            return self._distillation_step(batch)
         x, xl, y_in, y_out = batch
         y_in = self.apply_teacher_forcing(y_in)
         yhat = self.forward(x=x, xl=xl, y_in=y_in)
