@@ -11,8 +11,8 @@
 // Every row kernel walks the row in chunks of 8 columns per thread (thread i owns columns 8 i .. 8 i + 7, then 2048 further on), the
 // same chunks in all three tensors whatever their dtypes: one 16-byte load per chunk in bf16, two in fp32, where the tensor's pitch and
 // base allow, else 8 scalar loads -- decided per tensor.  Every sum: per thread in column order, xor butterfly over the wave,
-// ((w0 + w1) + w2) + w3 over the four waves.  No atomics: two runs give the same bits.
-#include "omr_common.h"
+// ((w0 + w1) + w2) + w3 over the four waves (loss_rows.h, which holds every step shared with loss.hip).  No atomics: two runs give the same bits.
+#include "loss_rows.h"
 #include "omr_hip.h"
 
 namespace {
@@ -69,36 +69,6 @@ __device__ __forceinline__ void store8(bf16* __restrict__ r, int v0, long ld, bo
     }
 }
 
-// One online-softmax step over a chunk: running maximum m and s = sum exp((x - m) * k), as ce_fwd_kernel keeps them (k = 1 there).
-__device__ __forceinline__ float chunk_max(const float (&x)[8]) {
-    float cm = x[0];
-#pragma unroll
-    for (int e = 1; e < 8; ++e) cm = fmaxf(cm, x[e]);
-    return cm;
-}
-__device__ __forceinline__ void online_add(const float (&x)[8], float m, float nm, float k, float& s) {
-    const float sub = nm == -INFINITY ? 0.f : nm;      // only -inf so far: exp(-inf - -inf) is NaN, exp(-inf - 0) = 0 keeps s
-    float add = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) add += __expf((x[e] - sub) * k);
-    s = s * __expf((m - sub) * k) + add;
-}
-
-// log sum_v exp(k x_v) of the row from the 256 threads' (m, s): every thread gets the value.  red_m / red_s: 4 floats of LDS each, free on return.
-__device__ __forceinline__ float block_lse(float m, float s, float k, float* red_m, float* red_s) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const float wm = wave_max(m);
-    s = wave_sum(m == -INFINITY ? 0.f : s * __expf((m - wm) * k));
-    if (lane == 0) { red_m[wv] = wm; red_s[wv] = s; }
-    __syncthreads();
-    const float mm = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) t += red_m[i] == -INFINITY ? 0.f : red_s[i] * __expf((red_m[i] - mm) * k);
-    __syncthreads();
-    return mm * k + logf(t);
-}
-
 // One workgroup per row.  Sweep 1 keeps, per thread and online, the student's maximum with its two sums of exponentials (at 1 and at
 // 1 / tau: they share the maximum) and each teacher's maximum and sum at 1 / tau; the four row constants follow.  Sweep 2 re-reads the
 // three rows (from cache: they were just read) and sums q_v (log q_v - log pt_v).  One teacher: log q_v = a_v / tau - lse_a exactly, no
@@ -111,7 +81,7 @@ __global__ __launch_bounds__(256) void distill_fwd_kernel(const TS* __restrict__
     __shared__ float red_m[4], red_s[4];
     const long row = blockIdx.x;
     const long t = target[row];
-    if (!(t != pad_idx && t >= 0 && t < V)) {                     // the same for the whole workgroup
+    if (!row_live(t, pad_idx, V)) {                               // the same for the whole workgroup
         if (threadIdx.x < 4) lse4[threadIdx.x * M + row] = 0.f;
         if (threadIdx.x == 4) rowkd[row] = 0.f;
         return;
@@ -164,43 +134,10 @@ __global__ __launch_bounds__(256) void distill_fwd_kernel(const TS* __restrict__
             kd += term;
         }
     }
-    kd = wave_sum(kd);
-    if ((threadIdx.x & 63) == 0) red_s[threadIdx.x >> 6] = kd;
-    __syncthreads();
+    kd = block_sum(kd, red_s);
     if (threadIdx.x == 0) {
         lse4[row] = lse_x; lse4[M + row] = lse_xt; lse4[2 * M + row] = lse_a; lse4[3 * M + row] = lse_b;
-        rowkd[row] = tau * tau * (((red_s[0] + red_s[1]) + red_s[2]) + red_s[3]);
-    }
-}
-
-// acc4 = {sum of the objective, live rows, sum of nll, sum of kd} over the live rows in fp64, in the order of ce_finalize_kernel;
-// means3 = {loss, nll, kd}.  The objective is formed in fp64 per row.  lam == 1 never multiplies nll (0 * inf on a row whose target logit is -inf).
-template <typename TS>
-__global__ __launch_bounds__(1024) void distill_finalize_kernel(const TS* __restrict__ logits, const long* __restrict__ target, const float* __restrict__ lse4,
-                                                                const float* __restrict__ rowkd, double* __restrict__ acc4, float* __restrict__ means3,
-                                                                long M, int V, long ldv, int pad_idx, float lam) {
-    __shared__ double rs[16], rc[16], rn[16], rk[16];
-    double s = 0.0, c = 0.0, n = 0.0, kk = 0.0;
-    const double keep = 1.0 - (double)lam;
-    for (long row = threadIdx.x; row < M; row += 1024) {
-        const long t = target[row];
-        if (t != pad_idx && t >= 0 && t < V) {
-            const double plain = (double)(lse4[row] - to_f32(logits[row * ldv + t])), kd = (double)rowkd[row];
-            s += lam < 1.f ? keep * plain + (double)lam * kd : kd;
-            n += plain;
-            kk += kd;
-            c += 1.0;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); c += __shfl_xor(c, o, 64); n += __shfl_xor(n, o, 64); kk += __shfl_xor(kk, o, 64); }
-    if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = s; rc[threadIdx.x >> 6] = c; rn[threadIdx.x >> 6] = n; rk[threadIdx.x >> 6] = kk; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double ts = 0.0, tc = 0.0, tn = 0.0, tk = 0.0;
-        for (int i = 0; i < 16; ++i) { ts += rs[i]; tc += rc[i]; tn += rn[i]; tk += rk[i]; }
-        acc4[0] = ts; acc4[1] = tc; acc4[2] = tn; acc4[3] = tk;
-        means3[0] = (float)(ts / tc); means3[1] = (float)(tn / tc); means3[2] = (float)(tk / tc);
+        rowkd[row] = tau * tau * kd;
     }
 }
 
@@ -219,7 +156,7 @@ __global__ __launch_bounds__(256) void distill_bwd_kernel(const TS* __restrict__
                                                           float alpha, float tau, float lam, float gscale, const float* __restrict__ grad_out) {
     const long row = blockIdx.x;
     const long t = target[row];
-    const bool live = (t != pad_idx && t >= 0 && t < V);      // the same for the whole workgroup
+    const bool live = row_live(t, pad_idx, V);                // the same for the whole workgroup
     TS* dr = dlogits + row * ldv;
     const bool vd = row_vec_ok(dlogits, ldv);
     if (!live) {
@@ -259,7 +196,7 @@ __global__ __launch_bounds__(256) void distill_bwd_kernel(const TS* __restrict__
 
 bool distill_args_ok(const void* logits, const void* ta, const void* tb, const long* target, long M, int V, long ldv, long ldt, float alpha, float tau,
                      float lam) {
-    if (M <= 0 || V <= 0 || ldv < V || ldt < V || logits == nullptr || target == nullptr) return false;
+    if (!loss_rows_ok(M, V, ldv) || ldt < V || logits == nullptr || target == nullptr) return false;
     if (!(tau > 0.f) || !(tau < INFINITY)) return false;                  // NaN fails both comparisons
     if (!(lam >= 0.f && lam <= 1.f) || !(alpha >= 0.f && alpha <= 1.f)) return false;
     if (tb == nullptr && alpha != 1.f) return false;
@@ -274,8 +211,8 @@ void launch_distill_fwd(const void* logits, long ldv, const void* ta, const void
                                rowkd, M, V, pad_idx, alpha, tau);
     else hipLaunchKernelGGL((distill_fwd_kernel<TS, TT, false>), (int)M, 256, 0, s, (const TS*)logits, ldv, (const TT*)ta, (const TT*)nullptr, ldt, target,
                             lse4, rowkd, M, V, pad_idx, alpha, tau);
-    hipLaunchKernelGGL((distill_finalize_kernel<TS>), 1, 1024, 0, s, (const TS*)logits, target, (const float*)lse4, (const float*)rowkd, acc4, means3, M, V,
-                       ldv, pad_idx, lam);
+    hipLaunchKernelGGL((ce_finalize_kernel<TS, CE_DISTILL>), 1, 1024, 0, s, (const TS*)logits, target, (const float*)lse4, (const float*)rowkd, acc4, means3,
+                       means3 + 1, means3 + 2, M, V, ldv, pad_idx, lam);
 }
 
 template <typename TS, typename TT>
@@ -287,21 +224,15 @@ void launch_distill_bwd(const void* logits, long ldv, const void* ta, const void
                             lse4, acc4, (TS*)dlogits, M, V, pad_idx, alpha, tau, lam, gscale, grad_out);
 }
 
-bool dtype_ok(int d) { return d == OMR_F32 || d == OMR_BF16; }
-
 }  // namespace
 
-#define DISTILL_DISPATCH(FN, ...)                                                         \
-    if (dtype == OMR_F32 && tdtype == OMR_F32) FN<float, float>(__VA_ARGS__);             \
-    else if (dtype == OMR_F32) FN<float, bf16>(__VA_ARGS__);                              \
-    else if (tdtype == OMR_F32) FN<bf16, float>(__VA_ARGS__);                             \
-    else FN<bf16, bf16>(__VA_ARGS__);
+// Run CALL with TS, TT = the element types of the student's and the teachers' dtype codes.
+#define DISPATCH_TS_TT(CALL) DISPATCH_T(dtype, { typedef T TS; DISPATCH_T(tdtype, { typedef T TT; CALL; }) })
 
 extern "C" int omr_ce_distill_fwd(int dtype, const void* logits, long ldv, int tdtype, const void* teacher_a, const void* teacher_b, long ldt,
                                   const long* target, float* lse4, float* rowkd, double* acc4, float* means3, long M, int V, int pad_idx, float alpha,
                                   float tau, float lam, void* stream) {
     if (!distill_args_ok(logits, teacher_a, teacher_b, target, M, V, ldv, ldt, alpha, tau, lam)) return OMR_ERR_ARG;
-    if (!dtype_ok(dtype) || (lam > 0.f && !dtype_ok(tdtype))) return OMR_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     if (lam == 0.f) {                                              // the plain loss: its own kernels, its bits; the teachers are never read
         const int rc = omr_ce_fwd(dtype, logits, target, lse4, acc4, means3, M, V, ldv, pad_idx, stream);
@@ -310,7 +241,7 @@ extern "C" int omr_ce_distill_fwd(int dtype, const void* logits, long ldv, int t
         OMR_CHECK_LAUNCH();
         return OMR_OK;
     }
-    DISTILL_DISPATCH(launch_distill_fwd, logits, ldv, teacher_a, teacher_b, ldt, target, lse4, rowkd, acc4, means3, M, V, pad_idx, alpha, tau, lam, s)
+    DISPATCH_TS_TT((launch_distill_fwd<TS, TT>(logits, ldv, teacher_a, teacher_b, ldt, target, lse4, rowkd, acc4, means3, M, V, pad_idx, alpha, tau, lam, s)))
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }
@@ -319,11 +250,10 @@ extern "C" int omr_ce_distill_bwd(int dtype, const void* logits, long ldv, int t
                                   const long* target, const float* lse4, const double* acc4, void* dlogits, long M, int V, int pad_idx, float alpha,
                                   float tau, float lam, float grad_scale, const float* grad_out, void* stream) {
     if (!distill_args_ok(logits, teacher_a, teacher_b, target, M, V, ldv, ldt, alpha, tau, lam)) return OMR_ERR_ARG;
-    if (!dtype_ok(dtype) || (lam > 0.f && !dtype_ok(tdtype))) return OMR_ERR_UNSUPPORTED;
     if (lam == 0.f) return omr_ce_bwd(dtype, logits, target, lse4, acc4, dlogits, M, V, ldv, pad_idx, grad_scale, grad_out, stream);
     hipStream_t s = (hipStream_t)stream;
-    DISTILL_DISPATCH(launch_distill_bwd, logits, ldv, teacher_a, teacher_b, ldt, target, lse4, acc4, dlogits, M, V, pad_idx, alpha, tau, lam, grad_scale,
-                     grad_out, s)
+    DISPATCH_TS_TT((launch_distill_bwd<TS, TT>(logits, ldv, teacher_a, teacher_b, ldt, target, lse4, acc4, dlogits, M, V, pad_idx, alpha, tau, lam, grad_scale,
+                                               grad_out, s)))
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }

@@ -620,66 +620,36 @@ class FusedCrossKVFn(Function):
 
 
 class CrossEntropyFn(Function):
-    """CrossEntropyLoss(ignore_index) on row-major logits [M, V] (model.py:109,166)."""
+    """CrossEntropyLoss(ignore_index) on row-major logits [M, V] (model.py:109,166), optionally with torch's label_smoothing = eps, or
+    with the KL divergence to one or two teachers (kernels.ce_distill_fwd): teachers = (a, b or None), which get no gradient, and
+    distill = (alpha, temperature, weight) -> (loss, nll, kd): the mean objective, and the mean un-smoothed lse - logit[target] and the
+    mean KL term of the same rows as outputs that carry no gradient; None where the objective has no such part of its own (the plain
+    loss is its nll, and without teachers there is no kd).  forward picks the kernel pair from (eps, weight), here and nowhere else:
+    eps == 0 and weight == 0 run exactly ce_fwd / ce_bwd."""
 
     @staticmethod
-    def forward(ctx, logits2d, target, V, pad_idx):
-        loss, lse, acc2 = K.ce_fwd(logits2d, target, V, pad_idx)
-        ctx.cfg = (V, pad_idx)
-        ctx.save_for_backward(logits2d, target, lse, acc2)
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, g):
-        V, pad_idx = ctx.cfg
-        logits2d, target, lse, acc2 = ctx.saved_tensors
-        dl = K.ce_bwd(logits2d, target, lse, acc2, V, pad_idx, grad_out=g)
-        return dl, None, None, None
-
-
-class SmoothCrossEntropyFn(Function):
-    """CrossEntropyFn with torch's label_smoothing = eps > 0 -> (loss, nll): the mean smoothed objective, and the mean un-smoothed
-    lse - logit[target] of the same rows as a second output that carries no gradient."""
-
-    @staticmethod
-    def forward(ctx, logits2d, target, V, pad_idx, eps):
-        loss, nll, lse, _rowsum, acc3 = K.ce_smooth_fwd(logits2d, target, V, pad_idx, eps)
-        ctx.cfg = (V, pad_idx, eps)
-        ctx.save_for_backward(logits2d, target, lse, acc3)   # the row sums only feed the forward's objective: backward needs eps alone
-        nll = nll.view(())
-        ctx.mark_non_differentiable(nll)
-        return loss.view(()), nll
-
-    @staticmethod
-    def backward(ctx, g, _g_nll):
-        V, pad_idx, eps = ctx.cfg
-        logits2d, target, lse, acc3 = ctx.saved_tensors
-        dl = K.ce_smooth_bwd(logits2d, target, lse, acc3, V, pad_idx, eps, grad_out=g)
-        return dl, None, None, None, None
-
-
-class DistillCrossEntropyFn(Function):
-    """Hard-label cross-entropy plus the KL divergence to one or two teachers on row-major logits [M, V] (kernels.ce_distill_fwd) ->
-    (loss, nll, kd): the mean objective (1 - weight) nll + weight kd, and its two parts as outputs that carry no gradient.  The teachers
-    get no gradient."""
-
-    @staticmethod
-    def forward(ctx, logits2d, target, teacher_a, teacher_b, V, pad_idx, alpha, temperature, weight):
-        means, lse4, _rowkd, acc4 = K.ce_distill_fwd(logits2d, target, teacher_a, teacher_b, V, pad_idx, alpha, temperature, weight)
-        ctx.cfg = (V, pad_idx, alpha, temperature, weight)
-        ctx.teachers = (teacher_a, teacher_b)              # no graph behind them: plain references, as the backward re-reads them
-        ctx.save_for_backward(logits2d, target, lse4, acc4)
-        nll, kd = means[1].view(()), means[2].view(())
-        ctx.mark_non_differentiable(nll, kd)
-        return means[0].view(()), nll, kd
+    def forward(ctx, logits2d, target, V, pad_idx, eps, teachers, distill):
+        lam = distill[2] if distill is not None else 0.0
+        assert not (eps > 0 and lam > 0), "label smoothing and distillation do not combine"
+        nll = kd = None
+        if lam > 0:
+            means, lse, _rowkd, acc = K.ce_distill_fwd(logits2d, target, *teachers, V, pad_idx, *distill)
+            loss, nll, kd = means[0], means[1].view(()), means[2].view(())
+            ctx.bwd = lambda x, t, lse4, acc4, g: K.ce_distill_bwd(x, t, *teachers, lse4, acc4, V, pad_idx, *distill, grad_out=g)
+        elif eps > 0:
+            loss, nll, lse, _rowsum, acc = K.ce_smooth_fwd(logits2d, target, V, pad_idx, eps)   # the row sums only feed the forward's objective
+            nll = nll.view(())
+            ctx.bwd = lambda x, t, lse, acc3, g: K.ce_smooth_bwd(x, t, lse, acc3, V, pad_idx, eps, grad_out=g)
+        else:
+            loss, lse, acc = K.ce_fwd(logits2d, target, V, pad_idx)
+            ctx.bwd = lambda x, t, lse, acc2, g: K.ce_bwd(x, t, lse, acc2, V, pad_idx, grad_out=g)
+        ctx.save_for_backward(logits2d, target, lse, acc)
+        ctx.mark_non_differentiable(*(t for t in (nll, kd) if t is not None))
+        return loss.view(()), nll, kd
 
     @staticmethod
     def backward(ctx, g, _g_nll, _g_kd):
-        V, pad_idx, alpha, temperature, weight = ctx.cfg
-        logits2d, target, lse4, acc4 = ctx.saved_tensors
-        teacher_a, teacher_b = ctx.teachers
-        dl = K.ce_distill_bwd(logits2d, target, teacher_a, teacher_b, lse4, acc4, V, pad_idx, alpha, temperature, weight, grad_out=g)
-        return dl, None, None, None, None, None, None, None, None
+        return ctx.bwd(*ctx.saved_tensors, g), None, None, None, None, None, None
 
 
 def _rows_of_bvt(logits_bvt: Tensor) -> Tensor:
@@ -710,8 +680,11 @@ def cross_entropy_distill(logits_bvt: Tensor, target_bt: Tensor, teachers_bvt, p
     rows = [_rows_of_bvt(t.detach()) for t in teachers]
     if len(rows) == 2 and rows[0].stride(0) != rows[1].stride(0):
         rows = [r.contiguous() for r in rows]
-    return DistillCrossEntropyFn.apply(_rows_of_bvt(logits_bvt), target_bt.reshape(-1).contiguous(), rows[0], rows[1] if len(rows) == 2 else None,
-                                       V, pad_idx, float(alpha), float(temperature), float(weight))
+    loss, nll, kd = CrossEntropyFn.apply(_rows_of_bvt(logits_bvt), target_bt.reshape(-1).contiguous(), V, pad_idx, 0.0,
+                                         (rows[0], rows[1] if len(rows) == 2 else None), (float(alpha), float(temperature), float(weight)))
+    if nll is None:                                                  # weight == 0: the plain loss, whose nll is itself
+        nll, kd = loss.detach(), torch.zeros_like(loss)
+    return loss, nll, kd
 
 
 def cross_entropy(logits_bvt: Tensor, target_bt: Tensor, pad_idx: int, label_smoothing: float = 0.0, return_nll: bool = False):
@@ -720,14 +693,7 @@ def cross_entropy(logits_bvt: Tensor, target_bt: Tensor, pad_idx: int, label_smo
     label_smoothing: torch's argument of that name, in [0, 1]; 0 (the reference) runs exactly the unsmoothed kernels.
     return_nll: also return the un-smoothed mean of the same rows (no gradient; with label_smoothing = 0 it is the loss, detached)."""
     eps = K.check_label_smoothing(label_smoothing)
-    B, V, T = logits_bvt.shape
-    rows = logits_bvt.permute(0, 2, 1)
-    if rows.stride(2) != 1 or rows.stride(1) % 8 or rows.stride(0) != T * rows.stride(1):
-        rows = rows.contiguous()
-    l2 = rows.reshape(B * T, V)   # a view: rows of one batch follow each other at the same pitch
-    if eps > 0:
-        loss, nll = SmoothCrossEntropyFn.apply(l2, target_bt.reshape(-1).contiguous(), V, pad_idx, eps)
-    else:
-        loss = CrossEntropyFn.apply(l2, target_bt.reshape(-1).contiguous(), V, pad_idx)
+    loss, nll, _kd = CrossEntropyFn.apply(_rows_of_bvt(logits_bvt), target_bt.reshape(-1).contiguous(), logits_bvt.shape[1], pad_idx, eps, None, None)
+    if nll is None:
         nll = loss.detach()
     return (loss, nll) if return_nll else loss

@@ -1026,28 +1026,39 @@ def attn_dropout_mask(B: int, H: int, T: int, S: int, p: float, seed: int, devic
 
 # ------------------------------------------------------------------------------------------------ loss
 
-def ce_fwd(logits2d: Tensor, target: Tensor, V: int, pad_idx: int):
-    """logits2d [M, ldv>=V]; target int64 [M] -> (loss fp32 [1], lse [M], acc2 fp64 [2])."""
+def _loss_fwd(logits2d: Tensor, target: Tensor, V: int, n: int, lse_shape: Tuple[int, ...] = ()):
+    """The checks every loss forward makes of its rows logits2d [M, ldv >= V] and targets int64 [M], and the buffers every one writes
+    -> (M, ldv, lse fp32 [*lse_shape, M], acc fp64 [n], means fp32 [n - 1])."""
     require_cuda(logits2d, target)
     M, cols, ldv = _rows2d(logits2d)
     assert cols >= V and target.numel() == M and target.dtype == torch.int64 and target.is_contiguous()
-    lse = torch.empty(M, dtype=torch.float32, device=logits2d.device)
-    acc2 = torch.empty(2, dtype=torch.float64, device=logits2d.device)
-    loss = torch.empty(1, dtype=torch.float32, device=logits2d.device)
+    new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=logits2d.device)  # noqa: E731
+    return M, ldv, new(lse_shape + (M,)), new(n, torch.float64), new(n - 1)
+
+
+def _loss_grad(logits2d: Tensor, target: Tensor, grad_out: Optional[Tensor]) -> Tuple[int, int, Tensor, Tensor]:
+    """The checks every loss backward makes, and its gradient -> (M, ldv, the [M, ldv] buffer the kernel writes, its view to return)."""
+    require_cuda(logits2d, target, grad_out)
+    if grad_out is not None:
+        assert grad_out.dtype == torch.float32 and grad_out.numel() == 1
+    M, cols, ldv = _rows2d(logits2d)
+    dl = torch.empty((M, ldv), dtype=logits2d.dtype, device=logits2d.device)
+    return M, ldv, dl, dl[:, :cols]
+
+
+def ce_fwd(logits2d: Tensor, target: Tensor, V: int, pad_idx: int):
+    """logits2d [M, ldv>=V]; target int64 [M] -> (loss fp32 [1], lse [M], acc2 fp64 [2])."""
+    M, ldv, lse, acc2, loss = _loss_fwd(logits2d, target, V, 2)
     lib().call("omr_ce_fwd", dtype_code(logits2d.dtype), ptr(logits2d), ptr(target), ptr(lse), ptr(acc2), ptr(loss), M, V, ldv, pad_idx, cur_stream())
     return loss, lse, acc2
 
 
 def ce_bwd(logits2d: Tensor, target: Tensor, lse: Tensor, acc2: Tensor, V: int, pad_idx: int, grad_scale: float = 1.0,
            grad_out: Optional[Tensor] = None) -> Tensor:
-    require_cuda(logits2d, target, grad_out)
-    if grad_out is not None:
-        assert grad_out.dtype == torch.float32 and grad_out.numel() == 1
-    M, cols, ldv = _rows2d(logits2d)
-    dl = torch.empty((M, ldv), dtype=logits2d.dtype, device=logits2d.device)
+    M, ldv, dl, out = _loss_grad(logits2d, target, grad_out)
     lib().call("omr_ce_bwd", dtype_code(logits2d.dtype), ptr(logits2d), ptr(target), ptr(lse), ptr(acc2), ptr(dl), M, V, ldv, pad_idx, float(grad_scale),
                ptr(grad_out), cur_stream())
-    return dl[:, :cols]
+    return out
 
 
 def check_label_smoothing(eps) -> float:
@@ -1063,14 +1074,8 @@ def ce_smooth_fwd(logits2d: Tensor, target: Tensor, V: int, pad_idx: int, eps: f
     loss is the mean smoothed objective, nll the mean un-smoothed lse - logit[target], rowsum the per-row sum of the logits over the
     columns < V, acc3 = {objective sum, live rows, nll sum}.  eps == 0 runs ce_fwd's kernels (same bits) and has no rowsum."""
     eps = check_label_smoothing(eps)
-    require_cuda(logits2d, target)
-    M, cols, ldv = _rows2d(logits2d)
-    assert cols >= V and target.numel() == M and target.dtype == torch.int64 and target.is_contiguous()
-    dev = logits2d.device
-    lse = torch.empty(M, dtype=torch.float32, device=dev)
-    rowsum = torch.empty(M, dtype=torch.float32, device=dev) if eps > 0 else None
-    acc3 = torch.empty(3, dtype=torch.float64, device=dev)
-    means = torch.empty(2, dtype=torch.float32, device=dev)
+    M, ldv, lse, acc3, means = _loss_fwd(logits2d, target, V, 3)
+    rowsum = torch.empty_like(lse) if eps > 0 else None
     lib().call("omr_ce_smooth_fwd", dtype_code(logits2d.dtype), ptr(logits2d), ptr(target), ptr(lse), ptr(rowsum), ptr(acc3), ptr(means),
                means.data_ptr() + 4, M, V, ldv, pad_idx, eps, cur_stream())
     return means[:1], means[1:], lse, rowsum, acc3
@@ -1080,14 +1085,10 @@ def ce_smooth_bwd(logits2d: Tensor, target: Tensor, lse: Tensor, acc3: Tensor, V
                   grad_out: Optional[Tensor] = None) -> Tensor:
     """ce_bwd with label smoothing eps: (softmax - (1 - eps) onehot - eps / V) * grad_scale * grad_out / count.  eps == 0 runs ce_bwd's kernel."""
     eps = check_label_smoothing(eps)
-    require_cuda(logits2d, target, grad_out)
-    if grad_out is not None:
-        assert grad_out.dtype == torch.float32 and grad_out.numel() == 1
-    M, cols, ldv = _rows2d(logits2d)
-    dl = torch.empty((M, ldv), dtype=logits2d.dtype, device=logits2d.device)
+    M, ldv, dl, out = _loss_grad(logits2d, target, grad_out)
     lib().call("omr_ce_smooth_bwd", dtype_code(logits2d.dtype), ptr(logits2d), ptr(target), ptr(lse), ptr(acc3), ptr(dl), M, V, ldv, pad_idx, eps,
                float(grad_scale), ptr(grad_out), cur_stream())
-    return dl[:, :cols]
+    return out
 
 
 def check_distill(alpha, temperature, weight, two_teachers: bool) -> Tuple[float, float, float]:
@@ -1123,15 +1124,9 @@ def ce_distill_fwd(logits2d: Tensor, target: Tensor, teacher_a: Optional[Tensor]
     teacher logits [M, ldt >= V] (teacher_b may be None, then alpha = 1) -> (means fp32 [3] = {loss, nll, kd}, lse4 fp32 [4, M],
     rowkd fp32 [M] or None, acc4 fp64 [4]).  weight == 0 runs ce_fwd's kernels (same bits), reads no teacher and has no rowkd."""
     alpha, tau, lam = check_distill(alpha, temperature, weight, teacher_b is not None)
-    require_cuda(logits2d, target)
-    M, cols, ldv = _rows2d(logits2d)
-    assert cols >= V and target.numel() == M and target.dtype == torch.int64 and target.is_contiguous()
+    M, ldv, lse4, acc4, means = _loss_fwd(logits2d, target, V, 4, lse_shape=(4,))
     tdtype, ldt = _distill_teachers(logits2d, teacher_a, teacher_b, V, lam)
-    dev = logits2d.device
-    lse4 = torch.empty((4, M), dtype=torch.float32, device=dev)
-    rowkd = torch.empty(M, dtype=torch.float32, device=dev) if lam > 0 else None
-    acc4 = torch.empty(4, dtype=torch.float64, device=dev)
-    means = torch.empty(3, dtype=torch.float32, device=dev)
+    rowkd = torch.empty_like(lse4[0]) if lam > 0 else None
     lib().call("omr_ce_distill_fwd", dtype_code(logits2d.dtype), ptr(logits2d), ldv, tdtype, ptr(teacher_a), ptr(teacher_b), ldt, ptr(target),
                ptr(lse4), ptr(rowkd), ptr(acc4), ptr(means), M, V, pad_idx, alpha, tau, lam, cur_stream())
     return means, lse4, rowkd, acc4
@@ -1142,16 +1137,12 @@ def ce_distill_bwd(logits2d: Tensor, target: Tensor, teacher_a: Optional[Tensor]
                    grad_out: Optional[Tensor] = None) -> Tensor:
     """((1 - weight)(softmax - onehot) + weight tau (softmax(x / tau) - q)) * grad_scale * grad_out / count.  weight == 0 runs ce_bwd's kernel."""
     alpha, tau, lam = check_distill(alpha, temperature, weight, teacher_b is not None)
-    require_cuda(logits2d, target, grad_out)
-    if grad_out is not None:
-        assert grad_out.dtype == torch.float32 and grad_out.numel() == 1
-    M, cols, ldv = _rows2d(logits2d)
+    M, ldv, dl, out = _loss_grad(logits2d, target, grad_out)
     tdtype, ldt = _distill_teachers(logits2d, teacher_a, teacher_b, V, lam)
     assert lse4.dtype == torch.float32 and tuple(lse4.shape) == (4, M) and lse4.is_contiguous()
-    dl = torch.empty((M, ldv), dtype=logits2d.dtype, device=logits2d.device)
     lib().call("omr_ce_distill_bwd", dtype_code(logits2d.dtype), ptr(logits2d), ldv, tdtype, ptr(teacher_a), ptr(teacher_b), ldt, ptr(target),
                ptr(lse4), ptr(acc4), ptr(dl), M, V, pad_idx, alpha, tau, lam, float(grad_scale), ptr(grad_out), cur_stream())
-    return dl[:, :cols]
+    return out
 
 
 def round_up(n: int, m: int) -> int:

@@ -81,10 +81,8 @@ class CrossEntropyLoss(nn.Module):
 
     def __init__(self, ignore_index: int = 0, label_smoothing: float = 0.0):
         super().__init__()
-        if not 0.0 <= float(label_smoothing) <= 1.0:
-            raise ValueError(f"label_smoothing must be between 0.0 and 1.0, got {label_smoothing}")
         self.ignore_index = ignore_index
-        self.label_smoothing = float(label_smoothing)
+        self.label_smoothing = K.check_label_smoothing(label_smoothing)
         self.last_nll: Optional[torch.Tensor] = None
 
     def forward(self, logits_bvt: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
