@@ -44,7 +44,9 @@ int omr_add_pe2d(int dtype, const void* x, const float* pe_hwc, void* out, int B
 /* bias gradients: db[n] += sum_m dy[m][n] */
 int omr_colsum(int dtype, const void* dy, float* db, long M, int N, long ld, void* stream);
 /* torch.optim.Adam step over one flat fp32 buffer (model.py:134-139; torch optim/adam.py:347); step is 1-based.
- * p_bf16 (nullable) receives the bf16 compute copy of the updated parameters in the same pass. */
+ * p_bf16 (nullable) receives the bf16 compute copy of the updated parameters in the same pass.
+ * omr_adamw_ema (below) with weight_decay = 0 and ema = decay_blocks = ctl = NULL, and its contract: any n >= 1, but p, g, m, v
+ * non-NULL and, like p_bf16, 16-byte aligned; anything else, or step < 1, is refused with OMR_ERR_ARG before any launch. */
 int omr_adam(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2, float eps,
              float grad_scale, void* stream);
 /* greedy token pick: argmax(dim=-1) / topk(1) of the last-step logits (model.py:187,253), one row per decoded sample
@@ -739,8 +741,10 @@ int omr_grad_norm(const float* g, long n, const long* range_begin, const long* r
                   float max_norm, void* ws, omr_step_ctl* ctl, void* stream);
 /* omr_adam behind the record (torch optim/adam.py:347 after clip_grad_norm_; GradScaler's skip): when ctl->apply == 0 the
  * launch writes NOTHING (p, m, v, p_bf16 keep their bits); otherwise g_i = (g[i] * grad_scale) * ctl->clip goes through the very
- * update omr_adam applies (one device function), so with clip == 1.0f the results are omr_adam's bit for bit.  ctl is read on
- * the device, in stream order behind omr_grad_norm. */
+ * update omr_adam applies (one kernel), so with clip == 1.0f the results are omr_adam's bit for bit.  ctl is read on
+ * the device, in stream order behind omr_grad_norm.  omr_adamw_ema (below) with weight_decay = 0, ema = decay_blocks = NULL and
+ * this ctl, and its contract: p, g, m, v non-NULL and, like p_bf16, 16-byte aligned, ctl 8-byte aligned; anything else, step < 1
+ * or a NULL ctl is refused with OMR_ERR_ARG before any launch. */
 int omr_adam_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2,
                      float eps, float grad_scale, const omr_step_ctl* ctl, void* stream);
 
@@ -753,17 +757,18 @@ int omr_adam_guarded(float* p, const float* g, float* m, float* v, void* p_bf16,
  *   p'    = p[i] * f                              f = (float)(1.0 - (double)lr * (double)weight_decay), formed on the host; ONLY
  *                                                 where weight_decay != 0 and the element's block decays -- elsewhere p' = p[i]
  *                                                 and no multiply touches it
- *   m, v, denom, p_new = fma(-lr/bc1, m / denom, p')   exactly omr_adam's four roundings (csrc/adam_update.h)
+ *   m, v, denom, p_new = fma(-lr/bc1, m / denom, p')   omr_adam's four roundings (adam_update in csrc/optim.hip)
  *   ema_new = fma(d, ema[i], omd * p_new)         only when ema != NULL; d = ema_decay, omd = (float)(1.0 - (double)ema_decay).
  *                                                 d = 0 leaves p_new's bits in ema, d = 1 leaves ema's bits (signed zeros aside)
  *   p_bf16[i] = (bf16)p_new                       only when p_bf16 != NULL
- * decay_blocks (nullable: every element decays): one byte per 64 elements, byte k for elements [64 k, 64 k + 64) counted from
- * p; non-zero = decays; ceil(n / 64) bytes are read.  With ctl != NULL and ctl->apply == 0 the launch writes NOTHING: p, m, v,
- * p_bf16 and ema keep their bits.  With weight_decay == 0, ema == NULL the results are omr_adam's (ctl == NULL) or
- * omr_adam_guarded's bit for bit.  16-byte loads and stores with a scalar tail: any n >= 1, but p, g, m, v, p_bf16 and ema
+ * decay_blocks (nullable: every element decays): one byte per OMR_ADAM_DECAY_BLOCK = 64 elements, byte k for elements
+ * [64 k, 64 k + 64) counted from p; non-zero = decays; ceil(n / 64) bytes are read.  With ctl != NULL and ctl->apply == 0 the launch writes NOTHING: p, m, v,
+ * p_bf16 and ema keep their bits.  With weight_decay == 0, ema == NULL this IS omr_adam (ctl == NULL) or
+ * omr_adam_guarded: the three entries share one kernel.  16-byte loads and stores with a scalar tail: any n >= 1, but p, g, m, v, p_bf16 and ema
  * must be 16-byte aligned (ctl: 8); anything else, step < 1 or an ema_decay outside [0, 1] is refused with OMR_ERR_ARG.
  * Error against exact arithmetic on the same inputs, u = 2^-24: omr_adam's bound plus one rounding of p for the decay;
  * |ema_new - exact| <= 2 u max(|ema|, |p_new|) per step on top of what p_new carries. */
+#define OMR_ADAM_DECAY_BLOCK 64
 int omr_adamw_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, const unsigned char* decay_blocks, long n,
                   int step, float lr, float b1, float b2, float eps, float weight_decay, float ema_decay, float grad_scale,
                   const omr_step_ctl* ctl, void* stream);

@@ -1,7 +1,6 @@
 // HBM-bound elementwise / gather / reduction kernels (gfx950): 16-byte vector access per lane,
 // grid-stride loops capped at 2048 blocks (256 CUs x 8).
 #include "omr_common.h"
-#include "adam_update.h"
 #include "omr_hip.h"
 
 namespace {
@@ -156,14 +155,6 @@ template <typename T> __global__ __launch_bounds__(256) void colsum_kernel(const
     red[ph][cl] = s;
     __syncthreads();
     if (ph == 0 && col < N) atomicAdd(&db[col], red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl]);
-}
-
-// ---------------------------------------------------------------- fused Adam over one flat buffer
-// The per-element math is adam_update (adam_update.h), shared with the guarded step of optim.hip.
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            bf16* __restrict__ p_lp, long n, float lr_over_bc1, float b1, float b2, float eps, float inv_sqrt_bc2, float gscale) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        adam_update(p, m, v, p_lp, i, g[i] * gscale, lr_over_bc1, b1, b2, eps, inv_sqrt_bc2);
 }
 
 // ---------------------------------------------------------------- argmax over fp32 rows (greedy decode, model.py:187)
@@ -388,17 +379,6 @@ extern "C" int omr_colsum(int dtype, const void* dy, float* db, long M, int N, l
     int rpb = 128;
     dim3 grid(cdiv(N, 64), cdiv(M, rpb));
     DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_kernel<T>), grid, 256, 0, (hipStream_t)stream, (const T*)dy, db, M, N, ld, rpb));
-    OMR_CHECK_LAUNCH();
-    return OMR_OK;
-}
-
-extern "C" int omr_adam(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2,
-                        float eps, float grad_scale, void* stream) {
-    if (n <= 0) return OMR_OK;
-    if (step < 1) return OMR_ERR_ARG;
-    double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    hipLaunchKernelGGL(adam_kernel, ew_grid(n), EW_BLOCK, 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, (float)(lr / bc1), b1, b2, eps,
-                       (float)(1.0 / sqrt(bc2)), grad_scale);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }

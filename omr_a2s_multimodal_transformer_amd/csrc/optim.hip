@@ -1,6 +1,7 @@
-// Guarded optimizer step (gfx950): global gradient norm, clip factor and the apply / skip decision on the device, and the Adam
-// launch that obeys them.  The host never waits for the decision: it is a record in device memory (omr_step_ctl, omr_hip.h) that
-// omr_adam_guarded reads in stream order and the host copies back one step late (params.FusedAdam).
+// The optimizer step (gfx950): global gradient norm, clip factor and the apply / skip decision on the device, and the one Adam
+// kernel -- AdamW decay, EMA and the guard's record all optional -- behind omr_adam, omr_adam_guarded and omr_adamw_ema.  The host
+// never waits for the decision: it is a record in device memory (omr_step_ctl, omr_hip.h) that the step kernel reads in stream
+// order and the host copies back one step late (params.FusedAdam).
 //
 // The norm is a two-stage slot reduction like the InstanceNorm statistics (norm.hip): no atomics, a fixed order at every level, a
 // chunk size that is a compile-time constant -- the bits do not depend on the CU count or on the run.
@@ -12,7 +13,6 @@
 #include <limits.h>
 
 #include "omr_common.h"
-#include "adam_update.h"
 #include "omr_hip.h"
 
 namespace {
@@ -117,33 +117,51 @@ __global__ __launch_bounds__(GN_BLOCK) void grad_norm_finish_kernel(const GnSlot
     }
 }
 
-// omr_adam's loop behind the record.  ctl->apply / ctl->clip are uniform loads; a skipped step leaves before the first access to
-// p, m, v, p_lp.
-__global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                    bf16* __restrict__ p_lp, long n, float lr_over_bc1, float b1, float b2, float eps, float inv_sqrt_bc2,
-                                    float gscale, const omr_step_ctl* __restrict__ ctl) {
-    if (ctl->apply == 0) return;
-    const float clip = ctl->clip;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        adam_update(p, m, v, p_lp, i, (g[i] * gscale) * clip, lr_over_bc1, b1, b2, eps, inv_sqrt_bc2);
-}
-
-// ---------------------------------------------------------------- AdamW + EMA in one pass (omr_adamw_ema)
-// The optimizer recipe around adam_update's four roundings (adam_update.h: adam_update_reg, ema_update): decoupled weight decay in
-// front, the exponential moving average of the new weights behind, the guard's record obeyed as in adam_guarded_kernel.
+// ---------------------------------------------------------------- the optimizer step (omr_adam, omr_adam_guarded, omr_adamw_ema)
+// ONE kernel behind the three entries.  torch optim/adam.py:347 single-tensor math (model.py:134-139: lr 1e-4, betas (0.9,0.999),
+// eps 1e-8):
+//   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// wrapped in two more fused steps (torch optim/adamw.py single-tensor math; optim/swa_utils.py get_ema_multi_avg_fn):
+//   before:  p' = p * f, f = (float)(1 - lr wd) from the host, only where the element decays
+//   after:   ema = fma(d, ema, (1-d) p_new), d = (float)decay and omd = (float)(1 - decay) from the host.  d = 0: omd = 1,
+//            fma(0, ema, p) = p's bits (a finite ema); d = 1: omd = 0, fma(1, ema, 0 * p) = ema's bits (a finite p).
+// The gradient the update sees is gi = (g * gscale) * clip, clip = the guard's record's or 1.0f.
+//
+// The library is built with -ffp-contract=fast, under which two copies of `a * b + c` -- or one copy inlined into two places --
+// are not guaranteed to contract into the same fma chain (moving the expression into a function once did change the chain of the
+// scalar kernel omr_adam had then).  So every multiply-add is spelled out as the fma omr_adam has always executed:
+//   m = fma(b1, m, (1-b1) g)   v = fma(b2, v, ((1-b2) g) g)   denom = fma(sqrt(v), 1/sqrt(bc2), eps)   p = fma(-lr/bc1, m / denom, p)
+// No fmul -> fadd pair is left for the contraction pass: a product only ever feeds an explicit fma, so the vector body and the
+// scalar tail execute these roundings, whatever surrounds the call.
+//
 // A pure streaming kernel: 16-byte loads and stores, four elements per thread per trip (g, p, m, v [, ema] in; p, m, v [, ema]
 // and 8 bytes of bf16 out), a grid-stride loop, no LDS, no atomics; the last n % 4 elements take the same update one at a time.
-// decay_blocks: one byte per AW_BLOCK_ELEMS elements, relative to p; a thread's four elements share a byte (4 | 64).
-// A block that does not decay takes p' = p through a select -- no multiply touches it -- so its bits are omr_adam's.
+// decay_blocks: one byte per AW_BLOCK_ELEMS elements, relative to p; a thread's four elements share a byte.
+// A block that does not decay takes p' = p through a select -- no multiply touches it.
 constexpr int AW_THREADS = 256;
-constexpr int AW_MAX_GRID = 2048;                      // as omr_adam_guarded: 256 CUs x 8 workgroups
-constexpr int AW_BLOCK_SHIFT = 6;                      // 64 elements per decay byte (params.ALIGN)
+constexpr int AW_MAX_GRID = 2048;                      // 256 CUs x 8 workgroups
+constexpr int AW_BLOCK_ELEMS = OMR_ADAM_DECAY_BLOCK;   // elements per decay byte
+constexpr int AW_BLOCK_SHIFT = __builtin_ctz(AW_BLOCK_ELEMS);
+static_assert((AW_BLOCK_ELEMS & (AW_BLOCK_ELEMS - 1)) == 0 && AW_BLOCK_ELEMS % 4 == 0, "a power of two, and a 16-byte vector never straddles a block");
 
 struct AwArgs {                                        // by value in the kernel arguments
     float lr_over_bc1, b1, b2, eps, inv_sqrt_bc2, gscale;
     float decay_f;                                     // (float)(1 - lr wd)
     float ema_d, ema_omd;                              // (float)d, (float)(1 - d)
 };
+
+// The per-element sequence on registers, written once for the vector body and the scalar tail.  -> the bf16 copy of the new p.
+template <bool DECAY, bool EMA>
+__device__ __forceinline__ bf16 adam_update(float& pi, float& mi, float& vi, float& ei, float g, bool dec, float clip, const AwArgs& a) {
+    const float gi = (g * a.gscale) * clip;
+    if (DECAY) pi = dec ? pi * a.decay_f : pi;
+    mi = __builtin_fmaf(a.b1, mi, (1.f - a.b1) * gi);
+    vi = __builtin_fmaf(a.b2, vi, ((1.f - a.b2) * gi) * gi);
+    const float denom = __builtin_fmaf(sqrtf(vi), a.inv_sqrt_bc2, a.eps);
+    pi = __builtin_fmaf(-a.lr_over_bc1, mi / denom, pi);
+    if (EMA) ei = __builtin_fmaf(a.ema_d, ei, a.ema_omd * pi);
+    return (bf16)pi;
+}
 
 template <bool DECAY, bool EMA>
 __global__ __launch_bounds__(AW_THREADS) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -170,12 +188,10 @@ __global__ __launch_bounds__(AW_THREADS) void adamw_ema_kernel(float* __restrict
         bf16x4 lp4;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            float pi = p4[c], mi = m4[c], vi = v4[c];
-            if (DECAY) pi = dec ? pi * a.decay_f : pi;
-            adam_update_reg(pi, mi, vi, (g4[c] * a.gscale) * clip, a.lr_over_bc1, a.b1, a.b2, a.eps, a.inv_sqrt_bc2);
+            float pi = p4[c], mi = m4[c], vi = v4[c], ei = EMA ? e4[c] : 0.f;
+            lp4[c] = adam_update<DECAY, EMA>(pi, mi, vi, ei, g4[c], dec, clip, a);
             p4[c] = pi; m4[c] = mi; v4[c] = vi;
-            lp4[c] = (bf16)pi;
-            if (EMA) e4[c] = ema_update(e4[c], pi, a.ema_d, a.ema_omd);
+            if (EMA) e4[c] = ei;
         }
         *reinterpret_cast<f32x4*>(p + i) = p4;
         *reinterpret_cast<f32x4*>(m + i) = m4;
@@ -184,12 +200,12 @@ __global__ __launch_bounds__(AW_THREADS) void adamw_ema_kernel(float* __restrict
         if (p_lp) *reinterpret_cast<bf16x4*>(p_lp + i) = lp4;
     }
     for (long i = (nvec << 2) + gid; i < n; i += stride) {               // at most three elements, on the grid's first threads
-        float pi = p[i], mi = m[i], vi = v[i];
-        if (DECAY && (!decay_blocks || decay_blocks[i >> AW_BLOCK_SHIFT] != 0)) pi = pi * a.decay_f;
-        adam_update_reg(pi, mi, vi, (g[i] * a.gscale) * clip, a.lr_over_bc1, a.b1, a.b2, a.eps, a.inv_sqrt_bc2);
+        float pi = p[i], mi = m[i], vi = v[i], ei = EMA ? ema[i] : 0.f;
+        const bool dec = DECAY && (!decay_blocks || decay_blocks[i >> AW_BLOCK_SHIFT] != 0);
+        const bf16 lp = adam_update<DECAY, EMA>(pi, mi, vi, ei, g[i], dec, clip, a);
         p[i] = pi; m[i] = mi; v[i] = vi;
-        if (p_lp) p_lp[i] = (bf16)pi;
-        if (EMA) ema[i] = ema_update(ema[i], pi, a.ema_d, a.ema_omd);
+        if (p_lp) p_lp[i] = lp;
+        if (EMA) ema[i] = ei;
     }
 }
 
@@ -214,9 +230,10 @@ inline long gn_slots(long len) { return (len + GN_CHUNK - 1) / GN_CHUNK; }
 
 }  // namespace
 
-extern "C" int omr_adamw_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, const unsigned char* decay_blocks, long n,
-                             int step, float lr, float b1, float b2, float eps, float weight_decay, float ema_decay, float grad_scale,
-                             const omr_step_ctl* ctl, void* stream) {
+// The one launch behind the three entries: checks, fp64 bias corrections, instance by what is asked for.
+static int adam_launch(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, const unsigned char* decay_blocks, long n,
+                       int step, float lr, float b1, float b2, float eps, float weight_decay, float ema_decay, float grad_scale,
+                       const omr_step_ctl* ctl, void* stream) {
     if (n <= 0) return OMR_OK;
     if (step < 1 || !p || !g || !m || !v) return OMR_ERR_ARG;
     if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)p_bf16 | (uintptr_t)ema) & 15) || ((uintptr_t)ctl & 7))
@@ -239,6 +256,23 @@ extern "C" int omr_adamw_ema(float* p, const float* g, float* m, float* v, void*
 #undef AW_LAUNCH
     OMR_CHECK_LAUNCH();
     return OMR_OK;
+}
+
+extern "C" int omr_adamw_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, const unsigned char* decay_blocks, long n,
+                             int step, float lr, float b1, float b2, float eps, float weight_decay, float ema_decay, float grad_scale,
+                             const omr_step_ctl* ctl, void* stream) {
+    return adam_launch(p, g, m, v, p_bf16, ema, decay_blocks, n, step, lr, b1, b2, eps, weight_decay, ema_decay, grad_scale, ctl, stream);
+}
+
+extern "C" int omr_adam(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2,
+                        float eps, float grad_scale, void* stream) {
+    return adam_launch(p, g, m, v, p_bf16, nullptr, nullptr, n, step, lr, b1, b2, eps, 0.f, 0.f, grad_scale, nullptr, stream);
+}
+
+extern "C" int omr_adam_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2,
+                                float eps, float grad_scale, const omr_step_ctl* ctl, void* stream) {
+    if (n > 0 && !ctl) return OMR_ERR_ARG;
+    return adam_launch(p, g, m, v, p_bf16, nullptr, nullptr, n, step, lr, b1, b2, eps, 0.f, 0.f, grad_scale, ctl, stream);
 }
 
 extern "C" int omr_swap_f32(float* a, float* b, long n, void* stream) {
@@ -274,18 +308,6 @@ extern "C" int omr_grad_norm(const float* g, long n, const long* range_begin, co
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(grad_norm_slots_kernel, (int)slots, GN_BLOCK, 0, s, g, rg, (GnSlot*)ws);
     hipLaunchKernelGGL(grad_norm_finish_kernel, 1, GN_BLOCK, 0, s, (const GnSlot*)ws, rg, grad_scale, max_norm, ctl);
-    OMR_CHECK_LAUNCH();
-    return OMR_OK;
-}
-
-extern "C" int omr_adam_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, long n, int step, float lr, float b1, float b2,
-                                float eps, float grad_scale, const omr_step_ctl* ctl, void* stream) {
-    if (n <= 0) return OMR_OK;
-    if (step < 1 || !ctl) return OMR_ERR_ARG;
-    double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    const long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(adam_guarded_kernel, (int)(blocks > 2048 ? 2048 : blocks), 256, 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n,
-                       (float)(lr / bc1), b1, b2, eps, (float)(1.0 / sqrt(bc2)), grad_scale, ctl);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }

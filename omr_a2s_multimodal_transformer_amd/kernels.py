@@ -309,17 +309,6 @@ def colsum_into(dy2d: Tensor, db: Tensor) -> None:
     lib().call("omr_colsum", dtype_code(dy2d.dtype), ptr(dy2d), ptr(db), M, N, ld, cur_stream())
 
 
-def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-              grad_scale: float = 1.0, p_lowp: Optional[Tensor] = None) -> None:
-    require_cuda(p, g, m, v)
-    n = p.numel()
-    for t in (p, g, m, v):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
-    if p_lowp is not None:
-        assert p_lowp.dtype == torch.bfloat16 and p_lowp.numel() == n
-    lib().call("omr_adam", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_lowp), n, step, lr, betas[0], betas[1], eps, grad_scale, cur_stream())
-
-
 class StepCtl(ctypes.Structure):
     """omr_step_ctl of include/omr_hip.h: the device-resident record of the guarded optimizer step."""
     _fields_ = [("sumsq", ctypes.c_double), ("norm", ctypes.c_float), ("clip", ctypes.c_float), ("apply", ctypes.c_int),
@@ -364,41 +353,34 @@ def grad_norm(g: Tensor, ranges, grad_scale: float, max_norm: Optional[float], w
                cur_stream())
 
 
-def adam_step_guarded(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                      grad_scale: float = 1.0, p_lowp: Optional[Tensor] = None, *, ctl: Tensor) -> None:
-    """adam_step behind the record grad_norm filled: no write at all when it says skip, else g * grad_scale * clip."""
-    require_cuda(p, g, m, v, ctl)
+DECAY_BLOCK = header_constant("OMR_ADAM_DECAY_BLOCK")        # elements per byte of decay_blocks; divides params.ALIGN
+
+
+def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+              grad_scale: float = 1.0, p_lowp: Optional[Tensor] = None, *, weight_decay: float = 0.0, decay_blocks: Optional[Tensor] = None,
+              ema: Optional[Tensor] = None, ema_decay: float = 0.0, ctl: Optional[Tensor] = None) -> None:
+    """The optimizer step, one launch (omr_adamw_ema): torch.optim.Adam; with weight_decay, decoupled weight decay in front (AdamW);
+    with ema, the moving average of the new weights behind; with ctl, behind the record grad_norm filled -- no write at all when it
+    says skip, else g * grad_scale * clip.  decay_blocks: uint8, one byte per DECAY_BLOCK elements counted from p[0] (None: every
+    element decays); ema: fp32 like p (None: no average).  p, g, m, v, p_lowp and ema start on 16-byte boundaries."""
+    require_cuda(p, g, m, v, p_lowp, decay_blocks, ema, ctl)
     n = p.numel()
     for t in (p, g, m, v):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    pp, pg, pm, pv, plp, pe = ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_lowp), ptr(ema)
     if p_lowp is not None:
         assert p_lowp.dtype == torch.bfloat16 and p_lowp.numel() == n
-    assert ctl.numel() * ctl.element_size() == ctypes.sizeof(StepCtl)
-    lib().call("omr_adam_guarded", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_lowp), n, step, lr, betas[0], betas[1], eps, grad_scale, ptr(ctl),
-               cur_stream())
-
-
-DECAY_BLOCK = 64        # elements per byte of omr_adamw_ema's decay_blocks (= params.ALIGN)
-
-
-def adamw_ema_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                   grad_scale: float = 1.0, p_lowp: Optional[Tensor] = None, *, weight_decay: float = 0.0, decay_blocks: Optional[Tensor] = None,
-                   ema: Optional[Tensor] = None, ema_decay: float = 0.0, ctl: Optional[Tensor] = None) -> None:
-    """adam_step / adam_step_guarded (ctl given) with decoupled weight decay in front and the EMA of the new weights behind, in one
-    launch (omr_adamw_ema).  decay_blocks: uint8, one byte per DECAY_BLOCK elements counted from p[0] (None: every element decays);
-    ema: fp32 like p (None: no average)."""
-    require_cuda(p, g, m, v, p_lowp, decay_blocks, ema, ctl)
-    n = p.numel()
-    for t in (p, g, m, v) + (() if ema is None else (ema,)):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
-    if p_lowp is not None:
-        assert p_lowp.dtype == torch.bfloat16 and p_lowp.numel() == n
+    if ema is not None:
+        assert ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == n
+    if (pp | pg | pm | pv | (plp or 0) | (pe or 0)) & 15:
+        raise RuntimeError("adam_step: invalid argument: p, g, m, v, p_lowp and ema must start on 16-byte boundaries (the kernel moves "
+                           "16-byte vectors); slices of the flat buffers that begin on a multiple of params.ALIGN do")
     if decay_blocks is not None:
         assert decay_blocks.dtype == torch.uint8 and decay_blocks.is_contiguous() and decay_blocks.numel() >= (n + DECAY_BLOCK - 1) // DECAY_BLOCK
     if ctl is not None:
         assert ctl.numel() * ctl.element_size() == ctypes.sizeof(StepCtl)
-    lib().call("omr_adamw_ema", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_lowp), ptr(ema), ptr(decay_blocks), n, step, lr, betas[0], betas[1], eps,
-               weight_decay, ema_decay, grad_scale, ptr(ctl), cur_stream())
+    lib().call("omr_adamw_ema", pp, pg, pm, pv, plp, pe, ptr(decay_blocks), n, step, lr, betas[0], betas[1], eps, weight_decay, ema_decay,
+               grad_scale, ptr(ctl), cur_stream())
 
 
 def swap_f32(a: Tensor, b: Tensor) -> None:

@@ -5,7 +5,7 @@ gradients, Adam moments and (bf16 mode) the bf16 compute copy.  nn.Parameters ar
 buffer that keep the reference's logical shapes (state-dict contract) while the memory
 is laid out for the kernels: conv weights [Cout,Cin,kh,kw] are stored [Cout,kh,kw,Cin] (the logical
 tensor is the channels_last-strided permutation), so MFMA B-fragments are 16-byte k-contiguous loads.
-One flat buffer means: Adam is a single kernel launch (omr_adam), zero_grad is one memset and the
+One flat buffer means: Adam is a single kernel launch (kernels.adam_step), zero_grad is one memset and the
 data-parallel gradient all-reduce runs over a few large contiguous buckets (ddp.py).
 """
 from __future__ import annotations
@@ -103,7 +103,7 @@ class FlatParams:
         # of every data gradient of the backward pass.  A per-parameter (torch version, update count) stamp guards manual edits.
         convs = [p for p in self.params if p.dim() == 4 and tuple(p.shape[2:]) == (3, 3) and p.shape[1] > 1]
         self.flip = torch.empty(sum(p.numel() for p in convs), dtype=compute_dtype, device=device)
-        self.updates = 0                 # weight updates that bypass torch's version counter (omr_adam writes through raw pointers)
+        self.updates = 0                 # weight updates that bypass torch's version counter (the step kernel writes through raw pointers)
         self._flip_table = None
         self._flip_params = convs
         pairs, off = [], 0
@@ -248,17 +248,19 @@ def decays(name: str, ndim: int, no_decay: Iterable[str]) -> bool:
 
 
 def decay_block_map(offsets: Dict[str, Tuple[int, int]], ndims: Dict[str, int], total: int, no_decay: Iterable[str]) -> List[int]:
-    """One entry per ALIGN elements of a flat buffer of `total` elements (omr_adamw_ema's decay_blocks): 1 where the block belongs
-    to a parameter that decays, else 0.  Every parameter starts on a block boundary, so a block never holds two parameters; the
-    unused end of a parameter's last block shares its entry (nothing reads those elements), and blocks no parameter touches
-    count as "no decay".  Host values only: a CPU test checks it against a hand-made table."""
+    """One entry per K.DECAY_BLOCK elements of a flat buffer of `total` elements (omr_adamw_ema's decay_blocks): 1 where the block
+    belongs to a parameter that decays, else 0.  Every parameter starts on a multiple of ALIGN, which the block size divides, so a
+    block never holds two parameters; the unused end of a parameter's last block shares its entry (nothing reads those elements),
+    and blocks no parameter touches count as "no decay".  Host values only: a CPU test checks it against a hand-made table."""
+    B = K.DECAY_BLOCK
+    assert ALIGN % B == 0
     no_decay = tuple(no_decay)
-    blocks = [0] * ((total + ALIGN - 1) // ALIGN)
+    blocks = [0] * ((total + B - 1) // B)
     for name, (off, count) in offsets.items():
         if off % ALIGN:
             raise ValueError(f"decay_block_map: {name} starts at {off}, not on a multiple of {ALIGN}")
         if decays(name, ndims[name], no_decay):
-            for k in range(off // ALIGN, (off + count + ALIGN - 1) // ALIGN):
+            for k in range(off // B, (off + count + B - 1) // B):
                 blocks[k] = 1
     return blocks
 
@@ -270,8 +272,9 @@ class FusedAdam:
 
     optim (config.OptimConfig, optional): the recipe around that update -- decoupled weight decay (torch.optim.AdamW) that leaves
     biases and norm gains alone, a learning-rate schedule (config.lr_at, indexed by step() CALLS) and an exponential moving
-    average of the weights (enable_ema / ema_weights).  A config that asks for none of them launches what no config launches;
-    otherwise every range goes through omr_adamw_ema, behind the guard's record when the guard is on.
+    average of the weights (enable_ema / ema_weights).  Every range goes through the one step kernel (kernels.adam_step,
+    omr_adamw_ema), behind the guard's record when the guard is on; what a config does not ask for is passed as its neutral value
+    (weight_decay 0, no average, no record), which leaves torch.optim.Adam's update.
 
     Parameters WITHOUT a gradient are skipped like torch.optim.Adam skips `p.grad is None` (Lightning zeroes with
     set_to_none): no update from stale momentum, no moment decay, no step count.  In MultimodalTransformer the modality-drop
@@ -314,8 +317,8 @@ class FusedAdam:
 
     @property
     def _recipe(self) -> bool:
-        """Does step() go through omr_adamw_ema?  Not with a config that asks for nothing new and no EMA: then it launches
-        omr_adam / omr_adam_guarded exactly as without a config."""
+        """Does the recipe ask for anything?  Not with a config that asks for nothing new and no EMA: then step() reads the learning
+        rate from param_groups and leaves it alone, exactly as without a config.  (The kernel is the same either way.)"""
         return self.flat.ema is not None or (self.optim is not None and not self.optim.plain)
 
     def enable_ema(self, decay: float) -> None:
@@ -378,8 +381,8 @@ class FusedAdam:
 
     # ---- guard: global gradient norm, clipping and the skip of a non-finite step, decided on the device (csrc/optim.hip)
     def enable_guard(self, max_norm: Optional[float] = None, skip_nonfinite: bool = True) -> None:
-        """From the next step() on: one omr_grad_norm over the touched sub-modules' ranges, then omr_adam_guarded instead of
-        omr_adam.  max_norm: clip the gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_; None = no clipping).
+        """From the next step() on: one omr_grad_norm over the touched sub-modules' ranges, then the step kernel behind the
+        record it filled.  max_norm: clip the gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_; None = no clipping).
         A step whose gradient holds inf / NaN (or whose sum of squares overflows) writes nothing and does not count.  That
         holds whenever the guard is on -- a clip factor computed from a non-finite norm has no meaning -- so skip_nonfinite only
         says whether a guard WITHOUT clipping is wanted; enable_guard(None, False) asks for nothing and is refused.
@@ -392,7 +395,7 @@ class FusedAdam:
         self._guard = _Guard(self.flat, max_norm)
 
     def disable_guard(self) -> None:
-        """Back to the unguarded path (omr_adam alone); the step counts and `skipped` stay."""
+        """Back to the unguarded path (the step kernel without a record); the step counts and `skipped` stay."""
         self.settle()
         self._guard = None
 
@@ -458,27 +461,17 @@ class FusedAdam:
                 runs.append([b, e, self.steps[n]])
         if guard is not None:
             K.grad_norm(f.grad, [self.ranges[n] for n in names], grad_scale, guard.max_norm, guard.ws, guard.ctl)
-        recipe = self._recipe
-        if recipe:
+        cfg = self.optim
+        if cfg is not None and self._recipe:
             # The schedule is indexed by CALLS: a step the device skips still advances it, so no host decision waits for the guard.
-            cfg = self.optim
-            lr = g["lr"] if cfg is None else lr_at(cfg, self.calls)
-            wd = 0.0 if cfg is None else cfg.weight_decay
-            for b, e, st in runs:
-                K.adamw_ema_step(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, lr, g["betas"], g["eps"], grad_scale,
-                                 p_lowp=None if f.lowp is None else f.lowp[b:e], weight_decay=wd,
-                                 decay_blocks=None if self._decay_blocks is None else self._decay_blocks[b // ALIGN:],
-                                 ema=None if f.ema is None else f.ema[b:e], ema_decay=self.ema_decay or 0.0,
-                                 ctl=None if guard is None else guard.ctl)
-            g["lr"] = lr
+            g["lr"] = lr_at(cfg, self.calls)
         self.calls += 1
-        for b, e, st in () if recipe else runs:
-            if guard is None:
-                K.adam_step(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, g["lr"], g["betas"], g["eps"], grad_scale,
-                            p_lowp=None if f.lowp is None else f.lowp[b:e])
-            else:
-                K.adam_step_guarded(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, g["lr"], g["betas"], g["eps"], grad_scale,
-                                    p_lowp=None if f.lowp is None else f.lowp[b:e], ctl=guard.ctl)
+        for b, e, st in runs:
+            K.adam_step(f.master[b:e], f.grad[b:e], f.exp_avg[b:e], f.exp_avg_sq[b:e], st, g["lr"], g["betas"], g["eps"], grad_scale,
+                        p_lowp=None if f.lowp is None else f.lowp[b:e], weight_decay=0.0 if cfg is None else cfg.weight_decay,
+                        decay_blocks=None if self._decay_blocks is None else self._decay_blocks[b // K.DECAY_BLOCK:],
+                        ema=None if f.ema is None else f.ema[b:e], ema_decay=self.ema_decay or 0.0,
+                        ctl=None if guard is None else guard.ctl)
         if guard is not None:
             guard.push(k, tuple(names), grad_scale)
         f.updates += 1

@@ -4,7 +4,7 @@ inputs the kernel-level tests share.  No GPU here: tests/test_optim_refs_cpu.py 
 
 The bound, u = 2^-24, first order, for inputs whose gradient g > 0 and first moment m >= 0 (`inputs` below builds such): every term
 of m = b1 m + (1 - b1) g and of v is then non-negative, so the relative error of m and v is the COUNT of roundings a term passes
-through -- no cancellation.  Roundings of the kernel per element in step j of a run of k steps (csrc/adam_update.h, csrc/optim.hip),
+through -- no cancellation.  Roundings of the kernel per element in step j of a run of k steps (adam_update in csrc/optim.hip),
 against exact arithmetic on the same fp32 arguments:
   gi = (g * scale) * clip                                    2
   m  = fma(b1, m, (1 - b1) * gi)      1 - b1: 1, product: 1, plus gi's 2 = 4 on the new term; the fma rounds the sum once per

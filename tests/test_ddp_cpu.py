@@ -221,7 +221,9 @@ def test_trainer_world2_gloo_equals_single_process_mean_gradient_training():
 MM_STEPS = 12
 
 
-def _cpu_adam_step(p, g, m, v, step, lr, betas, eps, grad_scale, p_lowp=None):
+def _cpu_adam_step(p, g, m, v, step, lr, betas, eps, grad_scale, p_lowp=None, *, weight_decay=0.0, decay_blocks=None, ema=None,
+                   ema_decay=0.0, ctl=None):
+    assert weight_decay == 0 and decay_blocks is None and ema is None and ema_decay == 0 and ctl is None      # plain Adam is all this stands in for
     b1, b2 = betas
     g = g * grad_scale
     m.mul_(b1).add_(g, alpha=1 - b1)

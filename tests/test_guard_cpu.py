@@ -77,6 +77,7 @@ def test_step_ctl_mirror_has_the_c_layout():
 
 def test_constants_come_from_the_header():
     assert K.GRAD_NORM_CHUNK == 256 * K.GRAD_NORM_K and K.GRAD_NORM_K % 4 == 0 and K.GRAD_NORM_MAX_RANGES == 16
+    assert K.DECAY_BLOCK == _lib.header_constant("OMR_ADAM_DECAY_BLOCK") == 64
     protos = _lib.parse_header()
     assert protos["omr_adam_guarded"][1][:12] == protos["omr_adam"][1][:12]         # omr_adam's arguments, then the record
     assert protos["omr_adam_guarded"][1][12:] == ["const omr_step_ctl* ctl", "void* stream"]

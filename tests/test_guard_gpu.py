@@ -182,7 +182,7 @@ def test_guarded_with_clip_one_is_omr_adam_bit_for_bit(lowp):
             p, g, m, v, lp = adam_state(n, 100 * n + step, lowp)
             p2, m2, v2, lp2 = p.clone(), m.clone(), v.clone(), None if lp is None else lp.clone()
             K.adam_step(p, g, m, v, step, 1e-3, grad_scale=0.5, p_lowp=lp)
-            K.adam_step_guarded(p2, g, m2, v2, step, 1e-3, grad_scale=0.5, p_lowp=lp2, ctl=one)
+            K.adam_step(p2, g, m2, v2, step, 1e-3, grad_scale=0.5, p_lowp=lp2, ctl=one)
             for a, b, what in ((p, p2, "p"), (m, m2, "m"), (v, v2, "v")) + (((lp, lp2, "p_bf16"),) if lowp else ()):
                 same_bits(a, b, f"n={n} step={step} {what}")
             assert not torch.equal(p, adam_state(n, 100 * n + step, lowp)[0])                # (the step did move p)
@@ -195,7 +195,7 @@ def test_guarded_with_apply_zero_writes_nothing(lowp):
         for step in (1, 2, 1000):
             before = adam_state(n, 7 * n + step, lowp)
             p, g, m, v, lp = [None if t is None else t.clone() for t in before]
-            K.adam_step_guarded(p, g, m, v, step, 1e-3, p_lowp=lp, ctl=skip)
+            K.adam_step(p, g, m, v, step, 1e-3, p_lowp=lp, ctl=skip)
             for a, b, what in zip((p, g, m, v, lp), before, ("p", "g", "m", "v", "p_bf16")):
                 if a is not None:
                     same_bits(a, b, f"n={n} step={step} {what}")
@@ -211,14 +211,14 @@ def test_guarded_clipping_equals_omr_adam_on_the_clipped_gradient():
     clip = K.read_step_ctl(ctl.cpu()).clip
     assert abs(clip - 0.1) < 1e-5
     p2, m2, v2, lp2 = p.clone(), m.clone(), v.clone(), lp.clone()
-    K.adam_step_guarded(p, g, m, v, 3, 1e-3, p_lowp=lp, ctl=ctl)
+    K.adam_step(p, g, m, v, 3, 1e-3, p_lowp=lp, ctl=ctl)
     K.adam_step(p2, g * clip, m2, v2, 3, 1e-3, p_lowp=lp2)                                   # g' = g * clip in fp32 (clip is an fp32 value)
     for a, b, what in ((p, p2, "p"), (m, m2, "m"), (v, v2, "v"), (lp, lp2, "p_bf16")):
         same_bits(a, b, what)
 
 
 def test_guarded_clipping_tracks_fp64_clip_grad_norm_and_adam():
-    """Five steps of torch.nn.utils.clip_grad_norm_ + torch.optim.Adam in fp64 against grad_norm + adam_step_guarded, at the
+    """Five steps of torch.nn.utils.clip_grad_norm_ + torch.optim.Adam in fp64 against grad_norm + adam_step(ctl=...), at the
     tolerance of the existing Adam parity test (tests/test_kernels_gpu.py::test_colsum_adam_argmax: rtol 1e-5, atol 1e-7)."""
     n, lr, steps = 5000, 1e-3, 5
     gen = torch.Generator().manual_seed(21)
@@ -237,7 +237,7 @@ def test_guarded_clipping_tracks_fp64_clip_grad_norm_and_adam():
     for t, gt in enumerate(grads):
         gd = gt.to(DEV)
         K.grad_norm(gd, [(0, n)], 1.0, max_norm, ws, ctl)
-        K.adam_step_guarded(p, gd, m, v, t + 1, lr, ctl=ctl)
+        K.adam_step(p, gd, m, v, t + 1, lr, ctl=ctl)
     torch.testing.assert_close(p.cpu(), ref.detach().float(), rtol=1e-5, atol=1e-7)
     assert (p.cpu() - p0).abs().max() > 1e-3
 

@@ -1,6 +1,7 @@
-"""omr_adamw_ema and omr_swap_f32 on the GPU: bit for bit omr_adam / omr_adam_guarded when nothing new is asked for, the skip, the
-decay-block map, the EMA's exact edges, and decay and EMA values against the fp64 restatement of tests/optim_refs.py inside the
-bound derived there (P_OPS(k) = 14 + 2 k roundings per step on |p| + |t|, E_OPS = 3 on max(|ema|, |p|); tests/test_optim_refs_cpu.py
+"""omr_adamw_ema and omr_swap_f32 on the GPU: bit for bit the ENTRIES omr_adam / omr_adam_guarded when nothing new is asked for
+(they are argument adapters onto the same launch: the tests prove that every argument is passed through; that the one kernel
+computes what the three kernels before it computed is tests/test_optim_bits_gpu.py's job), the skip, the decay-block map, the
+EMA's exact edges, and decay and EMA values against the fp64 restatement of tests/optim_refs.py inside the bound derived there (P_OPS(k) = 14 + 2 k roundings per step on |p| + |t|, E_OPS = 3 on max(|ema|, |p|); tests/test_optim_refs_cpu.py
 shows an fp32 transcription of the kernel's order inside that bound on these very inputs)."""
 import functools
 
@@ -12,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 import optim_refs as R  # noqa: E402
 from omr_a2s_multimodal_transformer_amd import kernels as K  # noqa: E402
+from omr_a2s_multimodal_transformer_amd._lib import cur_stream, lib, ptr  # noqa: E402
 
 DEV = "cuda:0"
 GRID_CAP, THREADS = 2048, 256                          # csrc/optim.hip: AW_MAX_GRID, AW_THREADS
@@ -20,6 +22,7 @@ SIZES = [1, 3, 4, 63, 64, 65, 4 * 1024 + 1, N_WRAP]
 STEPS = 4
 H = R.HYPER
 NAN = float("nan")
+OMR_ERR_ARG = -1                                       # csrc/omr_common.h
 
 
 def bits(t):
@@ -50,8 +53,13 @@ def clone(st):
 
 
 def new_step(st, g, step, *, ema=False, **kw):
-    K.adamw_ema_step(st["p"], g, st["m"], st["v"], step, H["lr"], (H["b1"], H["b2"]), H["eps"], R.GRAD_SCALE, p_lowp=st["lp"],
-                     ema=st["ema"] if ema else None, **kw)
+    K.adam_step(st["p"], g, st["m"], st["v"], step, H["lr"], (H["b1"], H["b2"]), H["eps"], R.GRAD_SCALE, p_lowp=st["lp"],
+                ema=st["ema"] if ema else None, **kw)
+
+
+def entry_args(st, g, step):
+    """The arguments omr_adam and omr_adam_guarded share, for a call of the C entry itself."""
+    return (ptr(st["p"]), ptr(g), ptr(st["m"]), ptr(st["v"]), ptr(st["lp"]), st["p"].numel(), step, H["lr"], H["b1"], H["b2"], H["eps"], R.GRAD_SCALE)
 
 
 def assert_state_bits(a, b, what, keys=("p", "m", "v", "lp")):
@@ -76,7 +84,7 @@ def test_plain_is_omr_adam_bit_for_bit(n):
         b = clone(a)
         start = a["p"].clone()
         for j in range(3):
-            K.adam_step(a["p"], grads[j], a["m"], a["v"], R.FIRST_STEP + j, H["lr"], (H["b1"], H["b2"]), H["eps"], R.GRAD_SCALE, p_lowp=a["lp"])
+            lib().call("omr_adam", *entry_args(a, grads[j], R.FIRST_STEP + j), cur_stream())
             new_step(b, grads[j], R.FIRST_STEP + j)
             assert_state_bits(a, b, f"n={n} lowp={lowp} step {j}")
         assert not torch.equal(a["p"], start)
@@ -90,7 +98,7 @@ def test_guarded_is_omr_adam_guarded_bit_for_bit(n):
     norm = float(np.sqrt((host_inputs(n)[4][0].astype(np.float64) ** 2).sum())) * R.GRAD_SCALE
     ctl, rec = real_ctl(grads[0], norm / 10)
     assert rec.apply == 1 and 0.09 < rec.clip < 0.11
-    K.adam_step_guarded(a["p"], grads[0], a["m"], a["v"], R.FIRST_STEP, H["lr"], (H["b1"], H["b2"]), H["eps"], R.GRAD_SCALE, p_lowp=a["lp"], ctl=ctl)
+    lib().call("omr_adam_guarded", *entry_args(a, grads[0], R.FIRST_STEP), ptr(ctl), cur_stream())
     new_step(b, grads[0], R.FIRST_STEP, ctl=ctl)
     assert_state_bits(a, b, f"n={n}")
     c = clone(device_state(n)[0])
@@ -198,15 +206,30 @@ def test_adamw_ema_refuses_bad_arguments():
     for off in ("p", "m", "v", "ema", "lp"):                         # one pointer one element off a 16-byte boundary
         t = {k: (x[1:65] if k == off else x[:64]) for k, x in wide.items()}
         with pytest.raises(RuntimeError, match="invalid argument"):
-            K.adamw_ema_step(t["p"], g2[:64], t["m"], t["v"], 1, *args, p_lowp=t["lp"], ema=t["ema"], ema_decay=0.5)
+            K.adam_step(t["p"], g2[:64], t["m"], t["v"], 1, *args, p_lowp=t["lp"], ema=t["ema"], ema_decay=0.5)
     with pytest.raises(RuntimeError, match="invalid argument"):
-        K.adamw_ema_step(st["p"][:64], g2[1:65], st["m"][:64], st["v"][:64], 1, *args)
+        K.adam_step(st["p"][:64], g2[1:65], st["m"][:64], st["v"][:64], 1, *args)
     with pytest.raises(RuntimeError, match="invalid argument"):
-        K.adamw_ema_step(st["p"], grads[0], st["m"], st["v"], 0, *args)                      # steps are 1-based
+        K.adam_step(st["p"], grads[0], st["m"], st["v"], 0, *args)                      # steps are 1-based
     for bad in (-0.1, 1.5, NAN):
         with pytest.raises(RuntimeError, match="invalid argument"):
-            K.adamw_ema_step(st["p"], grads[0], st["m"], st["v"], 1, *args, ema=st["ema"], ema_decay=bad)
+            K.adam_step(st["p"], grads[0], st["m"], st["v"], 1, *args, ema=st["ema"], ema_decay=bad)
     before = clone(st)
+    torch.cuda.synchronize()
+    assert_state_bits(st, before, "a refused call launches nothing", keys=("p", "m", "v", "lp", "ema"))
+
+
+def test_adam_entries_refuse_a_misaligned_gradient():
+    """omr_adam and omr_adam_guarded keep omr_adamw_ema's contract: g one element off a 16-byte boundary is OMR_ERR_ARG, nothing runs."""
+    st, grads = device_state(65)
+    g2 = torch.cat([grads[0], grads[0]])
+    ctl, rec = real_ctl(grads[0], None)
+    assert rec.apply == 1
+    before = clone(st)
+    part = {k: t[:64] for k, t in st.items()}
+    assert lib().query("omr_adam", *entry_args(part, g2[1:65], 1), cur_stream()) == OMR_ERR_ARG
+    assert lib().query("omr_adam_guarded", *entry_args(part, g2[1:65], 1), ptr(ctl), cur_stream()) == OMR_ERR_ARG
+    assert lib().query("omr_adam_guarded", *entry_args(part, g2[:64], 1), None, cur_stream()) == OMR_ERR_ARG      # and still no NULL record
     torch.cuda.synchronize()
     assert_state_bits(st, before, "a refused call launches nothing", keys=("p", "m", "v", "lp", "ema"))
 

@@ -80,7 +80,7 @@ def pieces(opt, steps):
     K.grad_norm(f.grad, [(0, f.total)], 1.0, 1.0, ws, ctl)
     return dict(grad_norm=piece(lambda: K.grad_norm(f.grad, [(0, f.total)], 1.0, 1.0, ws, ctl), steps),
                 adam=piece(lambda: K.adam_step(*args, p_lowp=f.lowp), steps),
-                adam_guarded=piece(lambda: K.adam_step_guarded(*args, p_lowp=f.lowp, ctl=ctl), steps),
+                adam_guarded=piece(lambda: K.adam_step(*args, p_lowp=f.lowp, ctl=ctl), steps),
                 record_copy=piece(lambda: host.copy_(ctl, non_blocking=True), steps))
 
 

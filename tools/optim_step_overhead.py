@@ -1,9 +1,10 @@
 """What the optimizer recipe costs at the benchmark size: one step over the C2 model's flat buffers (bench.py CONFIGS["c2"]: image
-encoder + 6-layer d_model=256 decoder, bf16 compute copy) through omr_adam / omr_adam_guarded (the path without a recipe) and
-through omr_adamw_ema in three settings -- decay only, EMA only, decay + EMA -- each unguarded and behind the guard's record.
+encoder + 6-layer d_model=256 decoder, bf16 compute copy) through kernels.adam_step (omr_adamw_ema, the one step kernel): plain and
+guarded (what a step without a recipe launches; before the three kernels became one these two rows were omr_adam's and
+omr_adam_guarded's scalar kernels), and decay only, EMA only, decay + EMA -- each unguarded and behind the guard's record.
 
 All variants run inside ONE process, interleaved: every round times each variant once, in a fixed order, over `--steps`
-back-to-back launches between two events; the table gives the median over the rounds and the spread.  omr_adam moves five fp32
+back-to-back launches between two events; the table gives the median over the rounds and the spread.  The plain step moves five fp32
 streams and one bf16 stream per element (g, p, m, v in; p, m, v, bf16 out -> 30 bytes), the full recipe seven and one (+ ema in and
 out -> 38 bytes, plus one byte of the decay map per 64 elements); the yardstick beside each time is that traffic at the
 device-copy rate DESIGN.md section 3 quotes (5.25 TB/s).  The guarded variants read a record filled once (clip < 1, apply = 1);
@@ -63,15 +64,14 @@ def main():
     decay = dict(weight_decay=0.1, decay_blocks=blocks)
     ema = dict(ema=f.ema, ema_decay=0.999)
     variants = {
-        "omr_adam": (lambda: K.adam_step(*base, p_lowp=f.lowp), 30),
-        "omr_adam_guarded": (lambda: K.adam_step_guarded(*base, p_lowp=f.lowp, ctl=ctl), 30),
-        "adamw_ema plain": (lambda: K.adamw_ema_step(*base, p_lowp=f.lowp), 30),
-        "adamw_ema decay": (lambda: K.adamw_ema_step(*base, p_lowp=f.lowp, **decay), 30),
-        "adamw_ema ema": (lambda: K.adamw_ema_step(*base, p_lowp=f.lowp, **ema), 38),
-        "adamw_ema decay+ema": (lambda: K.adamw_ema_step(*base, p_lowp=f.lowp, **decay, **ema), 38),
-        "adamw_ema decay guarded": (lambda: K.adamw_ema_step(*base, p_lowp=f.lowp, ctl=ctl, **decay), 30),
-        "adamw_ema ema guarded": (lambda: K.adamw_ema_step(*base, p_lowp=f.lowp, ctl=ctl, **ema), 38),
-        "adamw_ema decay+ema guarded": (lambda: K.adamw_ema_step(*base, p_lowp=f.lowp, ctl=ctl, **decay, **ema), 38),
+        "plain": (lambda: K.adam_step(*base, p_lowp=f.lowp), 30),
+        "guarded": (lambda: K.adam_step(*base, p_lowp=f.lowp, ctl=ctl), 30),
+        "decay": (lambda: K.adam_step(*base, p_lowp=f.lowp, **decay), 30),
+        "ema": (lambda: K.adam_step(*base, p_lowp=f.lowp, **ema), 38),
+        "decay+ema": (lambda: K.adam_step(*base, p_lowp=f.lowp, **decay, **ema), 38),
+        "decay guarded": (lambda: K.adam_step(*base, p_lowp=f.lowp, ctl=ctl, **decay), 30),
+        "ema guarded": (lambda: K.adam_step(*base, p_lowp=f.lowp, ctl=ctl, **ema), 38),
+        "decay+ema guarded": (lambda: K.adam_step(*base, p_lowp=f.lowp, ctl=ctl, **decay, **ema), 38),
         "swap_f32": (lambda: K.swap_f32(f.master, f.ema), 16),
     }
     times = {k: [] for k in variants}
