@@ -397,7 +397,7 @@ class Decoder(nn.Module):
         kvs = [None] * len(layers)
         if pack is not None:
             sink = Fn.KVGradSink()
-            kvs = Fn.FusedCrossKVFn.apply(memory, pack, sink)
+            kvs = Fn.FusedCrossKVFn.apply(memory, pack, sink, layers[0].multihead_attn.in_proj_weight)
             for li, kv in enumerate(kvs):
                 kv.omr_grad_sink = (sink, li)
         for li, (layer, kv) in enumerate(zip(layers, kvs)):

@@ -581,10 +581,12 @@ class FusedCrossKVFn(Function):
     tensor in every layer, so it is read once instead of L times, and its gradient is one GEMM over the concatenated K|V
     gradients instead of L GEMMs plus L-1 gradient adds.  `pack` holds row-group views of the layers' packed in_proj
     parameters where they lie back to back in the flat buffer (params._placement_order).  Returns L views [B,S,2d] of one
-    [B,S,L*2d] buffer."""
+    [B,S,L*2d] buffer.  `anchor` is any tensor that requires a gradient (the decoder hands over a packed parameter) and gets none
+    here: the parameters live in `pack`, which autograd does not see, so with a memory that needs no gradient (a frozen or
+    detached encoder) the node would otherwise not be part of the graph and the K|V weight gradients would never be formed."""
 
     @staticmethod
-    def forward(ctx, memory, pack, sink):
+    def forward(ctx, memory, pack, sink, anchor):
         L, d = pack["L"], pack["d"]
         mem2 = memory.reshape(-1, d)
         Rm = mem2.shape[0]
@@ -616,7 +618,7 @@ class FusedCrossKVFn(Function):
             dmem = torch.empty((Rm, d), dtype=mem2.dtype, device=mem2.device)
             K.gemm_row_groups(g2, pack["w"], dmem, Rm, d, L * 2 * d, trans_b=True, group=(2 * d, 3 * d, d, 2))
             dmem = dmem.view(ctx.mshape)
-        return dmem, None, None
+        return dmem, None, None, None
 
 
 class CrossEntropyFn(Function):

@@ -1,7 +1,8 @@
 """The DMA-fed tall GEMM (csrc/gemm_tall.hip): C[M][256] = A[M][K] . B[K][256] for at least 192 row tiles of 256 -- the
 data gradient of the all-layer K|V projection (functional.FusedCrossKVFn.backward; decoder.py:86-95).  Against torch fp32 on
 the same bf16 operands: plain and through the reduction-side row-group view, with a ragged last row tile, strided operands,
-one and several k-tiles."""
+one and several k-tiles.
+Every element of every row, exactly, through a second tile of a workgroup: tests/test_gemm_branches_gpu.py."""
 import math
 
 import pytest

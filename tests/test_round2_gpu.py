@@ -1,5 +1,6 @@
 """Round-2 GPU parity: the HIP modules against the reference's round-2 golden vectors (tests/golden/gen_golden_r2.py):
-non-degenerate shapes (deepest feature maps 4x20 / 13x12), weighted late-fusion decode, Adam with skipped sub-modules."""
+non-degenerate shapes (deepest feature maps 4x20 / 13x12), weighted late-fusion decode, Adam with skipped sub-modules.
+The grouped weight gradient bit for bit at every element, padding and Q rows included: tests/test_gemm_branches_gpu.py."""
 import random
 
 import numpy as np

@@ -1,6 +1,7 @@
 """Round-3 GPU tests: the reference's own operating point (run_experiments.sh:13: 8 layers, attn_window 100; the largest
 GRANDSTAFF shapes of grandstaff/max_lens/ImgDist_ar_w2i_kern.json: 361x4412 image -> S = 12 696, T = 1 268), recovery of the
-side stream after a failed backward pass, the native weighted-fusion executor."""
+side stream after a failed backward pass, the native weighted-fusion executor.
+The panel GEMM at every element, without a bias, with an odd tile count and through row groups: tests/test_gemm_branches_gpu.py."""
 import random
 
 import numpy as np
