@@ -21,7 +21,7 @@
 #include "omr_common.h"
 #include "omr_hip.h"
 
-#include "gemm_args.h"
+#include "gemm_steps.h"
 
 namespace {
 
@@ -65,15 +65,7 @@ __device__ __forceinline__ void mma32(f32x16& acc, u8x16 a, u8x16 b) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a2[1], b2[1], acc, 0, 0, 0);
 }
 
-int omr_gemm_panel_bf16(const GemmArgs& g, hipStream_t s);      // gemm_panel.hip
-int omr_gemm_tall_bf16(const GemmArgs& g, hipStream_t s);       // gemm_tall.hip
-
 namespace {
-
-// physical - logical row offset of the tile that starts at logical row i (tiles never straddle a group: host-checked)
-__device__ __forceinline__ long grp_delta(const GemmArgs& g, int operand, int i) {
-    return g.grp_operand == operand ? (long)(i / g.grp) * (g.grp_stride - g.grp) + g.grp_base : 0;
-}
 
 template <typename T> struct GemmCfg {
     static constexpr int VEC = Frag<T>::N;
@@ -159,12 +151,8 @@ __device__ __forceinline__ typename Frag<T>::type load_frag(const T* lds, int ro
     typedef GemmCfg<T> Cfg;
     typedef typename Frag<T>::type F;
     if constexpr (UseTrRead<T, TR>::value) {
-        typedef __attribute__((address_space(3))) bf16x4 LdsV4;
         const int q = (lane & 15) >> 2, col = row0 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4, k = ks + 8 * (lane >> 5) + q;
-        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LdsV4*)(lds + k * Cfg::TPITCH + col));
-        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LdsV4*)(lds + (k + 4) * Cfg::TPITCH + col));
-        const bf16x8 f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return f;
+        return tr_frag_bf16(lds + k * Cfg::TPITCH + col, 4 * Cfg::TPITCH * (int)sizeof(T));
     } else {
         return *reinterpret_cast<const F*>(&lds[(row0 + (lane & 31)) * Cfg::PITCH + ks + (lane >> 5) * Cfg::VEC]);
     }
@@ -202,15 +190,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int block_ind
     }
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    Stager<T, TA> sa;
-    Stager<T, TB> sb;
+    acc_clear(acc);
     float cs[Cfg::VEC];
 #pragma unroll
     for (int e = 0; e < Cfg::VEC; ++e) cs[e] = 0.f;
@@ -252,29 +232,31 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int block_ind
                 mma_slab();
             }
         __syncthreads();
-    } else {
-    sa.load(A, g.lda, m0, g.M, kbeg, kend, tid);
-    sb.load(B + grp_delta(g, 2, kbeg) * g.ldb, g.ldb, n0, g.N, kbeg, kend, tid);
-    if (do_cs) sa.add_colsum(cs);
-    sa.store(As, tid);
-    sb.store(Bs, tid);
-    __syncthreads();
-
-    for (int k0 = kbeg; k0 < kend; k0 += Cfg::BK) {
-        const bool more = (k0 + Cfg::BK) < kend;
-        if (more) {
-            sa.load(A, g.lda, m0, g.M, k0 + Cfg::BK, kend, tid);
-            sb.load(B + grp_delta(g, 2, k0 + Cfg::BK) * g.ldb, g.ldb, n0, g.N, k0 + Cfg::BK, kend, tid);
-        }
-        mma_slab();
+    } else {      // the pipelined loop: slab k + 1 is requested before the MFMAs of slab k and stored to LDS after them
+        Stager<T, TA> sa;
+        Stager<T, TB> sb;
+        sa.load(A, g.lda, m0, g.M, kbeg, kend, tid);
+        sb.load(B + grp_delta(g, 2, kbeg) * g.ldb, g.ldb, n0, g.N, kbeg, kend, tid);
+        if (do_cs) sa.add_colsum(cs);
+        sa.store(As, tid);
+        sb.store(Bs, tid);
         __syncthreads();
-        if (more) {
-            if (do_cs) sa.add_colsum(cs);   // here the prefetched registers are needed anyway (no extra wait)
-            sa.store(As, tid);
-            sb.store(Bs, tid);
+
+        for (int k0 = kbeg; k0 < kend; k0 += Cfg::BK) {
+            const bool more = (k0 + Cfg::BK) < kend;
+            if (more) {
+                sa.load(A, g.lda, m0, g.M, k0 + Cfg::BK, kend, tid);
+                sb.load(B + grp_delta(g, 2, k0 + Cfg::BK) * g.ldb, g.ldb, n0, g.N, k0 + Cfg::BK, kend, tid);
+            }
+            mma_slab();
             __syncthreads();
+            if (more) {
+                if (do_cs) sa.add_colsum(cs);   // here the prefetched registers are needed anyway (no extra wait)
+                sa.store(As, tid);
+                sb.store(Bs, tid);
+                __syncthreads();
+            }
         }
-    }
     }
 
     if (do_cs) {   // combine the 256 per-thread partials in LDS (operand tiles are dead), then ONE global atomic per row per block
@@ -294,7 +276,6 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int block_ind
     const float* biasp = g.bias ? g.bias + grp_delta(g, 1, n0) : nullptr;
     if constexpr (SWAP) {
         // ---- bf16 C: lane = row (lane & 31) of M-block i; register r = column (r&3) + 8(r>>2) + 4(lane>>5) of N-block j
-        typedef __attribute__((ext_vector_type(4))) bf16 B4;
         T* Cs = smem + wave * (64 * Cfg::CPITCH);          // all waves passed the last barrier: operand tiles are dead
         const int hsel = 4 * (lane >> 5);
 #pragma unroll
@@ -309,16 +290,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int block_ind
             for (int i = 0; i < 2; ++i) {
                 T* crow = Cs + (i * 32 + (lane & 31)) * Cfg::CPITCH + j * 32 + hsel;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    B4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = acc[i][j][4 * q + e] + bv[4 * q + e];
+                for (int q = 0; q < 4; ++q)
+                    *reinterpret_cast<bf16x4*>(crow + 8 * q) = pack_ct4(acc[i][j], q, [&](float v, int e) {
+                        v = v + bv[4 * q + e];
                         if (g.relu) v = fmaxf(v, 0.f);
-                        o[e] = (bf16)v;
-                    }
-                    *reinterpret_cast<B4*>(crow + 8 * q) = o;
-                }
+                        return v;
+                    });
             }
         }
         // same-wave LDS writes are ordered before the reads below (in-order LDS queue); no block barrier needed
@@ -382,6 +359,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     gemm_body<T, TC, TA, TB, FULLK>(g, blockIdx.x);
 }
 
+struct GemmPlan { int ksplit_len, splits, mt, nt, total, chunk, blocks; };      // gemm_plan below
+// the part of a plan a kernel reads: plan -> GemmArgs / DwProb on the host, DwProb -> GemmArgs in the grouped kernel
+template <typename D, typename S> __host__ __device__ __forceinline__ void put_plan(D& d, const S& s) {
+    d.ksplit_len = s.ksplit_len; d.mt = s.mt; d.nt = s.nt; d.chunk = s.chunk; d.total = s.total;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Grouped weight-gradient GEMM: dW_p[n_out][n_in] += dY_p^T . X_p (+ db_p += column sums of dY_p) for up to DW_MAX linear
 // layers in ONE launch.  A decoder layer's dW products are 256 x 256 outputs reduced over 16 384 rows: launched one by one
@@ -395,42 +378,49 @@ struct DwProb {
 };
 constexpr int DW_MAX = 24;
 struct DwGroup { int nprob, pad; DwProb p[DW_MAX]; };
+static_assert(sizeof(DwGroup) == 2312, "the table travels as kernel arguments: DwProb stays the compact record, not a GemmArgs (160 bytes each)");
 
 template <typename T>
 __global__ __launch_bounds__(256) void gemm_dw_grouped_kernel(DwGroup grp) {
     int pi = 0;
     for (int i = 1; i < grp.nprob; ++i) pi = ((int)blockIdx.x >= grp.p[i].block0) ? i : pi;
     const DwProb& q = grp.p[pi];
-    GemmArgs g;
-    g.A = q.A; g.B = q.B; g.C = q.C; g.bias = nullptr; g.M = q.M; g.N = q.N; g.K = q.K; g.lda = q.lda; g.ldb = q.ldb; g.ldc = q.ldc;
-    g.relu = 0; g.accum = 1; g.atomic = 1; g.ksplit_len = q.ksplit_len; g.colsum_a = q.colsum;
-    g.mt = q.mt; g.nt = q.nt; g.chunk = q.chunk; g.total = q.total;
-    g.drop_thresh = 0; g.drop_scale = 1.f; g.drop_seed = 0;
+    GemmArgs g;                          // the defaults plus what the record carries
+    g.A = q.A; g.B = q.B; g.C = q.C; g.M = q.M; g.N = q.N; g.K = q.K; g.lda = q.lda; g.ldb = q.ldb; g.ldc = q.ldc;
+    g.accum = 1; g.atomic = 1; g.colsum_a = q.colsum;
+    put_plan(g, q);
     g.grp = q.grp; g.grp_stride = q.grp_stride; g.grp_base = q.grp_base; g.grp_operand = q.grp ? 3 : 0;
-    g.scale_a = nullptr; g.scale_b = nullptr;
     gemm_body<T, float, true, true, false>(g, (int)blockIdx.x - q.block0);
 }
 
-template <typename T, typename TC> int launch(GemmArgs g, int ta, int tb, int splits, hipStream_t s) {
-    g.nt = cdiv(g.N, BN); g.mt = cdiv(g.M, BM);
+// The tile plan of one problem: the k range cut into `want_splits` pieces of whole k-tiles (which may give fewer splits than
+// asked for), the tile grid, the XCD chunking (see tile_of_block) and the block count padded to whole rounds of 8 chunks.
+GemmPlan gemm_plan(int M, int N, int K, int bk, int want_splits) {
+    GemmPlan p;
+    p.ksplit_len = cdiv(cdiv(K, want_splits), bk) * bk;
+    p.splits = cdiv(K, p.ksplit_len);
+    p.mt = cdiv(M, BM); p.nt = cdiv(N, BN);
+    p.total = p.nt * p.mt * p.splits;
+    p.chunk = p.splits > 1 ? p.nt * p.mt : p.nt;
+    p.blocks = cdiv(p.total / p.chunk, 8) * 8 * p.chunk;
+    return p;
+}
+
+// Only what can be launched is instantiated: per bf16 / fp32 type pair the four transposes and FULLK for the two without transA;
+// for fp8 the NT instance alone (omr_gemm_fp8 has no transposed operands).
+template <typename T, typename TC> int launch(GemmArgs g, int ta, int tb, const GemmPlan& p, hipStream_t s) {
+    put_plan(g, p);
     // FULLK keeps all four k-slabs of both operands in staging registers: fine for 2- and 4-byte elements, 42-75 spilled
     // registers with fp8's 16-element chunks -- the fp8 GEMMs take the pipelined loop.
     constexpr bool CAN_FULLK = !std::is_same<T, fp8>::value;
-    const bool fullk = CAN_FULLK && !ta && splits == 1 && g.K <= 4 * GemmCfg<T>::BK;
-    g.total = g.nt * g.mt * splits;
-    g.chunk = splits > 1 ? g.nt * g.mt : g.nt;
-    const int nchunks = g.total / g.chunk;
-    dim3 grid((unsigned)(cdiv(nchunks, 8) * 8 * g.chunk)), block(256);
-    bool done = false;
-    if constexpr (CAN_FULLK) {
-        if (!ta && !tb && fullk) { hipLaunchKernelGGL((gemm_kernel<T, TC, false, false, true>), grid, block, 0, s, g); done = true; }
-        else if (!ta && tb && fullk) { hipLaunchKernelGGL((gemm_kernel<T, TC, false, true, true>), grid, block, 0, s, g); done = true; }
-    }
-    if (done) {}
-    else if (!ta && !tb) hipLaunchKernelGGL((gemm_kernel<T, TC, false, false, false>), grid, block, 0, s, g);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm_kernel<T, TC, false, true, false>), grid, block, 0, s, g);
-    else if (ta && !tb) hipLaunchKernelGGL((gemm_kernel<T, TC, true, false, false>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm_kernel<T, TC, true, true, false>), grid, block, 0, s, g);
+    const bool fullk = CAN_FULLK && !ta && p.splits == 1 && g.K <= 4 * GemmCfg<T>::BK;
+    void (*kernel)(GemmArgs) = nullptr;
+    if constexpr (!CAN_FULLK) kernel = (ta || tb) ? nullptr : gemm_kernel<T, TC, false, false, false>;
+    else if (ta) kernel = tb ? gemm_kernel<T, TC, true, true, false> : gemm_kernel<T, TC, true, false, false>;
+    else if (tb) kernel = fullk ? gemm_kernel<T, TC, false, true, true> : gemm_kernel<T, TC, false, true, false>;
+    else kernel = fullk ? gemm_kernel<T, TC, false, false, true> : gemm_kernel<T, TC, false, false, false>;
+    if (!kernel) return OMR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.blocks), dim3(256), 0, s, g);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
 }
@@ -451,8 +441,6 @@ extern "C" int omr_gemm(int dtype, int c_dtype, int transA, int transB, int M, i
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.relu = relu; g.accum = accumulate; g.atomic = split_k > 1; g.colsum_a = colsum_a;
     if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && (split_k > 1 || accumulate || transA))) return OMR_ERR_ARG;      // dropout needs the final value
-    g.grp = g.grp_stride = g.grp_base = g.grp_operand = 0;
-    g.scale_a = g.scale_b = nullptr;
     if (row_group_operand) {
         if (row_group_operand < 1 || row_group_operand > 3 || row_group <= 0 || row_group % 128 || row_group_stride < row_group || row_group_base < 0) return OMR_ERR_ARG;
         if ((row_group_operand == 2 && !transB) || (row_group_operand == 1 && transB)) return OMR_ERR_ARG;
@@ -460,28 +448,20 @@ extern "C" int omr_gemm(int dtype, int c_dtype, int transA, int transB, int M, i
     }
     g.drop_thresh = OMR_DROP_THRESH16(drop_p); g.drop_scale = 1.f / (1.f - drop_p); g.drop_seed = drop_seed;
     if (colsum_a && !transA) return OMR_ERR_ARG;
-    const int bk = dtype == OMR_BF16 ? 64 : 32;
-    int len = cdiv(cdiv(K, split_k), bk) * bk;
-    g.ksplit_len = len;
-    int splits = cdiv(K, len);
+    const GemmPlan plan = gemm_plan(M, N, K, dtype == OMR_BF16 ? 64 : 32, split_k);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == OMR_BF16 && c_dtype == OMR_BF16 && !transA && !transB && !relu && !accumulate && splits == 1 && !colsum_a && drop_p == 0.f &&
-        !(lda % 8) && !(ldb % 8)) {
-        // tall-and-wide output with a short reduction (the all-layer K|V projection of the memory): panel kernel, gemm_panel.hip
-        const int rc = omr_gemm_panel_bf16(g, s);
-        if (rc != OMR_ERR_UNSUPPORTED) return rc;
-    }
-    if (dtype == OMR_BF16 && c_dtype == OMR_BF16 && !transA && transB && splits == 1) {
-        // tall output of 256 columns with a long reduction (the data gradient of the all-layer K|V projection): DMA-fed kernel, gemm_tall.hip
-        const int rc = omr_gemm_tall_bf16(g, s);
-        if (rc != OMR_ERR_UNSUPPORTED) return rc;
-    }
+    // The specialised routes, each asked in turn (GemmCall, gemm_args.h): the panel kernel (tall-and-wide output, short reduction),
+    // the DMA-fed tall kernel (256 columns, long reduction); what neither takes is the tile kernel's.
+    const GemmCall call = {dtype, c_dtype, transA, transB, plan.splits, drop_p};
+    int rc = omr_gemm_panel_bf16(call, g, s);
+    if (rc == OMR_ERR_UNSUPPORTED) rc = omr_gemm_tall_bf16(call, g, s);
+    if (rc != OMR_ERR_UNSUPPORTED) return rc;
     if (dtype == OMR_BF16) {
-        if (c_dtype == OMR_BF16) return launch<bf16, bf16>(g, transA, transB, splits, s);
-        return launch<bf16, float>(g, transA, transB, splits, s);
+        if (c_dtype == OMR_BF16) return launch<bf16, bf16>(g, transA, transB, plan, s);
+        return launch<bf16, float>(g, transA, transB, plan, s);
     } else if (dtype == OMR_F32) {
         if (c_dtype != OMR_F32) return OMR_ERR_UNSUPPORTED;
-        return launch<float, float>(g, transA, transB, splits, s);
+        return launch<float, float>(g, transA, transB, plan, s);
     }
     return OMR_ERR_UNSUPPORTED;
 }
@@ -508,19 +488,14 @@ extern "C" int omr_linear_wgrad_grouped(int dtype, int nprob, const omr_dw_probl
             DwProb& d = grp.p[i];
             d.A = q.dy; d.B = q.x; d.C = q.dw; d.colsum = q.db;
             d.M = q.n_out; d.N = q.n_in; d.K = q.rows; d.lda = (int)q.ld_dy; d.ldb = (int)q.ld_x; d.ldc = (int)q.ld_dw;
-            d.mt = cdiv(d.M, BM); d.nt = cdiv(d.N, BN);
             long want = (2048L + tiles_total - 1) / tiles_total;            // splits so that the call totals ~2048 workgroups
             long maxs = (q.rows + 511) / 512;
             if (want > maxs) want = maxs;
             if (want < 1) want = 1;
-            int len = cdiv(cdiv(d.K, (int)want), bk) * bk;
-            d.ksplit_len = len;
-            const int splits = cdiv(d.K, len);
-            d.total = d.nt * d.mt * splits;
-            d.chunk = splits > 1 ? d.nt * d.mt : d.nt;
-            const int nchunks = d.total / d.chunk;
+            const GemmPlan plan = gemm_plan(d.M, d.N, d.K, bk, (int)want);
+            put_plan(d, plan);
             d.block0 = block0;
-            block0 += cdiv(nchunks, 8) * 8 * d.chunk;
+            block0 += plan.blocks;
             d.grp = q.row_group; d.grp_stride = q.row_group_stride; d.grp_base = q.row_group_base; d.pad = 0;
         }
         if (dtype == OMR_BF16) hipLaunchKernelGGL((gemm_dw_grouped_kernel<bf16>), dim3((unsigned)block0), dim3(256), 0, s, grp);
@@ -568,12 +543,10 @@ extern "C" int omr_gemm_fp8(int c_dtype, int M, int N, int K, const unsigned cha
     if (lda % 16 || ldb % 16 || ((uintptr_t)A8 & 15) || ((uintptr_t)W8 & 15)) return OMR_ERR_ARG;      // 16-byte aligned rows
     GemmArgs g;
     g.A = A8; g.B = W8; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.relu = relu; g.accum = 0; g.atomic = 0; g.colsum_a = nullptr; g.ksplit_len = cdiv(K, 128) * 128;
-    g.drop_thresh = 0; g.drop_scale = 1.f; g.drop_seed = 0;
-    g.grp = g.grp_stride = g.grp_base = g.grp_operand = 0;
-    g.scale_a = scale_a; g.scale_b = scale_w;
+    g.relu = relu; g.scale_a = scale_a; g.scale_b = scale_w;
+    const GemmPlan plan = gemm_plan(M, N, K, GemmCfg<fp8>::BK, 1);      // one split of whole 128-wide k-tiles
     hipStream_t s = (hipStream_t)stream;
-    if (c_dtype == OMR_BF16) return launch<fp8, bf16>(g, 0, 0, 1, s);
-    if (c_dtype == OMR_F32) return launch<fp8, float>(g, 0, 0, 1, s);
+    if (c_dtype == OMR_BF16) return launch<fp8, bf16>(g, 0, 0, plan, s);
+    if (c_dtype == OMR_F32) return launch<fp8, float>(g, 0, 0, plan, s);
     return OMR_ERR_UNSUPPORTED;
 }

@@ -18,17 +18,12 @@
 #include "omr_common.h"
 #include "omr_hip.h"
 
-#include "gemm_args.h"
+#include "gemm_steps.h"
 #include "launch_setup.h"
 
 namespace {
 
 constexpr int PM = 256, PN = 64;
-typedef __attribute__((ext_vector_type(4))) unsigned short us4;
-
-__device__ __forceinline__ long pgrp_delta(const GemmArgs& g, int n) {
-    return g.grp_operand == 1 ? (long)(n / g.grp) * (g.grp_stride - g.grp) + g.grp_base : 0;
-}
 
 __device__ float g_zero_bias[4096];      // stands in for a missing bias: the per-tile bias load stays unconditional (see fetch)
 
@@ -72,7 +67,7 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_kernel(GemmArgs g) {
     for (int i = 0; i < PM * PN / 8 / 512; ++i) { const int c = tid + i * 512; coff[i] = (unsigned)((c >> 3) * (int)g.ldc + (c & 7) * 8); }
     auto fetch = [&](int nt) {
         const int n0 = nt * PN;
-        const long dn = pgrp_delta(g, n0);
+        const long dn = grp_delta(g, 1, n0);
         const bf16* wt = W + (n0 + dn) * g.ldb;
 #pragma unroll
         for (int i = 0; i < NLD; ++i) wreg[i] = *reinterpret_cast<const bf16x8*>(wt + woff[i]);
@@ -93,10 +88,7 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_kernel(GemmArgs g) {
     for (int nt = 0; nt < ntiles; ++nt) {
         const int cur = nt & 1;
         f32x16 acc[2];
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rb][r] = 0.f;
+        acc_clear(acc);
         const bf16* brow = Bs + (cur * PN + wn * 32 + (lane & 31)) * PB + hh * 8;
         // W fragments in groups of 8 LDS reads ahead of their 16 MFMAs (the next group's reads ride under this group's MFMAs)
         constexpr int GRP = NKS < 8 ? NKS : 8;
@@ -121,10 +113,7 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_kernel(GemmArgs g) {
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
                 const f32x4 b4 = *reinterpret_cast<const f32x4*>(&bias_s[cur * PN + wn * 32 + 8 * gq + 4 * hh]);
-                bf16x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (bf16)(acc[rb][4 * gq + e] + b4[e]);
-                *reinterpret_cast<bf16x4*>(crow + 8 * gq) = o;
+                *reinterpret_cast<bf16x4*>(crow + 8 * gq) = pack_ct4(acc[rb], gq, [&](float v, int e) { return v + b4[e]; });
             }
         }
         if (nt + 1 < ntiles) commit(cur ^ 1);
@@ -151,25 +140,24 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_kernel(GemmArgs g) {
     }
 }
 
+template <int NKS> int launch_panel(const GemmArgs& g, hipStream_t s) {
+    constexpr size_t shm = (2 * PN * (NKS * 16 + 8) + 2 * PM * (PN + 8)) * sizeof(bf16) + 2 * PN * sizeof(float);      // Bs, Cs, bias_s of the kernel
+    static std::atomic<int> ready{0};
+    if (!omr_launch_setup(ready, (const void*)gemm_panel_kernel<NKS>, shm, true)) return OMR_ERR_LAUNCH;
+    hipLaunchKernelGGL((gemm_panel_kernel<NKS>), dim3((unsigned)cdiv(g.M, PM)), dim3(512), shm, s, g);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
 }  // namespace
 
-// Takes the shapes it is built for (see the dispatch in omr_gemm); OMR_ERR_UNSUPPORTED otherwise.
-int omr_gemm_panel_bf16(const GemmArgs& g, hipStream_t s) {
+// The whole acceptance condition: a plain bf16 NT product (+ bias), tall and wide with a short reduction (the all-layer K|V projection
+// of the memory).  OMR_ERR_UNSUPPORTED = "not my shape": the caller asks the next route.
+int omr_gemm_panel_bf16(const GemmCall& call, const GemmArgs& g, hipStream_t s) {
+    if (!(call.dtype == OMR_BF16 && call.c_dtype == OMR_BF16 && !call.trans_a && !call.trans_b && !g.relu && !g.accum && call.splits == 1 &&
+          !g.colsum_a && call.drop_p == 0.f && !(g.lda % 8) && !(g.ldb % 8))) return OMR_ERR_UNSUPPORTED;
     if (g.K != 128 && g.K != 256) return OMR_ERR_UNSUPPORTED;
     if (g.N % PN || g.M < 200 * PM || g.N < 8 * PN || g.ldc % 8 || ((uintptr_t)g.C & 15)) return OMR_ERR_UNSUPPORTED;      // at least ~one panel per CU
     if (g.grp_operand != 0 && g.grp_operand != 1) return OMR_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)cdiv(g.M, PM)), block(512);
-    if (g.K == 256) {
-        constexpr size_t shm = (2 * PN * (256 + 8) + 2 * PM * (PN + 8)) * sizeof(bf16) + 2 * PN * sizeof(float);
-        static std::atomic<int> ready{0};
-        if (!omr_launch_setup(ready, (const void*)gemm_panel_kernel<16>, shm, true)) return OMR_ERR_LAUNCH;
-        hipLaunchKernelGGL((gemm_panel_kernel<16>), grid, block, shm, s, g);
-    } else {
-        constexpr size_t shm = (2 * PN * (128 + 8) + 2 * PM * (PN + 8)) * sizeof(bf16) + 2 * PN * sizeof(float);
-        static std::atomic<int> ready{0};
-        if (!omr_launch_setup(ready, (const void*)gemm_panel_kernel<8>, shm, true)) return OMR_ERR_LAUNCH;
-        hipLaunchKernelGGL((gemm_panel_kernel<8>), grid, block, shm, s, g);
-    }
-    OMR_CHECK_LAUNCH();
-    return OMR_OK;
+    return g.K == 256 ? launch_panel<16>(g, s) : launch_panel<8>(g, s);
 }

@@ -21,13 +21,12 @@
 // per k-tile (a tile never straddles a group: grp % 64 == 0, host-checked).
 #include "omr_common.h"
 #include "omr_hip.h"
-#include "gemm_args.h"
+#include "gemm_steps.h"
 #include "dma_common.h"
 #include "launch_setup.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4 LdsV4;
 constexpr int TM = 256, TN = 256;
 #ifndef OMR_TALL_BK
 #define OMR_TALL_BK 64
@@ -84,7 +83,9 @@ __global__ __launch_bounds__(1024) void gemm_tall_kernel(GemmArgs g) {
         auto issue = [&](int kt) {
             const unsigned st = lds0 + (kt % NST) * STAGE;
             const int k0 = kt * BK;
-            const long krow = g.grp_operand == 2 ? (long)(k0 / g.grp) * g.grp_stride + g.grp_base + k0 % g.grp : k0;
+            // the group's offset at the k-tile's first row: with k0 a multiple of BK and grp % BK == 0 (acceptance condition below)
+            // the tile lies inside one group, and this is (k0 / grp) * grp_stride + grp_base + k0 % grp
+            const long krow = k0 + grp_delta(g, 2, k0);
             const bf16* bt = B + krow * g.ldb;
 #pragma unroll
             for (int u = 0; u < A_COPIES; ++u) dma16(a_src[u] + k0, st + (A_COPIES * wave + u) * 1024);
@@ -94,12 +95,7 @@ __global__ __launch_bounds__(1024) void gemm_tall_kernel(GemmArgs g) {
         constexpr int PER_TILE = A_COPIES + B_COPIES;
 
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        acc_clear(acc);
 
 #pragma unroll
         for (int p = 0; p < NST - 1; ++p)
@@ -117,13 +113,7 @@ __global__ __launch_bounds__(1024) void gemm_tall_kernel(GemmArgs g) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const bf16x8*>(st + a_off[ks] + i * 32 * ROWB);
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const unsigned char* p = st + b_off[j] + ks * 16 * 512;
-                    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LdsV4*)p);
-                    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LdsV4*)(p + 4 * 512));
-                    const bf16x8 f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    bfr[j] = f;
-                }
+                for (int j = 0; j < 2; ++j) bfr[j] = tr_frag_bf16(st + b_off[j] + ks * 16 * 512, 4 * 512);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -137,12 +127,7 @@ __global__ __launch_bounds__(1024) void gemm_tall_kernel(GemmArgs g) {
             for (int j = 0; j < 2; ++j) {
                 unsigned char* row = smem + (wm * 64 + i * 32 + (lane & 31)) * CP + (wn * 64 + j * 32 + 4 * hh) * 2;
 #pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    bf16x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = (bf16)acc[i][j][4 * gq + e];
-                    *reinterpret_cast<bf16x4*>(row + gq * 16) = o;
-                }
+                for (int gq = 0; gq < 4; ++gq) *reinterpret_cast<bf16x4*>(row + gq * 16) = pack_ct4(acc[i][j], gq);
             }
         lds_barrier();
 #pragma unroll
@@ -156,8 +141,10 @@ __global__ __launch_bounds__(1024) void gemm_tall_kernel(GemmArgs g) {
 
 }  // namespace
 
-// OMR_ERR_UNSUPPORTED = "not my shape": the caller falls through to the tile kernel.
-int omr_gemm_tall_bf16(const GemmArgs& g0, hipStream_t s) {
+// The whole acceptance condition: a tall bf16 output of 256 columns with a long reduction over a reduction-major B (the data gradient of
+// the all-layer K|V projection).  OMR_ERR_UNSUPPORTED = "not my shape": the caller falls through to the tile kernel.
+int omr_gemm_tall_bf16(const GemmCall& call, const GemmArgs& g0, hipStream_t s) {
+    if (!(call.dtype == OMR_BF16 && call.c_dtype == OMR_BF16 && !call.trans_a && call.trans_b && call.splits == 1)) return OMR_ERR_UNSUPPORTED;
     GemmArgs g = g0;
     if (g.N != TN || g.K % BK || g.K < BK || g.bias || g.relu || g.accum || g.atomic || g.colsum_a || g.drop_thresh) return OMR_ERR_UNSUPPORTED;
     if (g.lda % 8 || g.ldb % 8 || g.ldc % 8 || ((uintptr_t)g.A & 15) || ((uintptr_t)g.B & 15) || ((uintptr_t)g.C & 15)) return OMR_ERR_UNSUPPORTED;

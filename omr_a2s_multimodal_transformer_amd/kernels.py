@@ -22,30 +22,34 @@ def _rows2d(t: Tensor) -> Tuple[int, int, int]:
     return t.shape[0], t.shape[1], t.stride(0)
 
 
+def _omr_gemm(a: Tensor, b: Tensor, out: Tensor, M: int, N: int, K: int, trans_a, trans_b, bias, relu, accumulate, split_k, colsum_a, drop, group) -> Tensor:
+    """The one spelling of the omr_gemm call and of the checks both wrappers share; `group` as gemm_row_groups takes it ((0, 0, 0, 0): off)."""
+    require_cuda(a, b, bias, out, colsum_a)
+    assert a.dtype == b.dtype
+    lib().call("omr_gemm", dtype_code(a.dtype), dtype_code(out.dtype), int(trans_a), int(trans_b), M, N, K, ptr(a), a.stride(0), ptr(b), b.stride(0),
+               ptr(out), out.stride(0), ptr(bias), int(relu), int(accumulate), split_k, ptr(colsum_a), float(drop[0]) if drop else 0.0,
+               (int(drop[1]) & (2**64 - 1)) if drop else 0, *group, cur_stream())
+    return out
+
+
 def gemm(a: Tensor, b: Tensor, *, trans_a: bool = False, trans_b: bool = False, bias: Optional[Tensor] = None, relu: bool = False,
          out: Optional[Tensor] = None, out_dtype: Optional[torch.dtype] = None, accumulate: bool = False, split_k: int = 1,
          colsum_a: Optional[Tensor] = None, drop: Optional[Tuple[float, int]] = None) -> Tensor:
     """C[M,N] (+)= act(opA(a) @ opB(b)^T + bias).  a is [M,K] ([K,M] if trans_a); b is [N,K] ([K,N] if trans_b)."""
-    require_cuda(a, b, bias, out)
-    assert a.dtype == b.dtype
-    ar, ac, lda = _rows2d(a)
-    br, bc, ldb = _rows2d(b)
+    ar, ac, _ = _rows2d(a)
+    br, bc, _ = _rows2d(b)
     M, K = (ac, ar) if trans_a else (ar, ac)
     N, Kb = (bc, br) if trans_b else (br, bc)
     assert K == Kb, f"gemm inner dims differ: {K} vs {Kb}"
     if out is None:
         out = torch.empty((M, N), dtype=out_dtype or a.dtype, device=a.device)
         assert not accumulate and split_k == 1, "accumulating gemm needs an initialised `out`"
-    cr, cc, ldc = _rows2d(out)
-    assert (cr, cc) == (M, N), f"gemm out shape {tuple(out.shape)} != {(M, N)}"
+    assert _rows2d(out)[:2] == (M, N), f"gemm out shape {tuple(out.shape)} != {(M, N)}"
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
     if colsum_a is not None:
         assert trans_a and colsum_a.dtype == torch.float32 and colsum_a.numel() == M and colsum_a.is_contiguous()
-    lib().call("omr_gemm", dtype_code(a.dtype), dtype_code(out.dtype), int(trans_a), int(trans_b), M, N, K, ptr(a), lda, ptr(b), ldb,
-               ptr(out), ldc, ptr(bias), int(relu), int(accumulate), split_k, ptr(colsum_a), float(drop[0]) if drop else 0.0,
-               (int(drop[1]) & (2**64 - 1)) if drop else 0, 0, 0, 0, 0, cur_stream())
-    return out
+    return _omr_gemm(a, b, out, M, N, K, trans_a, trans_b, bias, relu, accumulate, split_k, colsum_a, drop, (0, 0, 0, 0))
 
 
 def gemm_row_groups(a: Tensor, b: Tensor, out: Tensor, M: int, N: int, Kd: int, *, trans_a: bool = False, trans_b: bool = False,
@@ -54,8 +58,7 @@ def gemm_row_groups(a: Tensor, b: Tensor, out: Tensor, M: int, N: int, Kd: int, 
     """omr_gemm over a row-group view of the weight-side operand (include/omr_hip.h): `group` = (rows per group, physical
     group stride, first row inside a group, operand 1|2|3).  The grouped tensor (b, or out/colsum_a/bias) is the PHYSICAL
     2-D block that contains every group; M, N, Kd are the logical GEMM sizes, so only strides are taken from the tensors."""
-    require_cuda(a, b, bias, out, colsum_a)
-    assert a.dtype == b.dtype and a.dim() == b.dim() == out.dim() == 2 and a.stride(1) == b.stride(1) == out.stride(1) == 1
+    assert a.dim() == b.dim() == out.dim() == 2 and a.stride(1) == b.stride(1) == out.stride(1) == 1
     grp, stride, base, operand = group
     ngroups = {1: N, 2: Kd, 3: M}[operand] // grp
     phys_rows = (ngroups - 1) * stride + base + grp
@@ -64,9 +67,7 @@ def gemm_row_groups(a: Tensor, b: Tensor, out: Tensor, M: int, N: int, Kd: int, 
     for vec, need in ((bias, operand == 1), (colsum_a, operand == 3)):
         if vec is not None:
             assert vec.dtype == torch.float32 and vec.is_contiguous() and vec.numel() >= (phys_rows if need else 0)
-    lib().call("omr_gemm", dtype_code(a.dtype), dtype_code(out.dtype), int(trans_a), int(trans_b), M, N, Kd, ptr(a), a.stride(0), ptr(b), b.stride(0),
-               ptr(out), out.stride(0), ptr(bias), 0, int(accumulate), split_k, ptr(colsum_a), 0.0, 0, grp, stride, base, operand, cur_stream())
-    return out
+    return _omr_gemm(a, b, out, M, N, Kd, trans_a, trans_b, bias, False, accumulate, split_k, colsum_a, None, group)
 
 
 class _DwProblem(ctypes.Structure):
