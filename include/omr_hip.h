@@ -586,6 +586,70 @@ int omr_weighted_beam_select(const float* logits_a, long lda, const float* logit
 int omr_weighted_beam_decode_steps(const omr_decode_desc* desc_a, const int* mem_len_a, const omr_decode_desc* desc_b, const int* mem_len_b,
                                    const omr_beam_desc* beam_desc, void* self_kv2_b, float alpha, int t0, int n_steps, void* stream);
 
+/* ---- speculative greedy decoding ----------------------------------------------------------------------------------------- */
+/* An extension of the greedy loop of Transformer.validation_step / get_pred_seq_and_pred_prob_seq (src/transformer/model.py:171-199,
+ * 226-262), which runs one position per pass: a cheap DRAFT model with the same vocabulary proposes k tokens, ONE pass of the
+ * target model runs the R = k + 1 positions they would occupy, and the longest prefix of proposals the target itself would have
+ * picked is kept.  Tokens and top-1 values are those of the one-position loop, to the bit.
+ *
+ * A GROUPED position: rows = B * R, row m is position pos[m / R] + m % R of slot m / R (desc->B = B slots: the caches hold B
+ * slots, the scratch B * R rows).  Row path only (omr_decode_steps_rows' descriptors; any other: OMR_ERR_UNSUPPORTED before any
+ * pointer is read).  Per layer the q|k|v linear of all rows writes row m's K|V into cache row pos + m % R of slot m / R and
+ * completes before the attention launch, in which row m attends over cache rows [lo_m, pos + m % R] of its slot -- those of the
+ * rows before it in its group included -- and over the slot's memory keys.  Nothing past a row's own position is read. */
+#define OMR_MAX_VERIFY_ROWS 32
+/* Bytes of scratch a grouped position of R rows per slot wants (2 <= R <= OMR_MAX_VERIFY_ROWS; desc->ws is not looked at). */
+long omr_decode_group_workspace_bytes(const omr_decode_desc* desc, int R);
+/* R consecutive positions of every slot in one pass (the loop body of model.py:182-193,247-260, R times).  pos: device int32 [B];
+ * t_max: its largest entry, given by the host.  tokens: device int64 [B][R], column 0 the token slot b feeds to pos[b], columns
+ * 1..R-1 the proposed continuations.  out_tokens [B][R] / out_top1 [B][R] (nullable): the greedy pick of every row and its fp32
+ * logit -- out_tokens[b][r] is what omr_decode_steps_rows picks at position pos[b] + r after the prefix tokens[b][0..r].  ws /
+ * ws_bytes: omr_decode_group_workspace_bytes(desc, R) bytes of device scratch (desc->ws is not used).  Nothing is advanced;
+ * self_kv rows pos[b] .. pos[b] + R - 1 of every slot are overwritten.  Refused before the first launch: R outside
+ * 2..OMR_MAX_VERIFY_ROWS, t_max < 0, t_max + R > max_len, a NULL pos / tokens / out_tokens / ws, too small a ws, and (with
+ * OMR_ERR_UNSUPPORTED) desc->S <= 64 -- the rows of a slot share its memory K|V, which only the key-split kernel does; on the device
+ * positions are clamped into the cache as in omr_decode_steps_rows. */
+int omr_decode_verify_rows(const omr_decode_desc* desc, const int* mem_len, const int* pos, int t_max, int R, const long* tokens,
+                           long* out_tokens, float* out_top1, void* ws, long ws_bytes, void* stream);
+/* The state of a speculative decode of B slots with k proposals per cycle, all device memory carved out of ONE block `state` of
+ * omr_spec_workspace_bytes bytes, so that one copy brings the results to the host (the pattern of omr_beam_desc):
+ *   pos int32 [B]          the next position of each slot = the tokens it has produced (>= 1: position 0 is run by the caller)
+ *   out_len int32 [B]      tokens in the slot's output run
+ *   done int32 [B]         1: the slot took <eos> or filled its run; frozen from then on
+ *   accepted int32 [B]     j of the last cycle
+ *   totals int64 [2]       proposals made / proposals accepted, over all cycles and live slots
+ *   first / prev int64 [B] the token the slot feeds to pos[b] / fed to pos[b] - 1
+ *   tokens / picks int64 [B][k+1], top1 fp32 [B][k+1]      omr_decode_verify_rows' tokens, out_tokens and out_top1
+ *   dpicks int64 [k+1][B]  the draft's picks of the cycle
+ *   out_tokens int64 [B][max_out], out_top1 fp32 [B][max_out]      the output runs
+ * ws_t / ws_t_bytes: omr_decode_group_workspace_bytes(target, k + 1) bytes of scratch, not part of the block.  t_max: the host's
+ * upper bound of pos[] when omr_spec_decode_cycles is called. */
+typedef struct omr_spec_desc {
+    int B, k, eos, max_out, t_max, pad_;
+    void* state; long state_bytes;
+    int* pos; int* out_len; int* done; int* accepted; long* totals; long* first; long* prev;
+    long* tokens; long* picks; float* top1; long* dpicks; long* out_tokens; float* out_top1;
+    void* ws_t; long ws_t_bytes;
+} omr_spec_desc;
+/* Bytes of the state block for desc->{B, k, max_out}; also points the thirteen state fields into desc->state (NULL: offsets). */
+long omr_spec_workspace_bytes(omr_spec_desc* desc);
+/* The acceptance of ONE cycle for all slots in one launch (no counterpart in the reference's loop, model.py:182-193, which keeps
+ * every token it computes): per live slot j = the number of leading proposals with tokens[b][i] == picks[b][i - 1]; picks[b][0..j]
+ * and their top-1 values are appended to the slot's run, cut after the first <eos> and at max_out (either sets done); pos[b] and
+ * out_len[b] grow by the tokens appended, first[b] becomes the last of them and prev[b] the one before it; accepted[b] = j, and
+ * totals grow by (k, j).  Plain loads and stores, one workgroup, no atomics. */
+int omr_spec_accept(const omr_spec_desc* spec, void* stream);
+/* n_cycles cycles without a host round trip (an extension of model.py:171-199; all positions come from spec->pos).  Per cycle: the
+ * DRAFT runs k + 1 single positions pos - 1 .. pos + k - 1 of every slot through omr_decode_steps_rows' path on its own caches --
+ * the first one feeds prev[b] and closes the gap a fully accepted cycle leaves (its last proposal was never consumed), the
+ * second feeds first[b], the others the draft's own previous pick --, one launch builds tokens[B][k+1], the TARGET runs
+ * omr_decode_verify_rows, then omr_spec_accept.  Both descriptors: B slots, the same V, the row path.  Refused before the first
+ * launch: k outside 1..OMR_MAX_VERIFY_ROWS - 1, n_cycles < 1, spec->t_max < 1, spec->t_max + n_cycles * (k + 1) beyond either
+ * model's max_len, NULL state fields, too small a block or ws_t, and (OMR_ERR_UNSUPPORTED) target->S <= 64, or draft->S <= 64 with
+ * mem_len_d. */
+int omr_spec_decode_cycles(const omr_decode_desc* target, const omr_decode_desc* draft, const int* mem_len_t, const int* mem_len_d,
+                           const omr_spec_desc* spec, int k, int n_cycles, void* stream);
+
 /* ---- grammar-constrained decoding -------------------------------------------------------------------------------------- */
 /* An extension: the reference picks over the whole vocabulary at every position (argmax in Transformer.validation_step,
  * src/transformer/model.py:182-193; the mixed argmax of src/multimodal/weighted_multimodal/test.py:50-61), so nothing keeps a

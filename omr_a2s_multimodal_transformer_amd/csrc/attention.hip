@@ -62,8 +62,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, const uint
     const T* V = (const T*)a.v + (long)bk * a.bsv + h * HD;
     int S = a.S;                                                // this row's key count (never past the padded S; <= 0: no keys)
     if constexpr (SPLITW) {
-        if (kv_len) S = min(kv_len[bk], a.S);
-        if (kv_start) { const long first = max(kv_start[bk], 0); K += first * a.ldk; V += first * a.ldv; }
+        const int bt = a.kv_row_tables ? b : bk;                // uniform: a grouped decode position keeps its tables per row
+        if (kv_len) S = min(kv_len[bt], a.S);
+        if (kv_start) { const long first = max(kv_start[bt], 0); K += first * a.ldk; V += first * a.ldv; }
     }
 
     const float sc2 = a.scale * LOG2E;
@@ -385,14 +386,15 @@ int attn_fwd_impl(int dtype, const void* q, const void* k, const void* v, void* 
                   long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim, int causal, int window,
                   const float* key_bias, const int* blk_lq, const int* blk_lkv, float dropout_p, unsigned long long seed,
                   const unsigned long long* drop_words, float* split_ws, long split_ws_floats, void* stream, int* nsplit_out = nullptr,
-                  const int* kv_len = nullptr, int kv_group = 1, const int* kv_start = nullptr, bool rows = false) {
+                  const int* kv_len = nullptr, int kv_group = 1, const int* kv_start = nullptr, bool rows = false, bool row_tables = false) {
     AttnArgs a = {};
     int rc = fill_common(a, B, H, T, S, head_dim, dropout_p, seed, causal, window, key_bias, blk_lq, blk_lkv, drop_words, true);
     if (rc) return rc;
     rc = fill_qkvo(a, dtype, q, k, v, o, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso);
     if (rc || ldo % 4) return OMR_ERR_ARG;
-    a.lse = lse; a.kv_group = kv_group;
+    a.lse = lse; a.kv_group = kv_group; a.kv_row_tables = row_tables;
     if (kv_group < 1 || B % kv_group) return OMR_ERR_ARG;
+    if (row_tables && !(rows && kv_len && kv_start)) return OMR_ERR_ARG;
     rc = plan_split(a, head_dim, split_ws, split_ws_floats, fwd_split_floats);
     if (rc) return rc;
     // per-row key counts exist only in the key-split decode kernel: a shape that would not take it is refused, not run unmasked
@@ -534,4 +536,15 @@ int attn_fwd_split_partials_rows(int dtype, const void* q, const void* k, const 
     if (T > 32 || !nsplit) return OMR_ERR_ARG;
     return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, nullptr, nullptr, nullptr, 0.f, 0,
                          nullptr, split_ws, split_ws_floats, stream, nsplit, kv_len, 1, kv_start, true);
+}
+
+/* attn_fwd_split_partials_rows for a grouped decode position (omr_common.h): the slot from b / group, the key range from row b.  A
+ * C++ symbol, not part of the C ABI */
+int attn_fwd_split_partials_group(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                                  long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                                  const int* kv_len, const int* kv_start, int group, float* split_ws, long split_ws_floats, int* nsplit,
+                                  void* stream) {
+    if (T > 32 || !nsplit || group < 1) return OMR_ERR_ARG;
+    return attn_fwd_impl(dtype, q, k, v, o, lse, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, B, H, T, S, head_dim, 0, -1, nullptr, nullptr, nullptr, 0.f, 0,
+                         nullptr, split_ws, split_ws_floats, stream, nsplit, kv_len, group, kv_start, true, true);
 }

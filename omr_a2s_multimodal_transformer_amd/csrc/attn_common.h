@@ -25,6 +25,8 @@ struct AttnArgs {
     // single-query-block forward split over the keys (decode): blockIdx.x = split, partials [B][H][nsplit][T][HD + 2] floats
     int nsplit, split_len; float* part;
     int kv_group;                                      // key-split forward: batch row b reads the K|V (and kv_len) of slot b / kv_group
+    int kv_row_tables;                                 // key-split forward: kv_len / kv_start are indexed by the batch row b itself, the
+                                                       // slot still by b / kv_group (a grouped decode position)
     // backward only
     const void* dout; long lddo, bsdo;
     const float* delta;                                // [B][H][T]

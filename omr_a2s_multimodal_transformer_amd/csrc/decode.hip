@@ -15,8 +15,8 @@
 
 namespace omr_dec {
 
-size_t carve(const omr_decode_desc& d, char* base, Ws* w) {
-    const size_t es = d.dtype == OMR_BF16 ? 2 : 4, B = (size_t)d.B;
+size_t carve(const omr_decode_desc& d, int rows, char* base, Ws* w) {
+    const size_t es = d.dtype == OMR_BF16 ? 2 : 4, B = (size_t)rows;
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
     char* x = take(B * d.d * es); char* x2 = take(B * d.d * es); char* q = take(B * d.d * es); char* o = take(B * d.d * es); char* proj = take(B * d.d * es);
@@ -24,7 +24,7 @@ size_t carve(const omr_decode_desc& d, char* base, Ws* w) {
     float* l32 = (float*)take(B * (size_t)d.ldv * 4); float* lse = (float*)take(B * (size_t)d.nhead * 4);
     float* mean = (float*)take(B * 4); float* rstd = (float*)take(B * 4);
     const int smax = d.S > d.max_len ? d.S : d.max_len;                // key-split partials of the longer of the two attentions
-    const long sf = omr_attn_split_workspace_floats(d.B, d.nhead, 1, smax, d.d / d.nhead);
+    const long sf = omr_attn_split_workspace_floats(rows, d.nhead, 1, smax, d.d / d.nhead);
     float* split = (float*)take((size_t)sf * 4);
     float* apart = (float*)take(2 * B * (size_t)((d.V + 15) / 16) * 4);      // greedy pick: the head kernel's per-workgroup candidates
     const size_t kmax = (size_t)(d.d > d.ff ? d.d : d.ff);
@@ -35,11 +35,16 @@ size_t carve(const omr_decode_desc& d, char* base, Ws* w) {
     return off;
 }
 
-int check_model(const omr_decode_desc& d) {
+int check_desc(const omr_decode_desc& d) {
     if (d.B <= 0 || d.L <= 0 || d.d <= 0 || d.d % d.nhead || d.V <= 0 || d.ldv < d.V || d.ldv % 8) return OMR_ERR_ARG;
-    if (!d.emb || !d.pe || !d.layer_w || !d.head_w || !d.self_kv || !d.cross_kv || !d.ws) return OMR_ERR_ARG;
-    if (d.ws_bytes < (long)carve(d, nullptr, nullptr)) return OMR_ERR_ARG;
+    if (!d.emb || !d.pe || !d.layer_w || !d.head_w || !d.self_kv || !d.cross_kv) return OMR_ERR_ARG;
     if (d.fp8 && (!d.layer_w8 || !d.layer_s8 || !d.head_w8 || !d.head_s8 || d.d % 16 || d.ff % 16)) return OMR_ERR_ARG;
+    return OMR_OK;
+}
+
+int check_model(const omr_decode_desc& d) {
+    OMR_TRY(check_desc(d));
+    if (!d.ws || d.ws_bytes < (long)carve(d, d.B, nullptr, nullptr)) return OMR_ERR_ARG;
     return OMR_OK;
 }
 
@@ -50,13 +55,19 @@ int check_steps(int t0, int n_steps, int max_len) {
 }
 
 Model make_model(const omr_decode_desc* d, const int* mem_len, int kv_group) {
-    Model m = {d, Ws{}, mem_len, kv_group};
-    carve(*d, (char*)d->ws, &m.w);
+    Model m = {d, Ws{}, mem_len, kv_group, d->B, 1};
+    carve(*d, d->B, (char*)d->ws, &m.w);
+    return m;
+}
+
+Model make_group_model(const omr_decode_desc* d, const int* mem_len, int group, void* ws) {
+    Model m = {d, Ws{}, mem_len, group, d->B * group, group};      // the rows of a slot share its memory K|V: kv_group = group
+    carve(*d, m.rows, (char*)ws, &m.w);
     return m;
 }
 
 int copy_logits(const Model& m, float* dst, const float* logits32, void* stream) {
-    const size_t bytes = (size_t)m.d->B * m.d->ldv * sizeof(float);
+    const size_t bytes = (size_t)m.rows * m.d->ldv * sizeof(float);
     return hipMemcpyAsync(dst, logits32, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? OMR_OK : OMR_ERR_LAUNCH;
 }
 
@@ -115,7 +126,7 @@ typedef omr_decode_linear_args Lin;
 Lin shared_fields(const Model& m, const Position& p, const long* tok_in) {
     const omr_decode_desc& d = *m.d;
     Lin a = {};
-    a.dtype = d.dtype; a.M = d.B; a.H = d.nhead; a.hd = d.d / d.nhead; a.vocab = d.V; a.eps = 1e-5f; a.ld32 = d.ldv;
+    a.dtype = d.dtype; a.M = m.rows; a.H = d.nhead; a.hd = d.d / d.nhead; a.vocab = d.V; a.eps = 1e-5f; a.ld32 = d.ldv;
     a.tokens = tok_in; a.emb = d.emb; a.pe_row = d.pe + (size_t)p.t * d.d;
     return a;
 }
@@ -155,10 +166,11 @@ Lin merged_linear(const Lin& shared, const Matrix& mx, const Ws& w, int ns) {
 int row_position(const Model& m, const Position& p, const long* tok_in, Pick pick, void* stream) {
     const omr_decode_desc& d = *m.d;
     const Ws& w = m.w;
-    const int dt = d.dtype, B = d.B, dm = d.d, hd = dm / d.nhead, t = p.t, lo = band_start(d, t);
+    const int dt = d.dtype, B = m.rows, dm = d.d, hd = dm / d.nhead, t = p.t, lo = band_start(d, t);
     const size_t es = dt == OMR_BF16 ? 2 : 4;
     const long kv_ld = (long)d.max_len * 2 * dm;
     const Lin shared = shared_fields(m, p, tok_in);
+    if (m.group > 1 && !p.row_pos) return OMR_ERR_ARG;                           // a grouped position has its rows' tables
     // the residual stream alternates between two buffers because the workgroup that stores a freshly normalised row runs beside
     // workgroups still reading the previous one.  xa: the stream entering the sub-layer
     char* xa = w.x; char* xb = w.x2;
@@ -172,14 +184,18 @@ int row_position(const Model& m, const Position& p, const long* tok_in, Pick pic
         qkv.out0 = w.q; qkv.ld0 = dm; qkv.n0 = dm; qkv.ld1 = kv_ld;
         if (p.row_pos) {                    // per-row positions: the kernel adds each row's own positional and cache row
             qkv.pe_row = d.pe; qkv.out1 = cache_l;
-            OMR_TRY(decode_linear_impl(qkv, p.row_pos, 2L * dm, stream));
+            OMR_TRY(decode_linear_impl(qkv, p.row_pos, 2L * dm, stream, m.group));
         } else {
             qkv.out1 = cache_l + (size_t)t * 2 * dm * es;
             OMR_TRY(decode_linear_impl(qkv, nullptr, 0, stream));
         }
         std::swap(xa, xb);
         int ns = 1;
-        if (p.row_pos) {        // row b over its own keys [lo_b, t_b]; the split plan is that of the furthest row's count
+        if (m.group > 1) {      // row b over keys [lo_b, t_b] of slot b / group: those of the rows before it in its group were written
+                                // by the launch above
+            OMR_TRY(attn_fwd_split_partials_group(dt, w.q, cache_l, cache_l + (size_t)dm * es, w.o, w.lse, dm, 2 * dm, 2 * dm, dm, dm, kv_ld, kv_ld, dm, B,
+                                              d.nhead, 1, t + 1 - lo, hd, p.kv_count, p.kv_start, m.group, w.split, w.split_floats, &ns, stream));
+        } else if (p.row_pos) { // row b over its own keys [lo_b, t_b]; the split plan is that of the furthest row's count
             OMR_TRY(attn_fwd_split_partials_rows(dt, w.q, cache_l, cache_l + (size_t)dm * es, w.o, w.lse, dm, 2 * dm, 2 * dm, dm, dm, kv_ld, kv_ld, dm, B,
                                              d.nhead, 1, t + 1 - lo, hd, p.kv_count, p.kv_start, w.split, w.split_floats, &ns, stream));
         } else {
@@ -295,7 +311,35 @@ int omr_dec::run_position(const Model& m, const Position& p, const long* tok_in,
 
 extern "C" long omr_decode_workspace_bytes(const omr_decode_desc* d) {
     if (!d || d->B <= 0 || d->d <= 0 || d->ff <= 0 || d->ldv < d->V) return OMR_ERR_ARG;
-    return (long)carve(*d, nullptr, nullptr);
+    return (long)carve(*d, d->B, nullptr, nullptr);
+}
+
+extern "C" long omr_decode_group_workspace_bytes(const omr_decode_desc* d, int R) {
+    if (!d || d->B <= 0 || d->d <= 0 || d->ff <= 0 || d->ldv < d->V || R < 2 || R > OMR_MAX_VERIFY_ROWS) return OMR_ERR_ARG;
+    return (long)carve(*d, d->B * R, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// A grouped position: R consecutive positions of every slot as the rows of ONE pass of the row path (row_position with a group
+// model).  Row b * R + r feeds tokens[b][r] to position pos[b] + r; within a layer the q|k|v launch of all rows completes before
+// the attention launch, so row r reads the K|V rows r' < r of its group wrote.  Nothing is advanced.
+int omr_dec::verify_rows(const omr_decode_desc* dp, const int* mem_len, const int* pos, int t_max, int R, const long* tokens, long* out_tokens,
+                         float* out_top1, void* ws, long ws_bytes, void* stream) {
+    if (!dp) return OMR_ERR_ARG;
+    if (!takes_row_kernel(*dp)) return OMR_ERR_UNSUPPORTED;
+    if (!pos || !tokens || !out_tokens || !ws) return OMR_ERR_ARG;
+    if (R < 2 || R > OMR_MAX_VERIFY_ROWS || t_max < 0 || t_max + R > dp->max_len) return OMR_ERR_ARG;
+    if (dp->S <= 64) return OMR_ERR_UNSUPPORTED;          // the rows of a slot share its memory K|V: the key-split kernel only (S > 64)
+    OMR_TRY(check_desc(*dp));
+    if (ws_bytes < (long)carve(*dp, dp->B * R, nullptr, nullptr)) return OMR_ERR_ARG;
+    const Model m = make_group_model(dp, mem_len, R, ws);
+    const Position p = launch_group_tables(m, pos, t_max, stream);
+    return row_position(m, p, tokens, Pick{out_tokens, out_top1}, stream);
+}
+
+extern "C" int omr_decode_verify_rows(const omr_decode_desc* dp, const int* mem_len, const int* pos, int t_max, int R, const long* tokens,
+                                      long* out_tokens, float* out_top1, void* ws, long ws_bytes, void* stream) {
+    return verify_rows(dp, mem_len, pos, t_max, R, tokens, out_tokens, out_top1, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -46,10 +46,12 @@ __device__ __forceinline__ void w_unpack(const f32x4& c, float (&f)[4]) {
 
 // The kernel's argument block: the public omr_decode_linear_args (its layout is pinned) plus what a decode state with per-row
 // positions adds (ROWS): row m sits at position row_pos[m], so its positional row is pe_row + row_pos[m] * K and its out1 part
-// (the K|V projection's cache row) lands out1_pos_ld elements further per position.
-struct LinArgs { omr_decode_linear_args a; const int* row_pos; long out1_pos_ld; };
+// (the K|V projection's cache row) lands out1_pos_ld elements further per position.  GROUP (a grouped position, `group`
+// consecutive rows = consecutive positions of one slot; omr_decode_verify_rows): the out1 part of row m goes to the cache of slot
+// m / group, not of row m.
+struct LinArgs { omr_decode_linear_args a; const int* row_pos; long out1_pos_ld; int group; };
 
-template <typename T, bool W8, bool ROWS>
+template <typename T, bool W8, bool ROWS, bool GROUP>
 __global__ __launch_bounds__(256) void decode_linear_kernel(LinArgs la) {
     const omr_decode_linear_args& a = la.a;
     typedef typename Frag<T>::type F;
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(LinArgs la) {
                 const T o = from_f32<T>(v);
                 const long m = r0 + r;
                 if (n < a.n0) ((T*)a.out0)[m * a.ld0 + n] = o;
-                else ((T*)a.out1)[m * a.ld1 + (ROWS ? (long)la.row_pos[m] * la.out1_pos_ld : 0) + (n - a.n0)] = o;
+                else ((T*)a.out1)[(GROUP ? m / la.group : m) * a.ld1 + (ROWS ? (long)la.row_pos[m] * la.out1_pos_ld : 0) + (n - a.n0)] = o;
                 if (a.out32) a.out32[m * a.ld32 + n] = to_f32(o);
                 cand[r][nl] = to_f32(o);
             }
@@ -231,11 +233,12 @@ __global__ __launch_bounds__(64) void decode_pick_kernel(const float* __restrict
 // Per-row positions (omr_decode_steps_rows): ONE launch per host call turns pos[B] into the tables every kernel of position s
 // indexes at [s][b] -- the position pos[b] + off + s, the first visible key lo_b (banded causal mask, decoder.py:213-214) and
 // the key count.  A position is clamped into [0, max_len - n_steps]: whatever `pos` holds, no kernel leaves the caches.
+// grouped (omr_decode_verify_rows): the n_steps consecutive positions of slot b are ROWS of one position, entry [b][s], not steps [s][b].
 __global__ __launch_bounds__(256) void decode_rows_tables_kernel(const int* __restrict__ pos, int off, int B, int n_steps, int max_len, int window,
-                                                                 int* __restrict__ tpos, int* __restrict__ tstart, int* __restrict__ tcount) {
+                                                                 int grouped, int* __restrict__ tpos, int* __restrict__ tstart, int* __restrict__ tcount) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B * n_steps) return;
-    const int b = i % B, s = i / B;
+    const int b = grouped ? i / n_steps : i % B, s = grouped ? i % n_steps : i / B;
     const int t = min(max(pos[b] + off, 0), max_len - n_steps) + s;
     const int lo = (window > 0 && t - window > 0) ? t - window : 0;
     tpos[i] = t; tstart[i] = lo; tcount[i] = t + 1 - lo;
@@ -245,8 +248,8 @@ __global__ __launch_bounds__(256) void decode_rows_tables_kernel(const int* __re
 
 namespace omr_dec {
 
-// row_pos != NULL: the per-row-position form (LinArgs)
-int decode_linear_impl(const omr_decode_linear_args& a, const int* row_pos, long out1_pos_ld, void* stream) {
+// row_pos != NULL: the per-row-position form (LinArgs); group > 1 (with row_pos): the grouped form
+int decode_linear_impl(const omr_decode_linear_args& a, const int* row_pos, long out1_pos_ld, void* stream, int group) {
     const int vec = (a.dtype == OMR_BF16 || a.w8) ? 8 : 4;
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.K % vec || a.K > 2048 || (!a.w && !a.w8) || !a.out0 || a.n0 < 0) return OMR_ERR_ARG;
     if (a.w8 ? (!a.w8_scale || ((uintptr_t)a.w8 & 7)) : (((uintptr_t)a.w & 15) != 0)) return OMR_ERR_ARG;
@@ -263,16 +266,18 @@ int decode_linear_impl(const omr_decode_linear_args& a, const int* row_pos, long
     const dim3 grid((unsigned)cdiv(a.N, NOUT), (unsigned)cdiv(a.M, RM)), block(256);
     const size_t shm = (size_t)RM * a.K * sizeof(float);
     if (a.dtype != OMR_BF16 && a.dtype != OMR_F32) return OMR_ERR_UNSUPPORTED;
-    const LinArgs la = {a, row_pos, out1_pos_ld};
-    auto launch = [&](auto rows_c) {
-        constexpr bool ROWS = decltype(rows_c)::value;
-        if (a.dtype == OMR_BF16 && a.w8) hipLaunchKernelGGL((decode_linear_kernel<bf16, true, ROWS>), grid, block, shm, (hipStream_t)stream, la);
-        else if (a.dtype == OMR_F32 && a.w8) hipLaunchKernelGGL((decode_linear_kernel<float, true, ROWS>), grid, block, shm, (hipStream_t)stream, la);
-        else if (a.dtype == OMR_BF16) hipLaunchKernelGGL((decode_linear_kernel<bf16, false, ROWS>), grid, block, shm, (hipStream_t)stream, la);
-        else hipLaunchKernelGGL((decode_linear_kernel<float, false, ROWS>), grid, block, shm, (hipStream_t)stream, la);
+    if (group < 1 || (group > 1 && (!row_pos || a.M % group))) return OMR_ERR_ARG;
+    const LinArgs la = {a, row_pos, out1_pos_ld, group};
+    auto launch = [&](auto rows_c, auto group_c) {
+        constexpr bool ROWS = decltype(rows_c)::value, GROUP = decltype(group_c)::value;
+        if (a.dtype == OMR_BF16 && a.w8) hipLaunchKernelGGL((decode_linear_kernel<bf16, true, ROWS, GROUP>), grid, block, shm, (hipStream_t)stream, la);
+        else if (a.dtype == OMR_F32 && a.w8) hipLaunchKernelGGL((decode_linear_kernel<float, true, ROWS, GROUP>), grid, block, shm, (hipStream_t)stream, la);
+        else if (a.dtype == OMR_BF16) hipLaunchKernelGGL((decode_linear_kernel<bf16, false, ROWS, GROUP>), grid, block, shm, (hipStream_t)stream, la);
+        else hipLaunchKernelGGL((decode_linear_kernel<float, false, ROWS, GROUP>), grid, block, shm, (hipStream_t)stream, la);
     };
-    if (row_pos) launch(std::true_type());
-    else launch(std::false_type());
+    if (group > 1) launch(std::true_type(), std::true_type());
+    else if (row_pos) launch(std::true_type(), std::false_type());
+    else launch(std::false_type(), std::false_type());
     if (a.amax_idx) hipLaunchKernelGGL(decode_pick_kernel, dim3((unsigned)a.M), dim3(64), 0, (hipStream_t)stream, a.amax_part, (int)grid.x, a.amax_idx, a.amax_val);
     OMR_CHECK_LAUNCH();
     return OMR_OK;
@@ -287,15 +292,25 @@ bool takes_row_kernel(const omr_decode_desc& d) {
 
 void launch_rows_tables(const Model& m, const int* pos, int off, int n_steps, void* stream) {
     const omr_decode_desc& d = *m.d;
-    const size_t tab = (size_t)d.B * d.max_len;
+    const size_t tab = (size_t)m.rows * d.max_len;
     hipLaunchKernelGGL(decode_rows_tables_kernel, dim3((unsigned)cdiv((long)d.B * n_steps, 256)), dim3(256), 0, (hipStream_t)stream, pos, off, d.B,
-                       n_steps, d.max_len, d.window, m.w.rows_tab, m.w.rows_tab + tab, m.w.rows_tab + 2 * tab);
+                       n_steps, d.max_len, d.window, 0, m.w.rows_tab, m.w.rows_tab + tab, m.w.rows_tab + 2 * tab);
+}
+
+// The tables of ONE grouped position: row b * group + r sits at pos[b] + r (clamped like the steps of launch_rows_tables), entry
+// [b][r] of the first position's part of each table.
+Position launch_group_tables(const Model& m, const int* pos, int t_max, void* stream) {
+    const omr_decode_desc& d = *m.d;
+    const size_t tab = (size_t)m.rows * d.max_len;
+    hipLaunchKernelGGL(decode_rows_tables_kernel, dim3((unsigned)cdiv((long)m.rows, 256)), dim3(256), 0, (hipStream_t)stream, pos, 0, d.B, m.group,
+                       d.max_len, d.window, 1, m.w.rows_tab, m.w.rows_tab + tab, m.w.rows_tab + 2 * tab);
+    return Position{t_max + m.group - 1, m.w.rows_tab, m.w.rows_tab + tab, m.w.rows_tab + 2 * tab};
 }
 
 // pos == NULL: every row at t.  Otherwise the rows of step s of the tables launch_rows_tables filled; t is the furthest row's.
 Position position_at(const Model& m, const int* pos, int t, int s) {
     if (!pos) return Position{t, nullptr, nullptr, nullptr};
-    const size_t tab = (size_t)m.d->B * m.d->max_len, at = (size_t)s * m.d->B;
+    const size_t tab = (size_t)m.rows * m.d->max_len, at = (size_t)s * m.d->B;
     return Position{t, m.w.rows_tab + at, m.w.rows_tab + tab + at, m.w.rows_tab + 2 * tab + at};
 }
 
@@ -303,10 +318,10 @@ Position position_at(const Model& m, const int* pos, int t, int s) {
 
 extern "C" int omr_decode_linear(const omr_decode_linear_args* ap, void* stream) {
     if (!ap) return OMR_ERR_ARG;
-    return omr_dec::decode_linear_impl(*ap, nullptr, 0, stream);
+    return omr_dec::decode_linear_impl(*ap, nullptr, 0, stream, 1);
 }
 
 extern "C" int omr_decode_linear_rows(const omr_decode_linear_args* ap, const int* row_pos, long out1_pos_ld, void* stream) {
     if (!ap || !row_pos || out1_pos_ld < 0) return OMR_ERR_ARG;
-    return omr_dec::decode_linear_impl(*ap, row_pos, out1_pos_ld, stream);
+    return omr_dec::decode_linear_impl(*ap, row_pos, out1_pos_ld, stream, 1);
 }

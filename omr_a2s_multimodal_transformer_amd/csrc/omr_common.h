@@ -152,6 +152,14 @@ int attn_fwd_split_partials_rows(int dtype, const void* q, const void* k, const 
                                  long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
                                  const int* kv_len, const int* kv_start, float* split_ws, long split_ws_floats, int* nsplit, void* stream);
 
+// The self-attention of a grouped decode position (omr_decode_verify_rows): `group` consecutive rows are consecutive positions of ONE
+// K|V slot, so row b reads slot b / group while kv_len / kv_start stay PER ROW (device int32 [B]): row b sees slot rows
+// [kv_start[b], kv_start[b] + kv_len[b]).  Otherwise attn_fwd_split_partials_rows.
+int attn_fwd_split_partials_group(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, long ldq, long ldk, long ldv,
+                                  long ldo, long bsq, long bsk, long bsv, long bso, int B, int H, int T, int S, int head_dim,
+                                  const int* kv_len, const int* kv_start, int group, float* split_ws, long split_ws_floats, int* nsplit,
+                                  void* stream);
+
 // How a row body reads x[i].  PlainLoad: the value.  MaskedLoad (grammar-constrained decoding, omr_grammar_desc of include/omr_hip.h): -inf where the
 // token automaton forbids token i in the row's current state -- next_row[cls[i]] < 0, next_row being that state's row of the
 // transition table (C <= 256 ints, staged in LDS once per row by stage_next_row) and cls the class of every vocabulary entry

@@ -320,6 +320,22 @@ class Decoder(nn.Module):
             raise RuntimeError("init_slot_decode: this decoder's widths do not take omr_decode_steps_rows")
         return SlotDecodeState(self, rows, capacity, self._compute_dtype(), device, sos)
 
+    def width_text(self) -> str:
+        """The widths `takes_slot_state` goes by, for error messages."""
+        layer = self.transformer_decoder.layers[0]
+        return f"d = {self.embedding.weight.shape[1]}, ff = {layer.linear1.weight.shape[0]}, {layer.self_attn.num_heads} heads"
+
+    @torch.no_grad()
+    def init_spec_decode(self, draft: "Decoder", memory, draft_memory, k: int = 4, sos: int = 2, eos: int = 1,
+                         max_out: Optional[int] = None) -> "SpecDecodeState":
+        """The state of a speculative greedy decode (omr_spec_decode_cycles; an extension of the reference's greedy loop): this
+        decoder is the target, `draft` a cheaper decoder with the same vocabulary that proposes k tokens per cycle.  memory /
+        draft_memory: lists of [S_b, d] / [1, S_b, d] memories, one pair per input, each model's own encoding of it; the limits
+        of a ragged state apply to both (check_ragged_memories).  max_out: tokens per input at most (default: the shorter
+        positional table).  Caches of both models, the grouped workspace and the output runs are allocated here."""
+        as_list = lambda m: list(m) if isinstance(m, (list, tuple)) else [m]         # noqa: E731
+        return SpecDecodeState(self, as_list(memory), draft, as_list(draft_memory), k, sos, eos, max_out)
+
     @torch.no_grad()
     def init_beam_decode(self, memory, beam: int, sos: int = 2, eos: int = 1) -> "BeamDecodeState":
         """The state of a beam search over N inputs at once, `beam` hypotheses each (omr_beam_decode_steps).  memory: [1, S, d],
@@ -710,6 +726,137 @@ class SlotDecodeState(DecodeState):
         raise RuntimeError("a slot decode state has no common position: use admit / run_rows")
 
     run = step_logits = rewind = share_memory_between = reorder_rows = _no_lockstep
+
+
+MAX_DRAFT_LEN = 31           # OMR_MAX_VERIFY_ROWS - 1: a cycle's proposals plus the token before them are the rows of one grouped position
+
+
+def check_draft_len(k) -> None:
+    """THE check of the proposals per cycle (evaluation.check_draft, SpecDecodeState)."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_DRAFT_LEN:
+        raise ValueError(f"draft_len must be an integer in 1..{MAX_DRAFT_LEN}, got {k}")
+
+
+def check_row_widths(name: str, dec: "Decoder") -> None:
+    """THE check that a model of a speculative decode (`name`: "target" / "draft") takes the row kernel; the message names the widths."""
+    if not dec.takes_slot_state():
+        raise ValueError(f"speculative decode: the {name}'s decoder widths ({dec.width_text()}) are outside the row kernel")
+
+
+class _SpecDesc(ctypes.Structure):
+    """omr_spec_desc of include/omr_hip.h."""
+    STATE_FIELDS = ("pos", "out_len", "done", "accepted", "totals", "first", "prev", "tokens", "picks", "top1", "dpicks", "out_tokens", "out_top1")
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "k", "eos", "max_out", "t_max", "pad_")] + [("state", ctypes.c_void_p), ("state_bytes", ctypes.c_long)] + [
+        (n, ctypes.c_void_p) for n in STATE_FIELDS] + [("ws_t", ctypes.c_void_p), ("ws_t_bytes", ctypes.c_long)]
+
+
+class SpecDecodeState:
+    """Device state of a speculative greedy decode of B inputs (csrc/decode_spec.hip, omr_spec_decode_cycles): a ragged decode
+    state of the TARGET over its memories and one of the DRAFT over its own (both models encode the input themselves), the
+    target's scratch for a grouped position of k + 1 rows per slot, and the cycle state (positions, proposals, picks, output
+    runs, totals) in ONE device block that snapshot() brings to the host with one copy.  start() runs position 0 of both models
+    with the plain step; run_cycles(n, t_max) enqueues n cycles; plain(n, pos) runs n plain positions of the target from per-row
+    positions (the tail before max_len, where a cycle no longer fits)."""
+
+    def __init__(self, dec: "Decoder", mems, draft: "Decoder", draft_mems, k: int, sos: int, eos: int, max_out: Optional[int] = None):
+        import numpy as np
+        check_draft_len(k)
+        if len(mems) != len(draft_mems) or not mems:
+            raise ValueError(f"speculative decode: {len(mems)} memories for the target, {len(draft_mems)} for the draft")
+        if draft.output_size != dec.output_size or not (0 <= sos < dec.output_size and 0 <= eos < dec.output_size):
+            raise ValueError(f"speculative decode: vocabularies {dec.output_size} / {draft.output_size}, sos {sos}, eos {eos} do not fit")
+        check_row_widths("target", dec)
+        check_row_widths("draft", draft)
+        self.target = DecodeState(dec, dec.memory_list(mems), dec._compute_dtype())
+        self.draft = DecodeState(draft, draft.memory_list(draft_mems), draft._compute_dtype())
+        self.B, self.k, self.R, self.sos, self.eos = self.target.B, k, k + 1, sos, eos
+        self.max_len = min(self.target.max_len, self.draft.max_len)
+        self.max_out = self.max_len if max_out is None else min(int(max_out), self.max_len)
+        dev = self.target.self_kv.device
+        sd = self.sdesc = _SpecDesc()
+        sd.B, sd.k, sd.eos, sd.max_out, sd.t_max = self.B, k, eos, self.max_out, 1
+        sd.state = None
+        nbytes = lib().query("omr_spec_workspace_bytes", ctypes.byref(sd))
+        if nbytes <= 0:
+            raise RuntimeError("libomr_hip: omr_spec_workspace_bytes rejected the speculative descriptor")
+        self._off = {n: int(getattr(sd, n) or 0) for n in _SpecDesc.STATE_FIELDS}      # state == NULL: the fields are offsets
+        self._np = np
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        sd.state, sd.state_bytes = self.state.data_ptr(), nbytes
+        if lib().query("omr_spec_workspace_bytes", ctypes.byref(sd)) != nbytes:
+            raise RuntimeError("libomr_hip: omr_spec_workspace_bytes changed its answer")
+        ws_bytes = lib().query("omr_decode_group_workspace_bytes", ctypes.byref(self.target.desc), self.R)
+        if ws_bytes <= 0:
+            raise RuntimeError("libomr_hip: omr_decode_group_workspace_bytes rejected the target's descriptor")
+        self.ws_t = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        sd.ws_t, sd.ws_t_bytes = self.ws_t.data_ptr(), ws_bytes
+        self.tail_pos = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.cycles = 0
+
+    def _dev(self, name: str, dtype: torch.dtype, count: int) -> torch.Tensor:
+        off = self._off[name]
+        return self.state[off:off + count * torch.empty((), dtype=dtype).element_size()].view(dtype)
+
+    def start(self):
+        """Position 0 of both models with the plain step (omr_decode_steps_varlen from <sos>), and the cycle state after it: every
+        slot at position 1 with one token in its run -> (tokens [B], top-1 values [B]) on the device."""
+        B = self.B
+        sos = torch.full((B, 1), self.sos, dtype=torch.int64, device=self.state.device)
+        toks, top1 = self.target.run(sos, 1)
+        self.draft.run(sos, 1)
+        self.state.zero_()
+        self._dev("pos", torch.int32, B).fill_(1)
+        self._dev("out_len", torch.int32, B).fill_(1)
+        done = toks[0] == self.eos
+        self._dev("done", torch.int32, B).copy_(torch.ones_like(done) if self.max_out <= 1 else done)
+        self._dev("first", torch.int64, B).copy_(toks[0])
+        self._dev("prev", torch.int64, B).fill_(self.sos)
+        self._dev("out_tokens", torch.int64, B * self.max_out).view(B, self.max_out)[:, 0].copy_(toks[0])
+        self._dev("out_top1", torch.float32, B * self.max_out).view(B, self.max_out)[:, 0].copy_(top1[0])
+        self.cycles = 0
+        return toks[0], top1[0]
+
+    def run_cycles(self, n_cycles: int, t_max: int) -> None:
+        """n_cycles cycles of draft k, verify k + 1, accept, from one host call.  t_max: an upper bound of every live slot's position."""
+        if n_cycles < 1 or t_max < 1 or t_max + n_cycles * self.R > self.max_len:
+            raise RuntimeError("speculative decode beyond max_seq_len (positional-encoding table exhausted)")
+        self.sdesc.t_max = t_max
+        lib().call("omr_spec_decode_cycles", ctypes.byref(self.target.desc), ctypes.byref(self.draft.desc), ptr(self.target.mem_len),
+                   ptr(self.draft.mem_len), ctypes.byref(self.sdesc), self.k, n_cycles, cur_stream())
+        self.cycles += n_cycles
+
+    def snapshot(self) -> dict:
+        """One device-to-host copy of the whole block -> {field: numpy array}."""
+        np = self._np
+        host = self.state.cpu().numpy()
+        B, R = self.B, self.R
+
+        def view(name, dtype, count):
+            off = self._off[name]
+            return host[off:off + count * np.dtype(dtype).itemsize].view(dtype)
+
+        out = {n: view(n, np.int32, B) for n in ("pos", "out_len", "done", "accepted")}
+        out["totals"] = view("totals", np.int64, 2)
+        out["first"], out["prev"] = view("first", np.int64, B), view("prev", np.int64, B)
+        out["tokens"], out["picks"] = view("tokens", np.int64, B * R).reshape(B, R), view("picks", np.int64, B * R).reshape(B, R)
+        out["top1"] = view("top1", np.float32, B * R).reshape(B, R)
+        out["out_tokens"] = view("out_tokens", np.int64, B * self.max_out).reshape(B, self.max_out)
+        out["out_top1"] = view("out_top1", np.float32, B * self.max_out).reshape(B, self.max_out)
+        return out
+
+    def plain(self, n_steps: int, pos: List[int]):
+        """n_steps plain positions of the target (omr_decode_steps_rows), row b from pos[b], feeding the last token of its run ->
+        (tokens int64 [n_steps, B], top-1 fp32 [n_steps, B]) on the device."""
+        t_max = max(pos)
+        if n_steps < 1 or min(pos) < 0 or t_max + n_steps > self.target.max_len:
+            raise RuntimeError("decode_step beyond max_seq_len (positional-encoding table exhausted)")
+        dev = self.state.device
+        self.tail_pos.copy_(torch.tensor(pos, dtype=torch.int32))
+        toks = torch.empty((n_steps, self.B), dtype=torch.int64, device=dev)
+        top1 = torch.empty((n_steps, self.B), dtype=torch.float32, device=dev)
+        lib().call("omr_decode_steps_rows", ctypes.byref(self.target.desc), ptr(self.target.mem_len), ptr(self.tail_pos), t_max,
+                   ptr(self._dev("first", torch.int64, self.B)), n_steps, ptr(toks), ptr(top1), None, cur_stream())
+        return toks, top1
 
 
 class _BeamDesc(ctypes.Structure):

@@ -72,6 +72,92 @@ def active_grammar(model):
     return check_grammar(g, len(model.w2i), model.w2i[EOS_TOKEN])
 
 
+@dataclass
+class SpecOptions:
+    """What `spec_option` hands the decode routes: the draft model, the proposals per cycle, and how the draft encodes an item
+    of the call (its own encoder(s); for a unimodal draft of a multimodal target, the image or the audio of the pair)."""
+    draft: object
+    k: int
+    encode: Callable
+
+
+_SPEC = contextvars.ContextVar("omr_spec", default=None)
+
+
+def active_spec() -> Optional[SpecOptions]:
+    """The speculative-decoding options of the evaluation call under way (`spec_option`), or None: no draft."""
+    return _SPEC.get()
+
+
+def check_draft(model, draft, draft_len, draft_source, others: dict) -> SpecOptions:
+    """Every refusal of `draft=`, before the route or the hardware is looked at -> the options."""
+    from .decoder import check_draft_len, check_row_widths
+    if not hasattr(draft, "w2i") or not hasattr(draft, "decoder"):
+        raise ValueError("draft must be a Transformer or a MultimodalTransformer")
+    if dict(draft.w2i) != dict(model.w2i):
+        raise ValueError(f"draft: its vocabulary ({len(draft.w2i)} entries) differs from the target's ({len(model.w2i)}): a proposal is "
+                         "compared with the target's pick by token id")
+    check_draft_len(draft_len)
+    if others.get("beam", 1) != 1:
+        raise ValueError("draft= decodes greedily: it does not combine with beam=")
+    if others.get("grammar", None) is not None or getattr(model, "decode_grammar", None) is not None and "grammar" not in others:
+        raise ValueError("draft= does not combine with a grammar (grammar= or decode_grammar): the draft's proposals are unconstrained")
+    if others.get("refill", False):
+        raise ValueError("draft= does not combine with refill=True: the speculative state has no slots to refill")
+    if draft.max_seq_len < model.max_seq_len:
+        raise ValueError(f"draft: its max_seq_len {draft.max_seq_len} is shorter than the target's {model.max_seq_len}")
+    target_pair, draft_pair = hasattr(model, "image_encoder"), hasattr(draft, "image_encoder")
+    if draft_pair and not target_pair:
+        raise ValueError("draft: a MultimodalTransformer drafts for a MultimodalTransformer only")
+    if target_pair and not draft_pair:
+        if draft_source not in ("image", "audio"):
+            raise ValueError('draft: a unimodal draft of a multimodal target needs draft_source="image" or "audio"')
+        side = 0 if draft_source == "image" else 1
+        encode = lambda pair: draft._encode_input(pair[side])                       # noqa: E731
+    else:
+        if draft_source is not None:
+            raise ValueError("draft_source goes with a unimodal draft of a multimodal target only")
+        encode = draft._encode_input
+    check_row_widths("target", model.decoder)
+    check_row_widths("draft", draft.decoder)
+    return SpecOptions(draft=draft, k=draft_len, encode=encode)
+
+
+def spec_option(fn):
+    """Gives an evaluation entry point (`predict` / `predict_with_probs` / `evaluate` of both model classes) the keywords
+    `draft` (a model with the target's vocabulary, or None: no speculation), `draft_len` (proposals per cycle, 1..31, default 4) and
+    `draft_source` ("image" / "audio": what a unimodal draft of a multimodal target reads), like `refill_option`: the function's
+    own parameter list stays as it is and the options hold for the duration of the call; `_predict` asks `active_spec()`.  It is the
+    outermost option, so it sees -- without consuming them -- the `beam`, `grammar` and `refill` keywords it does not combine with.
+    Without a draft nothing is allocated or launched.  The statistics of the call are left in `model.last_spec_stats`."""
+    @functools.wraps(fn)
+    def call(self, *args, draft=None, draft_len=4, draft_source=None, **kwargs):
+        if draft is None:
+            if draft_source is not None:
+                raise ValueError("draft_source goes with draft=")
+            return fn(self, *args, **kwargs)
+        opts = check_draft(self, draft, draft_len, draft_source, kwargs)
+        self.last_spec_stats = {"cycles": 0, "drafted": 0, "accepted": 0, "tokens": 0}
+        token = _SPEC.set(opts)
+        try:
+            return fn(self, *args, **kwargs)
+        finally:
+            _SPEC.reset(token)
+    return call
+
+
+def no_draft_option(fn):
+    """For the late-fusion entry points (weighted_predict / weighted_evaluate, sw_predict / sw_evaluate): `draft=` (and `draft_len=`,
+    `draft_source=`) is refused with ValueError before anything is encoded -- two models decode in lock-step there, and a draft for
+    the pair is a later change.  draft=None passes, so a caller may hand the keyword through."""
+    @functools.wraps(fn)
+    def call(*args, draft=None, draft_len=None, draft_source=None, **kwargs):
+        if draft is not None or draft_len is not None or draft_source is not None:
+            raise ValueError(f"{fn.__name__} does not take draft=: speculative decoding covers predict / predict_with_probs / evaluate of one model")
+        return fn(*args, **kwargs)
+    return call
+
+
 def plan_groups(lengths: Sequence[int], batch_size: int, window: int = 0) -> Tuple[List[int], List[List[int]]]:
     """-> (singles, groups) over the indices of `lengths` (memory lengths in tokens).  singles: memories decoded alone at batch
     size 1 -- at most MIN_RAGGED_MEMORY tokens (such a row alone takes another attention kernel than the ragged batch) or
@@ -136,6 +222,58 @@ def decode_rows(step: Callable, rows: int, eos: int, budget: int, sync_every: in
                         values[b].append(float(top1[s][b]))
                     done[b] = t == eos
         left -= len(toks)
+    return out, values
+
+
+def decode_spec(first, cycles: Callable, plain: Callable, rows: int, eos: int, budget: int, R: int, sync_every: int,
+                want_probs: bool = False) -> Tuple[List[List[int]], List[List[float]]]:
+    """The read-back loop of a speculative greedy decode (decoder.SpecDecodeState), next to `decode_rows` and with its result:
+    (token ids, top-1 values) per row, each cut after its <eos> (kept) or after `budget` positions.
+    first: (tokens [rows], values [rows] or None) of position 0, which the caller ran with the plain step.
+    cycles(n, t_max) enqueues n cycles of R = k + 1 positions each and returns, per row, the tokens (and values, or None) the
+    cycles appended to that row's run -- between 1 and R per cycle for a live row, none for a finished one; t_max is the furthest
+    live row's position, and n is bounded here so that t_max + n * R <= budget: a cycle advances a row by at most R.
+    plain(n, pos) runs n plain positions of every row, row b from pos[b] (0 for a finished row), and returns (tokens, values) as
+    host lists [n][rows]: the last fewer-than-R positions before `budget`, where a cycle no longer fits.  Once the plain steps
+    have begun the rows stay with them.  Touches host lists and the two callbacks only."""
+    if rows < 1 or sync_every < 1 or R < 2:
+        raise ValueError(f"decode_spec: rows {rows}, sync_every {sync_every} must be >= 1 and R {R} >= 2")
+    out: List[List[int]] = [[] for _ in range(rows)]
+    values: List[List[float]] = [[] for _ in range(rows)]
+    if budget <= 0:
+        return out, values
+    done = [False] * rows
+
+    def append(b: int, t: int, v) -> None:
+        out[b].append(int(t))
+        if want_probs:
+            values[b].append(float(v))
+        done[b] = int(t) == eos or len(out[b]) >= budget
+
+    for b in range(rows):
+        append(b, first[0][b], first[1][b] if want_probs else None)
+    while not all(done):
+        t_max = max(len(out[b]) for b in range(rows) if not done[b])
+        n = min(sync_every, (budget - t_max) // R)
+        if n < 1:
+            break
+        new_t, new_v = cycles(n, t_max)
+        for b in range(rows):
+            if done[b]:
+                continue
+            if not len(new_t[b]):
+                raise RuntimeError("decode_spec: a live row did not advance")
+            for i, t in enumerate(new_t[b]):
+                append(b, t, new_v[b][i] if want_probs else None)
+                if done[b]:
+                    break
+    while not all(done):
+        pos = [0 if done[b] else len(out[b]) for b in range(rows)]
+        toks, top1 = plain(min(sync_every, budget - max(pos)), pos)
+        for s, row in enumerate(toks):
+            for b in range(rows):
+                if pos[b] and not done[b]:
+                    append(b, row[b], top1[s][b] if want_probs else None)
     return out, values
 
 

@@ -21,8 +21,9 @@ from ._lib import lib
 from .config import DistillConfig, ModelConfig
 from .decoder import MAX_BEAM, Decoder, MultiheadAttention, _to_dev, takes_ragged_state
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
-from .evaluation import (WINDOW_BATCHES, Alignment, active_grammar, cells_and_boxes, decode_rows, decode_stream, grammar_option, grid_of,
-                         plan_align_groups, plan_groups, refill_enabled, refill_option, stream_order)
+from .evaluation import (WINDOW_BATCHES, Alignment, active_grammar, active_spec, cells_and_boxes, decode_rows, decode_spec, decode_stream,
+                         grammar_option, grid_of, plan_align_groups, plan_groups, plan_pair_groups, refill_enabled, refill_option, spec_option,
+                         stream_order)
 from .grammar import host_mask
 from .lightning_shim import LightningModule
 from .metrics import compute_metrics, compute_metrics_sharded
@@ -159,6 +160,8 @@ class _Base(FlatModuleMixin, LightningModule):
     _refill_sync_every = 8    # positions per read-back of a refilled decode (evaluation.decode_stream); results do not depend on it
     decode_grammar = None     # grammar.Grammar every decode of this model is constrained by unless a call says `grammar=` (evaluation.grammar_option)
     _refill_state_hook = None  # called with every SlotDecodeState `_greedy_stream` creates, before its first admission (tests)
+    _spec_sync_every = 4      # cycles per read-back of a speculative decode (evaluation.decode_spec); results do not depend on it
+    last_spec_stats = None    # {"cycles", "drafted", "accepted", "tokens"} of the last call with draft= (evaluation.spec_option)
 
     def _common_init(self, w2i, i2w, ytest_i2w, max_seq_len, attn_window, teacher_forcing_prob, config: Optional[ModelConfig]):
         if isinstance(config, dict):
@@ -332,6 +335,43 @@ class _Base(FlatModuleMixin, LightningModule):
         return decode_stream(step, admit, stream_order(lens), state.B, self.w2i[EOS_TOKEN], self.max_seq_len, self._refill_sync_every, want_probs,
                              gstate)
 
+    def _greedy_spec(self, mems: List[torch.Tensor], draft_mems: List[torch.Tensor], spec, want_probs: bool = False):
+        """Speculative greedy decode of memories that all take a ragged state (Decoder.init_spec_decode, evaluation.decode_spec):
+        spec.draft's decoder proposes spec.k tokens per cycle over its own memories, this model's decoder verifies them in one
+        grouped position -> (token ids, top-1 logits) per memory, each what `_greedy_state` of that memory alone returns.  Adds the
+        device totals to `last_spec_stats`."""
+        state = self.decoder.init_spec_decode(spec.draft.decoder, mems, draft_mems, spec.k, self.w2i[SOS_TOKEN], self.w2i[EOS_TOKEN],
+                                              max_out=self.max_seq_len)
+        tok0, top0 = state.start()
+        first = (tok0.cpu().tolist(), top0.cpu().tolist() if want_probs else None)
+        lens = [1] * state.B
+
+        def cycles(n: int, t_max: int):
+            state.run_cycles(n, t_max)
+            snap = state.snapshot()                                   # one device sync for the whole chunk
+            new_t, new_v = [], []
+            for b in range(state.B):
+                n_b = int(snap["out_len"][b])
+                new_t.append(snap["out_tokens"][b, lens[b]:n_b].tolist())
+                new_v.append(snap["out_top1"][b, lens[b]:n_b].tolist() if want_probs else None)
+                lens[b] = n_b
+            cycles.totals = snap["totals"]
+            return new_t, new_v
+
+        def plain(n: int, pos: List[int]):
+            toks, top1 = state.plain(n, pos)
+            return toks.cpu().tolist(), top1.cpu().tolist() if want_probs else None
+
+        cycles.totals = (0, 0)
+        out, values = decode_spec(first, cycles, plain, state.B, self.w2i[EOS_TOKEN], self.max_seq_len, state.R, self._spec_sync_every, want_probs)
+        stats = self.last_spec_stats if self.last_spec_stats is not None else {"cycles": 0, "drafted": 0, "accepted": 0, "tokens": 0}
+        stats["cycles"] += state.cycles
+        stats["drafted"] += int(cycles.totals[0])
+        stats["accepted"] += int(cycles.totals[1])
+        stats["tokens"] += sum(len(seq) for seq in out)
+        self.last_spec_stats = stats
+        return out, values
+
     @torch.no_grad()
     def _predict(self, items: Iterable, encode: Callable[[object], torch.Tensor], batch_size: int, want_probs: bool = False):
         """Greedy predictions of inputs of any size, in input order, each equal to `_greedy` of that input alone.  A window
@@ -345,11 +385,15 @@ class _Base(FlatModuleMixin, LightningModule):
         a decoder whose widths omr_decode_steps_rows does not take decodes in groups as without the flag.
         Called with grammar= (evaluation.grammar_option), or on a model with `decode_grammar`: every route above decodes under
         that automaton (grammar.Grammar); with None nothing is allocated or launched for it.  A prediction that reaches
-        max_seq_len before an accepting state is a valid prefix."""
+        max_seq_len before an accepting state is a valid prefix.
+        Called with draft= (evaluation.spec_option; greedy only): the draft encodes every input itself, and the inputs of which BOTH
+        memories take a ragged state are decoded speculatively, group by group (`_greedy_spec`); the others go through `_greedy`.
+        Same predictions and values."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         beam = 1 if want_probs else self._decode_beam          # predict_with_probs takes no beam
         refill = refill_enabled()
+        spec = active_spec()                                   # evaluation.check_draft has refused beam, refill and a grammar beside it
         if refill and beam > 1:
             raise ValueError("refill=True decodes greedily: the beam state (two caches, a history table) has no slots to refill")
         if beam > 1:
@@ -380,7 +424,17 @@ class _Base(FlatModuleMixin, LightningModule):
             mems = [encode(x) for x in window]
             out: List[Optional[List[str]]] = [None] * len(mems)
             outp: List[Optional[List[float]]] = [None] * len(mems)
-            singles, groups = plan_groups([m.shape[1] for m in mems], rows)
+            if spec is not None:
+                dmems = [spec.encode(x) for x in window]
+                singles, groups = plan_pair_groups([m.shape[1] for m in mems], [m.shape[1] for m in dmems], rows)
+                for g in groups:
+                    ids, top1 = self._greedy_spec([mems[i] for i in g], [dmems[i] for i in g], spec, want_probs)
+                    for i, seq, t1 in zip(g, self._words(ids), top1):
+                        out[i], outp[i] = seq, t1
+                groups = []
+                del dmems
+            else:
+                singles, groups = plan_groups([m.shape[1] for m in mems], rows)
             for i in singles:
                 out[i], outp[i] = decode_single(mems[i])
             if refill and groups and self.decoder.takes_slot_state(max(mems[i].shape[1] for g in groups for i in g)):
@@ -702,6 +756,7 @@ class Transformer(_Base):
         assert x.size(0) == 1, "predict takes inputs of batch size 1 ([1, C, H, W]); their sizes may differ"
         return self.encode(x)
 
+    @spec_option
     @grammar_option
     @refill_option
     @_beam_option
@@ -710,9 +765,13 @@ class Transformer(_Base):
         """Greedy predictions of inputs [1, C, H_b, W_b] of any size, in input order: each equals validation_step's decode
         of that input, decoded batch_size memories at a time.  Keyword `beam` (2 .. 8, `_beam_option`): the words of
         `beam_search` of each input, batch_size // beam inputs at a time.  Keyword `refill` (default False, `refill_option`;
-        greedy only): continuous batching, a finished row's slot goes to the next input (`_predict`); same predictions."""
+        greedy only): continuous batching, a finished row's slot goes to the next input (`_predict`); same predictions.
+        Keywords `draft`, `draft_len` (evaluation.spec_option; also on `predict_with_probs` and `evaluate`): speculative decoding, a
+        cheaper model with this model's vocabulary proposes `draft_len` tokens per pass of this one; same predictions and values;
+        `last_spec_stats` holds the call's cycles and proposals made / accepted."""
         return self._predict(xs, self._encode_input, batch_size)
 
+    @spec_option
     @grammar_option
     @refill_option
     @torch.no_grad()
@@ -723,6 +782,7 @@ class Transformer(_Base):
         Keyword `grammar` (evaluation.grammar_option): the values are the top-1 ALLOWED logits."""
         return self._predict(xs, self._encode_input, batch_size, want_probs=True)
 
+    @spec_option
     @grammar_option
     @refill_option
     @_beam_option
@@ -950,6 +1010,7 @@ class MultimodalTransformer(_Base):
         x, _ = self.encoder_forward(xi=xi, xa=xa, xli=None, xla=None, apply_teacher_forcing_modality=False)
         return x
 
+    @spec_option
     @grammar_option
     @refill_option
     @_beam_option
@@ -958,9 +1019,12 @@ class MultimodalTransformer(_Base):
         """Greedy predictions of (image, audio) pairs of any size, in input order: each equals validation_step's decode of
         that pair, decoded batch_size memories at a time.  Keyword `beam` (2 .. 8, `_beam_option`): the words of `beam_search`
         of each pair's memory, batch_size // beam pairs at a time.  Keyword `refill` (default False, `refill_option`; greedy
-        only): continuous batching (`_predict`), same predictions."""
+        only): continuous batching (`_predict`), same predictions.  Keywords `draft`, `draft_len`, `draft_source`
+        (evaluation.spec_option; also on `evaluate`): speculative decoding with another MultimodalTransformer on the pair, or with a
+        unimodal Transformer on the pair's image / audio (`draft_source`); same predictions."""
         return self._predict(pairs, self._encode_input, batch_size)
 
+    @spec_option
     @grammar_option
     @refill_option
     @_beam_option
