@@ -763,6 +763,49 @@ int omr_ce_distill_bwd(int dtype, const void* logits, long ldv, int tdtype, cons
                        const long* target, const float* lse4, const double* acc4, void* dlogits, long M, int V, int pad_idx, float alpha,
                        float tau, float lam, float grad_scale, const float* grad_out, void* stream);
 
+/* ---- CTC auxiliary head (csrc/ctc.hip; an extension: joint CTC / attention training, and a transcript from the encoder alone) ---- */
+/* Memory -> time-ordered frames.  mem [B][S][d] holds sample b's own gh_b x gw_b feature grid row-major with pitch gw_b (cell (i, j) is
+ * row i * gw_b + j), zeros behind: the packed memory of the ragged route with grid = int32 [B][2] = (gh_b, gw_b) on the device, or the dense
+ * memory with grid == NULL, where every sample has the grid gh x gw (gh * gw <= S).  frames [B][Fmax][d]:
+ *   G_b = ceil(gh_b / pool),  F_b = G_b * gw_b,  frame f = j * G_b + q  (column j, left to right; group q, top to bottom inside the column)
+ *   frames[b][f][c] = (((x_r0 + x_r0+1) + x_r0+2) + ... + x_r1-1) / (float)(r1 - r0)     x_i = (float)mem[b][i * gw_b + j][c],
+ *   r0 = q * pool, r1 = min(r0 + pool, gh_b): fp32 additions top to bottom, ONE IEEE fp32 division by the count, one rounding to dtype.
+ *   A group of one row (always so with pool = 1) is a copy of the input's bits.  Rows f >= F_b are +0.  frame_len[b] = F_b (int32 [B]).
+ * A sample whose grid is not positive, does not fit S, or has F_b > Fmax counts as empty: F_b = 0.
+ * _bwd is the adjoint: dmem[b][i * gw_b + j][c] = dframes[b][f][c] / (float)count of the frame f that row i of column j went into (a copy
+ * where count = 1), rounded once to dtype; rows outside the grid are +0.
+ * OMR_ERR_ARG before any launch: a NULL mem / frames / frame_len, B < 1 or > 65535, S, d, pool or Fmax < 1, grid == NULL with gh or gw < 1 or
+ * gh * gw > S. */
+int omr_ctc_frames_fwd(int dtype, const void* mem, const int* grid, void* frames, int* frame_len, int B, int S, int d, int gh, int gw,
+                       int pool, int Fmax, void* stream);
+int omr_ctc_frames_bwd(int dtype, const void* dframes, const int* grid, void* dmem, int B, int S, int d, int gh, int gw, int pool, int Fmax,
+                       void* stream);
+/* bytes of the workspace of omr_ctc_fwd / omr_ctc_bwd (16-byte aligned): the frames' log-sum-exp, the stored log alpha / log beta
+ * [2][B][Fmax][2 Tmax + 2] fp32, their fp64 offsets [2][B][Fmax], log P [2][B], and the per-sample label tables.  -1 for sizes the entries refuse. */
+long omr_ctc_workspace_bytes(int B, int Fmax, int Tmax, int V);
+/* F.ctc_loss(log_softmax(logits), targets, frame_len, L, blank=blank_idx, reduction="mean", zero_infinity=True) on logits [B][Fmax][ldv >= V]
+ * (fp32 or bf16), frame_len int32 [B] (clamped into [0, Fmax]), targets int64 [B][T].  Sample b's label sequence is the prefix of
+ * targets[b] before the first element that equals blank_idx or eos_idx (or lies outside [0, V)); its length L_b is found on the device.
+ *   rows[b] = -log P_b (fp32; 0 where infeasible),  loss = (1 / B) sum_b rows_b / max(L_b, 1),  acc2 = {that sum, B} (fp64),
+ *   infeasible[0] = the number of samples with P_b = 0 (F_b < L_b + repeats_b, F_b = 0, or -inf logits): they add 0 and get +0 gradients.
+ * log alpha and log beta are kept relative to an fp64 offset that is advanced every 8 frames, so their precision does not fall with
+ * Fmax; log P, the division and the mean are one fp64 fixed-order pass.  No atomics on floats: two calls give the same bits.
+ * ws: omr_ctc_workspace_bytes(B, Fmax, T, V) bytes, handed unchanged to omr_ctc_bwd.
+ * OMR_ERR_ARG before any launch: a NULL pointer, B < 1 or > 32767, Fmax < 1, T < 1 or > 1023, V < 1, ldv < V, blank_idx outside [0, V),
+ * eos_idx outside [-1, V) (-1: no such token). */
+int omr_ctc_fwd(int dtype, const void* logits, long ldv, const int* frame_len, const long* targets, void* ws, double* acc2, float* loss,
+                float* rows, int* infeasible, int B, int Fmax, int T, int V, int blank_idx, int eos_idx, void* stream);
+/* dlogits[b][f][v] = s_b (softmax(logits[b][f])[v] - post[b][f][v]), s_b = grad_scale * grad_out / (B max(L_b, 1)), post = the sum over the
+ * lattice states that carry label v of exp(log alpha + log beta - log P - emission), summed in state order; written in the logits' dtype.
+ * +0: the columns [V, ldv), the frames >= F_b, every frame of an infeasible sample.  The same refusals as the forward. */
+int omr_ctc_bwd(int dtype, const void* logits, long ldv, const int* frame_len, const long* targets, const void* ws, void* dlogits, int B,
+                int Fmax, int T, int V, int blank_idx, float grad_scale, const float* grad_out, void* stream);
+/* The encoder-only transcript.  frame_arg / frame_val [B][Fmax]: each frame's arg-max column (ties to the lowest index) and its value as
+ * fp32 (frames >= F_b: blank_idx and 0).  tokens int32 [B][Fmax]: the arg-max path with repeats collapsed and blanks dropped, blank_idx
+ * behind; lengths int32 [B].  The same refusals as omr_ctc_fwd (no T). */
+int omr_ctc_greedy(int dtype, const void* logits, long ldv, const int* frame_len, int* frame_arg, float* frame_val, int* tokens, int* lengths,
+                   int B, int Fmax, int V, int blank_idx, void* stream);
+
 /* ---- guarded optimizer step ------------------------------------------------------------------------------- */
 /* What the reference gets from Lightning: Trainer(precision="16-mixed") (src/train.py:153) puts every step behind GradScaler,
  * which skips optimizer.step() when a gradient holds inf / NaN (torch/amp/grad_scaler.py, _maybe_opt_step), and

@@ -24,6 +24,16 @@ class ModelConfig:
     compute_dtype: str = "fp32"   # "fp32" (parity mode) or "bf16" (fp32 master weights + Adam)
     fp8_decode: bool = False      # BASELINE config 5 (extension): greedy / beam decode with fp8 (e4m3) MFMA weights in the decoder
     label_smoothing: float = 0.0  # extension: CrossEntropyLoss(label_smoothing=...) in training, torch's definition and range [0, 1]
+    ctc_weight: float = 0.0       # extension: w in [0, 1] of loss = (1 - w) CE + w CTC; > 0 gives Transformer a CTC head on the encoder memory
+    ctc_pool: int = 1             # extension: feature-grid rows averaged into one CTC frame (>= 1): divides the head's cost
+
+    def __post_init__(self) -> None:
+        w, p = self.ctc_weight, self.ctc_pool
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0.0 <= w <= 1.0:       # NaN fails
+            raise ValueError(f"ModelConfig: ctc_weight must lie in [0, 1] (got {w!r})")
+        if isinstance(p, bool) or not isinstance(p, int) or p < 1:
+            raise ValueError(f"ModelConfig: ctc_pool must be an integer >= 1 (got {p!r})")
+        self.ctc_weight = float(w)
 
     def to_dict(self) -> Dict[str, Any]:
         return asdict(self)

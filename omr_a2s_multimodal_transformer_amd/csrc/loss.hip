@@ -18,36 +18,10 @@ namespace {
 // in column order; rowsum[row] = block_sum of the 256 rs.
 template <typename T, bool SMOOTH>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logits, float* __restrict__ lse, int V, long ldv, float* __restrict__ rowsum) {
-    typedef typename Frag<T>::type F;
-    constexpr int VEC = Frag<T>::N;
     __shared__ float red_m[4], red_s[4], red_r[4];
     const long row = blockIdx.x;
-    const T* lr = logits + row * ldv;
     float mx = -INFINITY, s = 0.f, rs = 0.f;
-    const bool vec_ok = (ldv % VEC) == 0 && (((uintptr_t)logits) & 15) == 0;
-    if (vec_ok) {
-        for (int v0 = threadIdx.x * VEC; v0 < V; v0 += 256 * VEC) {
-            const F f = *reinterpret_cast<const F*>(lr + v0);      // v0 + VEC <= ldv: the padding columns are readable
-            float x[VEC];
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) x[e] = (v0 + e < V) ? to_f32(f[e]) : -INFINITY;
-            const float nm = fmaxf(mx, chunk_max(x));
-            online_add(x, mx, nm, 1.f, s);
-            mx = nm;
-            if constexpr (SMOOTH) {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) rs += (v0 + e < V) ? to_f32(f[e]) : 0.f;
-            }
-        }
-    } else {
-        for (int v = threadIdx.x; v < V; v += 256) {
-            const float x[1] = {to_f32(lr[v])};
-            const float nm = fmaxf(mx, x[0]);
-            online_add(x, mx, nm, 1.f, s);
-            mx = nm;
-            if constexpr (SMOOTH) rs += x[0];
-        }
-    }
+    row_online_pass<T, SMOOTH>(logits + row * ldv, row_vec_ok<T>(logits, ldv), V, mx, s, rs);
     if constexpr (SMOOTH) {
         rs = block_sum(rs, red_r);
         if (threadIdx.x == 0) rowsum[row] = rs;

@@ -27,6 +27,41 @@ template <int N> __device__ __forceinline__ void online_add(const float (&x)[N],
     s = s * __expf((m - sub) * k) + add;
 }
 
+// One thread's share of a row's single pass (256 threads per row, k = 1): the running (mx, s) over its 16-byte chunks (vec_ok) or its
+// strided columns, and with SMOOTH the fp32 sum rs of its logits (columns < V only: the padding may hold anything), added in column order.
+// ce_fwd_kernel (loss.hip) and the frame rows of the CTC loss (ctc.hip) run this very loop.
+template <typename T> __device__ __forceinline__ bool row_vec_ok(const T* logits, long ldv) {
+    return (ldv % Frag<T>::N) == 0 && (((uintptr_t)logits) & 15) == 0;
+}
+template <typename T, bool SMOOTH>
+__device__ __forceinline__ void row_online_pass(const T* __restrict__ lr, bool vec_ok, int V, float& mx, float& s, float& rs) {
+    typedef typename Frag<T>::type F;
+    constexpr int VEC = Frag<T>::N;
+    if (vec_ok) {
+        for (int v0 = threadIdx.x * VEC; v0 < V; v0 += 256 * VEC) {
+            const F f = *reinterpret_cast<const F*>(lr + v0);      // v0 + VEC <= ldv: the padding columns are readable
+            float x[VEC];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) x[e] = (v0 + e < V) ? to_f32(f[e]) : -INFINITY;
+            const float nm = fmaxf(mx, chunk_max(x));
+            online_add(x, mx, nm, 1.f, s);
+            mx = nm;
+            if constexpr (SMOOTH) {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) rs += (v0 + e < V) ? to_f32(f[e]) : 0.f;
+            }
+        }
+    } else {
+        for (int v = threadIdx.x; v < V; v += 256) {
+            const float x[1] = {to_f32(lr[v])};
+            const float nm = fmaxf(mx, x[0]);
+            online_add(x, mx, nm, 1.f, s);
+            mx = nm;
+            if constexpr (SMOOTH) rs += x[0];
+        }
+    }
+}
+
 // log sum_v exp(k x_v) of the row from the 256 threads' (m, s): every thread gets the value.  red_m / red_s: 4 floats of LDS each, free on
 // return.  ce_fwd_kernel needs the value on thread 0 alone; the second barrier and the other threads' arithmetic do not show in its time
 // (DESIGN.md "Loss kernels: shared steps").

@@ -699,3 +699,49 @@ def cross_entropy(logits_bvt: Tensor, target_bt: Tensor, pad_idx: int, label_smo
     if nll is None:
         nll = loss.detach()
     return (loss, nll) if return_nll else loss
+
+
+# ------------------------------------------------------------------------------------------------ CTC auxiliary head
+
+class CTCFramesFn(Function):
+    """Decoder memory [B, S, d] -> time-ordered frames [B, fmax, d] and their count per sample (kernels.ctc_frames_fwd): each sample's feature
+    grid read column by column, `pool` grid rows averaged per frame.  grid: the int32 [B, 2] device tensor of the ragged route, or None with
+    the one grid (gh, gw) of the dense route.  Nothing but the grid is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, mem, grid, gh, gw, pool, fmax):
+        ctx.cfg = (grid, gh, gw, pool, mem.shape[1])
+        frames, frame_len = K.ctc_frames_fwd(mem.contiguous(), grid, gh, gw, pool, fmax)
+        ctx.mark_non_differentiable(frame_len)
+        return frames, frame_len
+
+    @staticmethod
+    def backward(ctx, g, _g_len):
+        grid, gh, gw, pool, S = ctx.cfg
+        return K.ctc_frames_bwd(g.contiguous(), grid, gh, gw, pool, S), None, None, None, None, None
+
+
+class CTCLossFn(Function):
+    """F.ctc_loss(log_softmax(logits), ..., blank, reduction="mean", zero_infinity=True) on the head's logits [B, F, V] (kernels.ctc_fwd) ->
+    (loss, rows [B], infeasible [1]); the last two carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, frame_len, targets, V, blank, eos):
+        loss, rows, infeasible, _acc2, ws = K.ctc_fwd(logits, frame_len, targets, V, blank, eos)
+        ctx.cfg = (V, blank)
+        ctx.save_for_backward(logits, frame_len, targets, ws)
+        ctx.mark_non_differentiable(rows, infeasible)
+        return loss.view(()), rows, infeasible
+
+    @staticmethod
+    def backward(ctx, g, _g_rows, _g_inf):
+        logits, frame_len, targets, ws = ctx.saved_tensors
+        V, blank = ctx.cfg
+        return K.ctc_bwd(logits, frame_len, targets, ws, V, blank, grad_out=g.contiguous()), None, None, None, None, None
+
+
+def ctc_loss(frames_logits: Tensor, frame_len: Tensor, y_out: Tensor, blank: int, eos: int):
+    """CTC loss of the head's logits [B, F, V] (any row pitch >= V) against the targets y_out int64 [B, T], whose rows end at their first
+    `blank` (<PAD>) or `eos` -> (loss, rows, infeasible): the batch mean of nll_b / max(L_b, 1), the per-sample nll (0 where the target does not
+    fit the frames) and the number of such samples, all on the device (no sync)."""
+    return CTCLossFn.apply(frames_logits, frame_len, y_out.contiguous(), frames_logits.shape[2], int(blank), int(eos))

@@ -1130,3 +1130,122 @@ def ce_distill_bwd(logits2d: Tensor, target: Tensor, teacher_a: Optional[Tensor]
 
 def round_up(n: int, m: int) -> int:
     return (n + m - 1) // m * m
+
+
+# ------------------------------------------------------------------------------------------------ CTC auxiliary head (csrc/ctc.hip)
+
+def check_ctc(weight, pool) -> Tuple[float, int]:
+    """The ranges of ModelConfig.ctc_weight ([0, 1]) and ctc_pool (an integer >= 1); refused here, before anything is allocated or launched."""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)):
+        raise ValueError(f"ctc_weight must be a number, got {weight!r}")
+    weight = float(weight)
+    if not 0.0 <= weight <= 1.0:
+        raise ValueError(f"ctc_weight must be between 0.0 and 1.0, got {weight}")
+    if isinstance(pool, bool) or not isinstance(pool, int) or pool < 1:
+        raise ValueError(f"ctc_pool must be an integer >= 1, got {pool!r}")
+    return weight, pool
+
+
+def ctc_frame_count(gh: int, gw: int, pool: int) -> int:
+    """Frames of a gh x gw feature grid: ceil(gh / pool) groups per column, column by column."""
+    return (gh + pool - 1) // pool * gw
+
+
+def _check_grid(grid: Optional[Tensor], B: int, device) -> None:
+    if grid is not None:
+        assert grid.dtype == torch.int32 and grid.is_contiguous() and tuple(grid.shape) == (B, 2) and grid.device == device, \
+            f"grid must be int32 [B, 2] on the memory's device, got {grid.dtype} {tuple(grid.shape)} on {grid.device}"
+
+
+def ctc_frames_fwd(mem: Tensor, grid: Optional[Tensor], gh: int, gw: int, pool: int, fmax: int) -> Tuple[Tensor, Tensor]:
+    """Memory [B, S, d] (sample b's own gh_b x gw_b grid row-major, zeros behind) -> (frames [B, fmax, d], frame_len int32 [B]): column by
+    column, `pool` grid rows averaged per frame (omr_ctc_frames_fwd).  grid int32 [B, 2] on the device: the ragged route; None: every sample has
+    the grid gh x gw."""
+    require_cuda(mem, grid)
+    assert mem.dim() == 3 and mem.is_contiguous(), f"expected a contiguous [B, S, d] memory, got shape {tuple(mem.shape)} strides {mem.stride()}"
+    B, S, d = mem.shape
+    _check_grid(grid, B, mem.device)
+    frames = torch.empty((B, fmax, d), dtype=mem.dtype, device=mem.device)
+    frame_len = torch.empty(B, dtype=torch.int32, device=mem.device)
+    lib().call("omr_ctc_frames_fwd", dtype_code(mem.dtype), ptr(mem), ptr(grid), ptr(frames), ptr(frame_len), B, S, d, gh, gw, pool, fmax, cur_stream())
+    return frames, frame_len
+
+
+def ctc_frames_bwd(dframes: Tensor, grid: Optional[Tensor], gh: int, gw: int, pool: int, S: int) -> Tensor:
+    """Adjoint of ctc_frames_fwd: gradient [B, fmax, d] -> [B, S, d], zeros outside each sample's grid."""
+    require_cuda(dframes, grid)
+    assert dframes.dim() == 3 and dframes.is_contiguous()
+    B, fmax, d = dframes.shape
+    _check_grid(grid, B, dframes.device)
+    dmem = torch.empty((B, S, d), dtype=dframes.dtype, device=dframes.device)
+    lib().call("omr_ctc_frames_bwd", dtype_code(dframes.dtype), ptr(dframes), ptr(grid), ptr(dmem), B, S, d, gh, gw, pool, fmax, cur_stream())
+    return dmem
+
+
+def _ctc_logits(logits: Tensor, frame_len: Tensor, V: int) -> Tuple[int, int, int]:
+    """The checks every CTC entry makes of logits [B, Fmax, >= V] (unit inner stride, frames and samples back to back) -> (B, Fmax, ldv)."""
+    require_cuda(logits, frame_len)
+    assert logits.dim() == 3 and logits.stride(2) == 1 and logits.shape[2] >= V, f"expected logits [B, F, >= {V}], got {tuple(logits.shape)}"
+    B, fmax, _ = logits.shape
+    ldv = logits.stride(1)
+    assert ldv >= V and logits.stride(0) == fmax * ldv, f"logits rows must lie back to back at one pitch, got strides {logits.stride()}"
+    assert frame_len.dtype == torch.int32 and frame_len.is_contiguous() and tuple(frame_len.shape) == (B,) and frame_len.device == logits.device
+    return B, fmax, ldv
+
+
+def ctc_workspace_bytes(B: int, fmax: int, tmax: int, V: int) -> int:
+    n = lib().query("omr_ctc_workspace_bytes", B, fmax, tmax, V)
+    if n < 0:
+        raise ValueError(f"the CTC loss takes 1 <= B <= 32767, F >= 1 and 1 <= T <= 1023, got B = {B}, F = {fmax}, T = {tmax}")
+    return n
+
+
+def ctc_workspace_lse(ws: Tensor, B: int, fmax: int) -> Tensor:
+    """The frames' log-sum-exp fp32 [B, fmax] inside a workspace omr_ctc_fwd has filled (frames >= F_b are not written): it lies behind the
+    fp64 offsets [2][B][fmax] and log P [2][B], each block rounded up to 16 bytes (csrc/ctc.hip, ctc_ws_layout)."""
+    r16 = lambda n: (n + 15) // 16 * 16  # noqa: E731
+    start = r16(2 * B * fmax * 8) + r16(2 * B * 8)
+    return ws[start:start + B * fmax * 4].view(torch.float32).view(B, fmax)
+
+
+def ctc_fwd(logits: Tensor, frame_len: Tensor, targets: Tensor, V: int, blank: int, eos: int):
+    """F.ctc_loss(log_softmax(logits), ..., blank, reduction="mean", zero_infinity=True) on logits [B, Fmax, ldv >= V]; targets int64 [B, T], each
+    row's labels end in front of its first `blank` or `eos` (omr_ctc_fwd) -> (loss fp32 [1], rows fp32 [B] = the samples' nll, 0 where
+    infeasible, infeasible int32 [1], acc2 fp64 [2], the workspace omr_ctc_bwd reads)."""
+    B, fmax, ldv = _ctc_logits(logits, frame_len, V)
+    require_cuda(targets)
+    assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.dim() == 2 and targets.shape[0] == B
+    T = targets.shape[1]
+    dev = logits.device
+    ws = torch.empty(ctc_workspace_bytes(B, fmax, T, V), dtype=torch.uint8, device=dev)
+    acc2 = torch.empty(2, dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    rows = torch.empty(B, dtype=torch.float32, device=dev)
+    infeasible = torch.empty(1, dtype=torch.int32, device=dev)
+    lib().call("omr_ctc_fwd", dtype_code(logits.dtype), ptr(logits), ldv, ptr(frame_len), ptr(targets), ptr(ws), ptr(acc2), ptr(loss), ptr(rows),
+               ptr(infeasible), B, fmax, T, V, blank, eos, cur_stream())
+    return loss, rows, infeasible, acc2, ws
+
+
+def ctc_bwd(logits: Tensor, frame_len: Tensor, targets: Tensor, ws: Tensor, V: int, blank: int, grad_scale: float = 1.0,
+            grad_out: Optional[Tensor] = None) -> Tensor:
+    """dlogits of ctc_fwd (omr_ctc_bwd), in the logits' dtype and pitch; the view of the logits' own columns is returned."""
+    B, fmax, ldv = _ctc_logits(logits, frame_len, V)
+    require_cuda(targets, ws, grad_out)
+    if grad_out is not None:
+        assert grad_out.dtype == torch.float32 and grad_out.numel() == 1
+    dl = torch.empty((B, fmax, ldv), dtype=logits.dtype, device=logits.device)
+    lib().call("omr_ctc_bwd", dtype_code(logits.dtype), ptr(logits), ldv, ptr(frame_len), ptr(targets), ptr(ws), ptr(dl), B, fmax, targets.shape[1], V,
+               blank, float(grad_scale), ptr(grad_out), cur_stream())
+    return dl[:, :, :logits.shape[2]]
+
+
+def ctc_greedy(logits: Tensor, frame_len: Tensor, V: int, blank: int):
+    """Best-path transcript of logits [B, Fmax, ldv >= V] (omr_ctc_greedy) -> (tokens int32 [B, Fmax], lengths int32 [B], each frame's arg-max
+    column int32 [B, Fmax] and its value fp32 [B, Fmax]), all on the device."""
+    B, fmax, ldv = _ctc_logits(logits, frame_len, V)
+    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=logits.device)  # noqa: E731
+    arg, val, tokens, lengths = new(torch.int32, B, fmax), new(torch.float32, B, fmax), new(torch.int32, B, fmax), new(torch.int32, B)
+    lib().call("omr_ctc_greedy", dtype_code(logits.dtype), ptr(logits), ldv, ptr(frame_len), ptr(arg), ptr(val), ptr(tokens), ptr(lengths), B, fmax, V,
+               blank, cur_stream())
+    return tokens, lengths, arg, val

@@ -19,7 +19,7 @@ from . import functional as Fn
 from . import kernels as K
 from ._lib import lib
 from .config import DistillConfig, ModelConfig
-from .decoder import MAX_BEAM, Decoder, MultiheadAttention, _to_dev, takes_ragged_state
+from .decoder import MAX_BEAM, Decoder, Linear, MultiheadAttention, _to_dev, takes_ragged_state
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
 from .evaluation import (WINDOW_BATCHES, Alignment, active_grammar, active_spec, cells_and_boxes, decode_rows, decode_spec, decode_stream,
                          grammar_option, grid_of, plan_align_groups, plan_groups, plan_pair_groups, refill_enabled, refill_option, spec_option,
@@ -177,6 +177,7 @@ class _Base(FlatModuleMixin, LightningModule):
         self.teacher_forcing_prob = teacher_forcing_prob
         self.attn_window = attn_window
         self.compute_loss = CrossEntropyLoss(ignore_index=self.padding_idx, label_smoothing=self.config.label_smoothing)
+        self.ctc_weight, self.ctc_pool = K.check_ctc(self.config.ctc_weight, self.config.ctc_pool)
         self.Y: List[List[str]] = []
         self.YHat: List[List[str]] = []
 
@@ -221,6 +222,7 @@ class _Base(FlatModuleMixin, LightningModule):
         table = enc.extent_table(sizes, flat.device)
         grid, grid_dev = table.host[-1], table.dev[-1]                            # int32 [B, 2]: each sample's feature grid
         lens = (grid[:, 0].long() * grid[:, 1].long()).tolist()
+        self._memory_grid = (grid_dev, grid)                                      # what the CTC head's frame order needs (Transformer._ctc_logits)
         f = enc.forward_nhwc(x, flat.compute_dtype, extents=table).permute(0, 3, 1, 2)
         f = pos(f).permute(0, 2, 3, 1)                                            # NHWC again (a view of the PE kernel's output)
         mem = Fn.PackMemoryFn.apply(f, grid_dev, max(lens))
@@ -653,12 +655,15 @@ class Transformer(_Base):
         self.pos_2d = PositionalEncoding2D(num_channels=c.d_model, max_height=math.ceil(max_input_height / HEIGHT_REDUCTION),
                                            max_width=math.ceil(max_input_width / WIDTH_REDUCTION), dropout_p=c.dropout)
         self.decoder = self._make_decoder()
+        if self.ctc_weight > 0:        # after the decoder: its parameters close the decoder-side range of the flat buffers (attach_reducer)
+            self.ctc_head = Linear(c.d_model, len(w2i))
 
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         """encoder -> 2-D PE -> flatten -> [B, S, d] (model.py:143-147,176-180)."""
         flat = self.ensure_flat()
         x = x.to(flat.device, non_blocking=True)
         f = self.encoder.forward_nhwc(x, flat.compute_dtype).permute(0, 3, 1, 2)
+        self._memory_grid = (None, (f.shape[2], f.shape[3]))       # every sample's grid is the whole plane
         return self._boundary(_flatten_memory(self.pos_2d(f)))
 
     def _encode_packed(self, x: torch.Tensor, sizes: torch.Tensor) -> Tuple[torch.Tensor, List[int], torch.Tensor]:
@@ -681,11 +686,31 @@ class Transformer(_Base):
         key-padding mask [B, S].  An INTEGER xl of shape [B, 2] -- never a valid memory_len -- holds the (height, width) in pixels
         of each sample's content in the top-left corner of x and takes the ragged route: sample b's logits, loss share and gradients are
         those of b run alone at its own size; the memory rows past a sample's own length are masked out (-inf)."""
+        return self._forward_memory(x, xl, y_in)[0]
+
+    def _forward_memory(self, x: torch.Tensor, xl: torch.Tensor, y_in: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`forward` -> (logits, the memory the decoder read): what `training_step` hands the CTC head."""
         if self._is_pixel_sizes(xl):
             mem, _, lens_dev = self._encode_packed(x, xl)
-            return self.decoder(tgt=y_in, memory=mem, memory_len=_pad_mask(mem.shape[1], lens_dev))     # bool [B, Smax]: True = no key
+            return self.decoder(tgt=y_in, memory=mem, memory_len=_pad_mask(mem.shape[1], lens_dev)), mem     # bool [B, Smax]: True = no key
         mem = self.encode(x)
-        return self.decoder(tgt=y_in, memory=mem, memory_len=xl)     # host-resident ids / lengths go as they are: the decoder reads them before the copy
+        return self.decoder(tgt=y_in, memory=mem, memory_len=xl), mem     # host-resident ids / lengths go as they are: the decoder reads them before the copy
+
+    def _ctc_logits(self, mem: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The CTC head on the memory `encode` / `_encode_packed` returned last: memory -> time-ordered frames (each sample's grid column by
+        column, ctc_pool grid rows averaged per frame) -> head -> (logits [B, F, V] at a row pitch of round_up(V, 8), frame counts int32 [B])."""
+        if self.ctc_weight <= 0:
+            raise ValueError("this model has no CTC head: build it with ModelConfig(ctc_weight > 0)")
+        grid_dev, grid = self._memory_grid
+        if grid_dev is None:
+            gh, gw = grid
+            fmax = K.ctc_frame_count(gh, gw, self.ctc_pool)
+        else:
+            gh = gw = 0
+            fmax = max(K.ctc_frame_count(h, w, self.ctc_pool) for h, w in grid.tolist())
+        frames, frame_len = Fn.CTCFramesFn.apply(mem, grid_dev, gh, gw, self.ctc_pool, fmax)
+        V = len(self.w2i)
+        return Fn.linear(frames, self.ctc_head.weight, self.ctc_head.bias, out_ld=K.round_up(V, 8)), frame_len
 
     _is_pixel_sizes = staticmethod(_is_pixel_sizes)
 
@@ -710,6 +735,8 @@ class Transformer(_Base):
         """Attaches a distill.Distillation (training_step then trains towards its teachers) or, with None, detaches it.  The teachers do not
         become sub-modules.  ValueError when a teacher's vocabulary differs or the model smooths its labels."""
         if distillation is not None:
+            if self.ctc_weight > 0:
+                raise ValueError("distillation and the CTC head do not combine: train with ctc_weight = 0 or without teachers")
             distillation.attach(self)
         self._distillation = distillation
 
@@ -731,12 +758,83 @@ class Transformer(_Base):
             return self._distillation_step(batch)
         x, xl, y_in, y_out = batch
         y_in = self.apply_teacher_forcing(y_in)
+        if self.ctc_weight > 0:
+            return self._ctc_step(x, xl, y_in, y_out)
         yhat = self.forward(x=x, xl=xl, y_in=y_in)
         loss = self.compute_loss(yhat, _to_dev(y_out, yhat.device))
         self.log("train_loss", loss, prog_bar=True, logger=True, on_epoch=True)
         if self.compute_loss.label_smoothing > 0:      # the un-smoothed mean: comparable between runs that smooth differently
             self.log("train_nll", self.compute_loss.last_nll, prog_bar=True, logger=True, on_epoch=True)
         return loss
+
+    last_ctc = None           # (loss, rows [B], infeasible [1]) of the last `_ctc_step`: detached device tensors (no sync)
+
+    def _ctc_step(self, x, xl, y_in, y_out) -> torch.Tensor:
+        """training_step with the CTC head: loss = (1 - w) CE + w CTC, both against y_out (the CTC labels end in front of <eos>), the CTC
+        part on the memory the decoder read.  Label smoothing applies to the CE part only."""
+        yhat, mem = self._forward_memory(x, xl, y_in)
+        y_dev = _to_dev(y_out, yhat.device)
+        ce = self.compute_loss(yhat, y_dev)
+        logits, frame_len = self._ctc_logits(mem)
+        ctc, rows, infeasible = Fn.ctc_loss(logits, frame_len, y_dev, self.padding_idx, self.w2i[EOS_TOKEN])
+        w = self.ctc_weight
+        loss = (1.0 - w) * ce + w * ctc
+        self.last_ctc = (ctc.detach(), rows, infeasible)
+        self.log("train_loss", loss, prog_bar=True, logger=True, on_epoch=True)
+        self.log("train_ce", ce.detach(), prog_bar=True, logger=True, on_epoch=True)
+        self.log("train_ctc", ctc.detach(), prog_bar=True, logger=True, on_epoch=True)
+        self.log("ctc_infeasible", infeasible, prog_bar=False, logger=True, on_epoch=True)
+        if self.compute_loss.label_smoothing > 0:
+            self.log("train_nll", self.compute_loss.last_nll, prog_bar=True, logger=True, on_epoch=True)
+        return loss
+
+    @torch.no_grad()
+    def predict_ctc(self, xs: Iterable[torch.Tensor], batch_size: int = 32) -> List[List[str]]:
+        """The encoder-only transcript of inputs [1, C, H_b, W_b] (or [C, H_b, W_b]) of any size, in input order: batch_size inputs at a time
+        through the ragged batch encoder (`collate_ragged` + `_encode_packed`), the CTC head, and the arg-max path with repeats collapsed and
+        blanks dropped (kernels.ctc_greedy) -- no decoder, no decode loop; the host reads tokens and lengths once per batch."""
+        if self.ctc_weight <= 0:
+            raise ValueError("this model has no CTC head: build it with ModelConfig(ctc_weight > 0)")
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        from .image import collate_ragged
+        was_training = self.training
+        self.eval()
+        out: List[List[str]] = []
+        try:
+            it = iter(xs)
+            while True:
+                group = [x[0] if x.dim() == 4 else x for x in itertools.islice(it, batch_size)]
+                if not group:
+                    break
+                x, sizes = collate_ragged(group)
+                mem, _, _ = self._encode_packed(x, sizes)
+                logits, frame_len = self._ctc_logits(mem)
+                tokens, lengths, _, _ = K.ctc_greedy(logits, frame_len, len(self.w2i), self.padding_idx)
+                tokens, lengths = tokens.cpu(), lengths.cpu().tolist()
+                out.extend(self._words([tokens[b, :n].tolist() for b, n in enumerate(lengths)]))
+        finally:
+            self.train(was_training)
+        return out
+
+    @torch.no_grad()
+    def evaluate_ctc(self, batches: Iterable, batch_size: int = 32) -> Dict[str, float]:
+        """The metrics of `evaluate` (sym-er / seq-er) with `predict_ctc`'s transcripts as predictions.  The truth of a batch ends in front
+        of its <eos>: the CTC path emits none."""
+        if self.ctc_weight <= 0:
+            raise ValueError("this model has no CTC head: build it with ModelConfig(ctc_weight > 0)")
+        truth: List[List[str]] = []
+
+        def inputs():
+            for batch in batches:
+                y = batch[-1]
+                assert y.size(0) == 1, "evaluate_ctc takes the batches of validation_step (batch_size = 1)"
+                words = [self.ytest_i2w[i] for i in y[0][1:].tolist()]
+                truth.append(words[:words.index(EOS_TOKEN)] if EOS_TOKEN in words else words)
+                yield batch[0]
+
+        preds = self.predict_ctc(inputs(), batch_size)
+        return compute_metrics(y_true=truth, y_pred=preds)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx) -> None:
@@ -852,6 +950,9 @@ class MultimodalTransformer(_Base):
         super().__init__()
         self.save_hyperparameters()
         self._common_init(w2i, i2w, ytest_i2w, max_seq_len, attn_window, teacher_forcing_prob, config)
+        if self.ctc_weight > 0:
+            raise ValueError("the CTC head reads ONE feature grid as a frame sequence: ctc_weight > 0 is for Transformer, not the mixed memory "
+                             "of MultimodalTransformer")
         self.max_img_height, self.max_img_width = max_img_height, max_img_width
         self.max_audio_height, self.max_audio_width = max_audio_height, max_audio_width
         self.teacher_forcing_modality_prob = teacher_forcing_modality_prob
