@@ -806,6 +806,67 @@ int omr_ctc_bwd(int dtype, const void* logits, long ldv, const int* frame_len, c
 int omr_ctc_greedy(int dtype, const void* logits, long ldv, const int* frame_len, int* frame_arg, float* frame_val, int* tokens, int* lengths,
                    int B, int Fmax, int V, int blank_idx, void* stream);
 
+/* ---- joint CTC / attention beam search (csrc/ctc_prefix.hip; an extension: Watanabe et al.'s decoding half of the CTC head) ---- */
+/* The CTC prefix score.  Per input n with F_n frames (frame_len[n] clamped into [0, Fmax]), y_f(v) = (float)logits[n][f][v] - lse[n][f] (fp32,
+ * one subtraction; lse from the row pass of omr_ctc_fwd, run once by omr_ctc_prefix_init).  A hypothesis g (the tokens behind <sos>) of row
+ * r = n * beam + k holds two fp32 log-space rows of F_n entries and two scalars:
+ *   gn[f] / gb[f]   log P(frames 0..f emit exactly g, the last frame a label / a blank);  empty g: gn = -inf, gb[f] = y_0(blank) + .. + y_f(blank)
+ *   logpsi          log P(the frames emit something that starts with g): 0 for the empty g;     last: g's last token (sos: g is empty)
+ * A label c (not blank, sos, eos; 0 <= c < V) extends g to h = g c -- log-add la(a, b) = max + log1pf(expf(min - max)), -inf for two -inf:
+ *   phi[f]  = la(gb^g[f], c == last(g) ? -inf : gn^g[f]),   phi[-1] = g empty ? 0 : -inf
+ *   gn^h[f] = la(gn^h[f-1], phi[f-1]) + y_f(c),   gb^h[f] = la(gb^h[f-1], gn^h[f-1]) + y_f(blank),   gn^h[-1] = gb^h[-1] = -inf
+ *   logpsi(h) = log sum_f exp(phi[f-1] + y_f(c)), summed 8 frames at a time in frame order around a running maximum (m, s):
+ *               cm = max(m, the 8 terms); s = s * expf(m - cm) + expf(term_0 - cm) + .. + expf(term_7 - cm); m = cm; logpsi = m + logf(s)
+ * c == eos: logpsi = la(gn^g[F-1], gb^g[F-1]) (F_n = 0: 0 for the empty g, else -inf).  Any other c (blank, sos, outside [0, V)): -inf.
+ *   delta(g, c) = logpsi(g c) == -inf ? -inf : min(logpsi(g c) - logpsi(g), 0)
+ * Plain fp32 log space, every operation rounded on its own (the file is built without contraction); the score, the advance and the selection
+ * run ONE row body, so a survivor's stored logpsi has the bits its candidate's had, and the batched and the per-input route agree to the bit.
+ * No atomics: two runs give the same bits.
+ * omr_ctc_beam_desc: N inputs x beam rows.  logits [N][Fmax][ldv >= V] (dtype fp32 / bf16), frame_len int32 [N], lambda the CTC weight.
+ * Everything from `ws` on is carved out of ONE block `ws` of omr_ctc_beam_workspace_bytes bytes:
+ *   lse fp32 [N][Fmax];  state[p] fp32 [rows][2][Fmax] (gn row, gb row) for the two parities p;  last[p] int32 [rows];  logpsi fp32 [rows];
+ *   cand_tok int64 / cand_val fp32 [N][beam * beam]: scratch of omr_beam_select_ctc (each row's top-`beam` tokens, their mixed values);
+ *   advanced int32 [N]: the omr_ctc_prefix_advance launches that took input n since omr_ctc_prefix_init.  In a search that is the position at
+ *   which the input stopped; the host needs it where an input stops with nothing finished (every candidate at -inf: no label fits the frames
+ *   left and <eos> is not among the attention's candidates) -- its result is then row 0 of the last position it survived.
+ * Position t reads parity t & 1 and omr_ctc_prefix_advance writes the other one. */
+typedef struct omr_ctc_beam_desc {
+    int dtype, N, beam, V, Fmax, blank, sos, eos;
+    long ldv;
+    float lambda;
+    const void* logits; const int* frame_len;
+    void* ws; long ws_bytes;
+    float* lse; float* state[2]; int* last[2]; float* logpsi; long* cand_tok; float* cand_val; int* advanced;
+} omr_ctc_beam_desc;
+/* Bytes of the block for desc->{N, beam, Fmax}; also points the fields behind ws_bytes into desc->ws (NULL: offsets).  OMR_ERR_ARG: N or
+ * Fmax < 1, beam outside 1..OMR_MAX_BEAM. */
+long omr_ctc_beam_workspace_bytes(omr_ctc_beam_desc* desc);
+/* Once per search, before position 0: the frames' lse, then every row's parity-0 state = the empty hypothesis (gb by fp32 additions in frame
+ * order, logpsi = 0, last = sos).  Refused with OMR_ERR_ARG before the first launch, like every entry below that takes the descriptor: a NULL
+ * pointer, fields that are not the ones omr_ctc_beam_workspace_bytes set, lambda outside (0, 1), beam outside 1..OMR_MAX_BEAM, V < 1, ldv < V,
+ * blank / sos / eos outside [0, V) or two of them equal; OMR_ERR_UNSUPPORTED: a dtype other than fp32 / bf16. */
+int omr_ctc_prefix_init(const omr_ctc_beam_desc* desc, void* stream);
+/* delta[r][j] (fp32 [rows][beam]) of candidate cand[r][j] (int64 [rows][beam]) against the hypothesis of row r in the parity `parity` state.
+ * One workgroup per input, one candidate per lane of the scanning wave; nothing is written but delta.  Also refused: parity outside {0, 1}. */
+int omr_ctc_prefix_scores(const omr_ctc_beam_desc* desc, int parity, const long* cand, float* delta, void* stream);
+/* New row i of input n continues row parents[n * beam + i] (int32, LOCAL, clamped into 0..beam-1) of the parity `parity` state by the label
+ * tokens[n * beam + i] (int64): its gn / gb rows, logpsi and last go into the OTHER parity (logpsi is shared: the advance does not read it).
+ * scores (nullable, fp64 [rows]): rows of -inf (the dead padding of a selection) are skipped; done (nullable, int32 [N]): inputs that are done
+ * are skipped.  A token that is no label leaves its row untouched.  The row body is the score's, with stores. */
+int omr_ctc_prefix_advance(const omr_ctc_beam_desc* desc, int parity, const int* parents, const long* tokens, const double* scores,
+                           const int* done, void* stream);
+/* omr_beam_select with the CTC prefix score (the loop body of _Base.beam_search with ctc_decode, model.py of this package), three launches:
+ * (1) phase 1 of omr_beam_select: each live input's beam * beam candidates (token, fp32 log-softmax value) -> cand_tok / cand_val;
+ * (2) the score kernel over the parity t & 1 state: cand_val = fl(fl(wa * value) + fl(wc * delta)), wc = lambda, wa = (float)(1 - (double)lambda);
+ * (3) omr_beam_select's phase 2 on those values, by the same code: fp64 scores, order, walk, finished record, stop rule, padding.
+ * The CTC re-ranks inside the attention's candidate list; it does not widen it.  The state is not advanced (omr_ctc_prefix_advance).
+ * Also refused: V != ctc->V, N or beam differing between the descriptors, eos differing. */
+int omr_beam_select_ctc(const float* logits, long ld, int V, const omr_beam_desc* beam_desc, const omr_ctc_beam_desc* ctc, int t, void* stream);
+/* omr_beam_decode_steps with omr_beam_select_ctc as the selection and, behind it, omr_ctc_prefix_advance over beam_desc's parents / tokens /
+ * scores / done; then the cache reorder.  A run starts at position 0 behind omr_ctc_prefix_init.  Also refused: desc->V != ctc->V. */
+int omr_beam_decode_steps_ctc(const omr_decode_desc* desc, const omr_beam_desc* beam_desc, const omr_ctc_beam_desc* ctc, const int* mem_len,
+                              int t0, int n_steps, void* stream);
+
 /* ---- guarded optimizer step ------------------------------------------------------------------------------- */
 /* What the reference gets from Lightning: Trainer(precision="16-mixed") (src/train.py:153) puts every step behind GradScaler,
  * which skips optimizer.step() when a gradient holds inf / NaN (torch/amp/grad_scaler.py, _maybe_opt_step), and

@@ -19,7 +19,7 @@
 // block sum over the blank states) and off each distinct label's column: the thread of a label's FIRST occurrence walks the sample's
 // "next state with this label" chain (ctc_prep_kernel) and adds in state order.  No float atomics anywhere.
 #include "dma_common.h"
-#include "loss_rows.h"
+#include "ctc_rows.h"
 #include "omr_hip.h"
 
 namespace {
@@ -104,22 +104,6 @@ __global__ __launch_bounds__(256) void ctc_frames_bwd_kernel(const T* __restrict
 
 // ------------------------------------------------------------------------------------------------ loss
 
-__device__ __forceinline__ int clamp_len(int n, int Fmax) { return min(max(n, 0), Fmax); }
-
-// One workgroup per frame: the row pass of ce_fwd_kernel (loss_rows.h).  Frames >= F_b are skipped.
-template <typename T>
-__global__ __launch_bounds__(256) void ctc_lse_kernel(const T* __restrict__ logits, const int* __restrict__ frame_len, float* __restrict__ lse, int Fmax,
-                                                      int V, long ldv) {
-    __shared__ float red_m[4], red_s[4];
-    const int b = blockIdx.y, f = blockIdx.x;
-    if (f >= clamp_len(frame_len[b], Fmax)) return;
-    const long row = (long)b * Fmax + f;
-    float mx = -INFINITY, s = 0.f, rs = 0.f;
-    row_online_pass<T, false>(logits + row * ldv, row_vec_ok<T>(logits, ldv), V, mx, s, rs);
-    const float l = block_lse(mx, s, 1.f, red_m, red_s);
-    if (threadIdx.x == 0) lse[row] = l;
-}
-
 // One workgroup per sample: L_b, and for every label index the next one with the same label / whether it is the first with it.
 __global__ __launch_bounds__(256) void ctc_prep_kernel(const long* __restrict__ tgt, int* __restrict__ len, int* __restrict__ next, int* __restrict__ first,
                                                        int T, int V, int blank, int eos) {
@@ -151,10 +135,6 @@ __global__ __launch_bounds__(256) void ctc_prep_kernel(const long* __restrict__ 
     if (tid == 0) len[b] = L;
 }
 
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float m = fmaxf(a, b);
-    return m == -INFINITY ? -INFINITY : m + log1pf(expf(fminf(a, b) - m));
-}
 __device__ __forceinline__ float lse3(float a, float b, float c) {
     const float m = fmaxf(fmaxf(a, b), c);
     return m == -INFINITY ? -INFINITY : m + logf(expf(a - m) + expf(b - m) + expf(c - m));

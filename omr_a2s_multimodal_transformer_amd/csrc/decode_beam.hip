@@ -109,6 +109,36 @@ __global__ __launch_bounds__(256 * BEAM_GROUPS) void beam_select_kernel(const fl
     beam_rank_and_put(bd, n, t, c_val, c_tok);
 }
 
+// beam_select_kernel as two launches, for a selection that re-scores the candidates in between (omr_beam_select_ctc: the CTC prefix
+// scores of ctc_prefix.hip scan thousands of frames with one wave per input).  Phase 1 alone: input n's candidates (token, value) go to
+// g_tok / g_val [N][beam * beam] in the order c_tok / c_val have in LDS above.
+__global__ __launch_bounds__(256 * BEAM_GROUPS) void beam_topk_kernel(const float* __restrict__ logits, long ld, int V, omr_beam_desc bd,
+                                                                      long* __restrict__ g_tok, float* __restrict__ g_val) {
+    __shared__ float sv[BEAM_GROUPS][256];
+    __shared__ int si[BEAM_GROUPS][256];
+    const int n = blockIdx.x, beam = bd.beam, row0 = n * beam;
+    if (bd.done[n]) return;                         // frozen (uniform over the workgroup)
+    const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
+    const long c0 = (long)row0 * beam;
+    for (int k0 = 0; k0 < beam; k0 += BEAM_GROUPS) {
+        const int k = k0 + g;
+        const bool real = k < beam;                 // a group without a row walks an empty one: the barriers stay uniform
+        topk_logprob_row(logits + (long)(row0 + (real ? k : 0)) * ld, real ? V : 0, beam, tid, sv[g], si[g], [&](int j, int idx, float val) {
+            if (tid == 0 && real) { g_tok[c0 + k * beam + j] = idx; g_val[c0 + k * beam + j] = val; }
+        });
+    }
+}
+
+// Phase 2 alone, one wave per input: the candidates come back from g_tok / g_val and go through beam_rank_and_put.
+__global__ __launch_bounds__(64) void beam_rank_kernel(const long* __restrict__ g_tok, const float* __restrict__ g_val, omr_beam_desc bd, int t) {
+    __shared__ float c_val[64];
+    __shared__ int c_tok[64];
+    const int n = blockIdx.x, nc = bd.beam * bd.beam, lane = threadIdx.x;
+    if (bd.done[n]) return;                         // frozen (uniform over the workgroup)
+    if (lane < nc) { c_tok[lane] = (int)g_tok[(long)n * nc + lane]; c_val[lane] = g_val[(long)n * nc + lane]; }
+    beam_rank_and_put(bd, n, t, c_val, c_tok);      // its first barrier orders the two arrays
+}
+
 // beam_select_kernel over the weighted late fusion of two models (an extension: the reference decodes greedily,
 // weighted_multimodal/test.py:50-61): phase 1 ranks wa * softmax(la) + wb * softmax(lb) of each row pair
 // (weighted_topk_logprob_row, the row body of omr_weighted_topk_logprob); phase 2 is the same.
@@ -247,6 +277,16 @@ void launch_select(const float* logits, long ld, int V, const omr_beam_desc& b, 
     else hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)b.N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, logits, ld, V, b, t);
 }
 
+// The selection with the CTC prefix score (include/omr_hip.h, omr_beam_select_ctc): top-k, score + mix over the parity t & 1 state, rank.
+void launch_select_ctc(const float* logits, long ld, int V, const omr_beam_desc& b, const omr_ctc_beam_desc& c, int t, void* stream) {
+    hipLaunchKernelGGL(beam_topk_kernel, dim3((unsigned)b.N), dim3(256 * BEAM_GROUPS), 0, (hipStream_t)stream, logits, ld, V, b, c.cand_tok, c.cand_val);
+    launch_prefix_scores(c, t & 1, c.cand_tok, b.scores, b.done, c.cand_val, c.cand_val, stream);
+    hipLaunchKernelGGL(beam_rank_kernel, dim3((unsigned)b.N), dim3(64), 0, (hipStream_t)stream, (const long*)c.cand_tok, (const float*)c.cand_val, b, t);
+}
+
+// a CTC descriptor ctc_beam_desc_check took against the search it scores for
+bool ctc_fits_beam(const omr_ctc_beam_desc& c, const omr_beam_desc& b, int V) { return c.V == V && c.N == b.N && c.beam == b.beam && c.eos == b.eos; }
+
 struct LogitRows { const float* logits; long ld; };
 void launch_weighted_select(LogitRows a, LogitRows b, int V, float alpha, const omr_beam_desc& bd, const omr_grammar_desc* g, int t, void* stream) {
     const float wb = (float)(1.0 - (double)alpha);                           // the weights as omr_weighted_argmax_rows rounds them
@@ -370,6 +410,30 @@ extern "C" int omr_beam_decode_steps(const omr_decode_desc* dp, const omr_beam_d
 extern "C" int omr_weighted_beam_decode_steps(const omr_decode_desc* da, const int* mem_len_a, const omr_decode_desc* db, const int* mem_len_b,
                                               const omr_beam_desc* bp, void* self_kv2_b, float alpha, int t0, int n_steps, void* stream) {
     return weighted_beam_decode(da, mem_len_a, db, mem_len_b, bp, self_kv2_b, nullptr, alpha, t0, n_steps, stream);
+}
+
+/* The selection and the decode with the CTC prefix score (include/omr_hip.h "joint CTC / attention beam search"; extensions of the host
+ * loop _Base.beam_search of this package's model.py).  The state advances behind the selection of a position: survivors read their parents'
+ * rows of parity t & 1 and write their own of the other. */
+extern "C" int omr_beam_select_ctc(const float* logits, long ld, int V, const omr_beam_desc* bp, const omr_ctc_beam_desc* cp, int t, void* stream) {
+    OMR_TRY(ctc_beam_desc_check(cp));
+    if (!logits || !bp || !beam_desc_ok(*bp)) return OMR_ERR_ARG;
+    if (!beam_fits_vocab(*bp, V) || !ctc_fits_beam(*cp, *bp, V) || ld < V || t < 0 || t >= bp->max_len) return OMR_ERR_ARG;
+    launch_select_ctc(logits, ld, V, *bp, *cp, t, stream);
+    OMR_CHECK_LAUNCH();
+    return OMR_OK;
+}
+
+extern "C" int omr_beam_decode_steps_ctc(const omr_decode_desc* dp, const omr_beam_desc* bp, const omr_ctc_beam_desc* cp, const int* mem_len, int t0,
+                                         int n_steps, void* stream) {
+    OMR_TRY(ctc_beam_desc_check(cp));
+    if (!dp || !bp || bp->max_len != dp->max_len || !ctc_fits_beam(*cp, *bp, dp->V)) return OMR_ERR_ARG;
+    const BeamModel bm = {dp, mem_len, bp->self_kv2};
+    auto select = [&](float* const* l32, int t) {
+        launch_select_ctc(l32[0], (long)dp->ldv, dp->V, *bp, *cp, t, stream);
+        launch_prefix_advance(*cp, t & 1, bp->parents, bp->tokens, bp->scores, bp->done, stream);
+    };
+    return beam_steps(&bm, 1, *bp, t0, n_steps, select, stream);
 }
 
 /* The same four under a token automaton (include/omr_hip.h "grammar-constrained decoding"; extensions of the host loop

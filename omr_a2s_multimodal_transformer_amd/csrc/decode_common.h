@@ -1,5 +1,6 @@
 // What crosses the three decode translation units: decode_linear.hip (the row kernel and its launch), decode.hip (workspace,
 // the position executor, the greedy and weighted-greedy entries) and decode_beam.hip (selection, reorder, the beam entries).
+// ctc_prefix.hip (the CTC prefix score of the joint beam search) hands decode_beam.hip its two launches through here too.
 #pragma once
 #include "omr_common.h"
 #include "omr_hip.h"
@@ -62,5 +63,15 @@ int verify_rows(const omr_decode_desc* d, const int* mem_len, const int* pos, in
 // token each row feeds in (device int64 [B]).  *logits32: where the position's fp32 logits [B][ldv] lie in the workspace.
 int run_position(const Model& m, const Position& p, const long* tok_in, Pick pick, float** logits32, void* stream);
 int copy_logits(const Model& m, float* dst, const float* logits32, void* stream);      // [B][ldv] fp32, device to device, async
+
+
+// ---- ctc_prefix.hip: the CTC prefix score of the joint beam search (decode_beam.hip launches it between its own two phases)
+int ctc_beam_desc_check(const omr_ctc_beam_desc* c);                    // every descriptor check, once
+// out[r][j] over cand [rows][beam] against the parity state: delta, or with att_val the mix fl(fl(wa * att_val) + fl(wc * delta));
+// scores / done (nullable): dead rows' candidates get -inf, done inputs nothing
+void launch_prefix_scores(const omr_ctc_beam_desc& c, int parity, const long* cand, const double* scores, const int* done, const float* att_val,
+                          float* out, void* stream);
+void launch_prefix_advance(const omr_ctc_beam_desc& c, int parity, const int* parents, const long* tokens, const double* scores, const int* done,
+                           void* stream);
 
 }  // namespace omr_dec

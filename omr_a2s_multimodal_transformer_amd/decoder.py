@@ -926,13 +926,13 @@ class BeamSearchBlock:
             out[n] = self._view(host, n, np.int32, self.max_len * rows).reshape(self.max_len, rows)
         return out
 
-    def results(self, positions: int):
+    def results(self, positions: int, dead_end=None):
         """-> [(token ids, score)] per input after `positions` positions: what the host loop finds for that input alone
-        (evaluation.beam_results)."""
+        (evaluation.beam_results; dead_end: as there)."""
         from .evaluation import beam_results
         s = self.snapshot()
         return beam_results(self.beam, positions, int(self.bdesc.eos), s["scores"], s["best_score"], s["best_row"], s["best_pos"], s["done"],
-                            s["hist_parent"], s["hist_token"])
+                            s["hist_parent"], s["hist_token"], dead_end)
 
 
 class BeamDecodeState(DecodeState):
@@ -953,11 +953,30 @@ class BeamDecodeState(DecodeState):
     def share_memory_between(self, rows: int) -> None:
         raise RuntimeError("share_memory_between: a beam decode state already shares each memory between its hypotheses")
 
+    ctc = None             # kernels.CtcPrefixBlock: the CTC prefix scores the selection mixes in (None: attention scores alone)
+
+    def attach_ctc(self, logits: torch.Tensor, frame_len: torch.Tensor, weight: float):
+        """The analogue of `constrain` for the joint CTC / attention search, called once before position 0: logits [N, Fmax, >= V] of the CTC
+        head (input n's frames in rows [0, frame_len[n])), frame_len int32 [N], weight the CTC share of every candidate's value.  Allocates the
+        prefix-score block and runs the frames' lse pass (omr_ctc_prefix_init); run() then issues omr_beam_decode_steps_ctc."""
+        from .kernels import CtcPrefixBlock
+        if self.t != 0:
+            raise RuntimeError("attach_ctc: the search has started")
+        if self.gstate is not None:
+            raise ValueError("the CTC prefix score does not combine with a grammar")
+        if logits.dim() != 3 or logits.shape[0] != self.N:
+            raise ValueError(f"attach_ctc: logits of {tuple(logits.shape)} for {self.N} inputs")
+        self.ctc = CtcPrefixBlock(logits, frame_len, self.V, self.beam, blank=self.dec.padding_idx, sos=self.sos, eos=self.eos, weight=weight)
+        return self.ctc
+
     def run(self, n_steps: int) -> None:                   # noqa: D401 -- positions t .. t + n_steps - 1, nothing returned
         """Run n_steps positions of every input (decode step, selection, cache reorder) without a host round trip."""
         if n_steps < 1 or self.t + n_steps > self.max_len:
             raise RuntimeError("beam decode beyond max_seq_len (positional-encoding table exhausted)")
-        if self.gstate is not None:
+        if self.ctc is not None:
+            lib().call("omr_beam_decode_steps_ctc", ctypes.byref(self.desc), ctypes.byref(self.bdesc), self.ctc.byref(), ptr(self.mem_len), self.t,
+                       n_steps, cur_stream())
+        elif self.gstate is not None:
             lib().call("omr_beam_decode_steps_grammar", ctypes.byref(self.desc), ctypes.byref(self.bdesc), ptr(self.mem_len), self.gstate.byref(), self.t,
                        n_steps, cur_stream())
         else:
@@ -975,7 +994,7 @@ class BeamDecodeState(DecodeState):
 
     def results(self):
         """-> [(token ids, score)] per input, what _Base.beam_search finds for that input alone (evaluation.beam_results)."""
-        return self.search.results(self.t)
+        return self.search.results(self.t, None if self.ctc is None else self.ctc.advanced().cpu().tolist())
 
 
 class WeightedBeamState:

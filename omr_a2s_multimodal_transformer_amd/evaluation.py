@@ -158,6 +158,69 @@ def no_draft_option(fn):
     return call
 
 
+_CTC_DECODE = contextvars.ContextVar("omr_ctc_decode", default=None)
+
+
+def active_ctc_decode() -> Optional[float]:
+    """The CTC weight of the joint CTC / attention beam search the call under way asked for (`ctc_decode_option`), or None: the beam
+    search ranks by the attention log-probabilities alone."""
+    return _CTC_DECODE.get()
+
+
+def check_ctc_decode_call(model, weight, beam, others: dict) -> float:
+    """Every refusal of `ctc_decode=`, before anything is encoded -> the weight."""
+    from .decoder import MAX_BEAM
+    from .kernels import check_ctc_decode
+    weight = check_ctc_decode(weight)
+    if hasattr(model, "image_encoder"):
+        raise ValueError("ctc_decode= is for Transformer: the CTC head reads ONE feature grid as a frame sequence, not the mixed memory of "
+                         "MultimodalTransformer")
+    if getattr(model, "ctc_weight", 0.0) <= 0:
+        raise ValueError("ctc_decode= needs the CTC head: build the model with ModelConfig(ctc_weight > 0)")
+    if isinstance(beam, bool) or not isinstance(beam, int) or not 2 <= beam <= MAX_BEAM:
+        raise ValueError(f"ctc_decode= re-ranks the candidates of a beam search: beam must be an integer in 2..{MAX_BEAM}, got {beam!r}")
+    if others.get("grammar", None) is not None or getattr(model, "decode_grammar", None) is not None and "grammar" not in others:
+        raise ValueError("ctc_decode= does not combine with a grammar (grammar= or decode_grammar) yet")
+    if others.get("refill", False):
+        raise ValueError("ctc_decode= does not combine with refill=True: refill decodes greedily")
+    if others.get("draft", None) is not None:
+        raise ValueError("ctc_decode= does not combine with draft=: speculative decoding is greedy")
+    return weight
+
+
+def ctc_decode_option(beam_default: int, beam_at: Optional[int] = None):
+    """Gives a decode entry point of a model the keyword `ctc_decode` (the CTC weight, strictly between 0 and 1; None: off), like
+    `grammar_option`: the function's own parameter list stays as it is, and the weight holds for the duration of the call; `beam_search`
+    and the batched beam state ask `active_ctc_decode`.  It is the outermost option, so it sees -- without consuming them -- the `beam`,
+    `grammar`, `refill` and `draft` keywords it checks (`check_ctc_decode_call`).  beam_default: the beam of a call that names none;
+    beam_at: where a positional beam sits behind `self`.  Without the keyword nothing is allocated or launched."""
+    def wrap(fn):
+        @functools.wraps(fn)
+        def call(self, *args, ctc_decode=None, **kwargs):
+            if ctc_decode is None:
+                return fn(self, *args, **kwargs)
+            beam = args[beam_at] if beam_at is not None and len(args) > beam_at else kwargs.get("beam", beam_default)
+            token = _CTC_DECODE.set(check_ctc_decode_call(self, ctc_decode, beam, kwargs))
+            try:
+                return fn(self, *args, **kwargs)
+            finally:
+                _CTC_DECODE.reset(token)
+        return call
+    return wrap
+
+
+def no_ctc_decode_option(fn):
+    """For the late-fusion entry points, like `no_draft_option`: `ctc_decode=` is refused with ValueError before anything is encoded -- two
+    models decode in lock-step there, and a CTC score for the pair is a later change.  ctc_decode=None passes."""
+    @functools.wraps(fn)
+    def call(*args, ctc_decode=None, **kwargs):
+        if ctc_decode is not None:
+            raise ValueError(f"{fn.__name__} does not take ctc_decode=: the joint CTC / attention search covers beam_search / beam_search_batch / "
+                             "predict / evaluate of one Transformer")
+        return fn(*args, **kwargs)
+    return call
+
+
 def plan_groups(lengths: Sequence[int], batch_size: int, window: int = 0) -> Tuple[List[int], List[List[int]]]:
     """-> (singles, groups) over the indices of `lengths` (memory lengths in tokens).  singles: memories decoded alone at batch
     size 1 -- at most MIN_RAGGED_MEMORY tokens (such a row alone takes another attention kernel than the ragged batch) or
@@ -345,12 +408,14 @@ def beam_backtrack(hist_parent, hist_token, row: int, position: int) -> List[int
 
 
 def beam_results(beam: int, positions: int, eos: int, scores, best_score, best_row, best_pos, done, hist_parent,
-                 hist_token) -> List[Tuple[List[int], float]]:
+                 hist_token, dead_end=None) -> List[Tuple[List[int], float]]:
     """(token ids, score) of every input of a batched beam search from its device state read back (BeamDecodeState.snapshot;
     rows n * beam .. n * beam + beam - 1 belong to input n), after `positions` positions.  The finished hypothesis
     (best_score, best_row, best_pos) is the prefix of row best_row before position best_pos, plus <eos>.  An input that is not
     done ran out of positions: its best unfinished hypothesis (row 0) wins iff its score is greater than the best finished
-    one -- the last two lines of _Base.beam_search."""
+    one -- the last two lines of _Base.beam_search.  dead_end (the joint CTC / attention search only: per input the position at which it
+    stopped): an input that is done with nothing finished met candidates of -inf alone; its result is row 0 of the last position it
+    survived, whose score its frozen state still holds."""
     out: List[Tuple[List[int], float]] = []
     for n in range(len(best_score)):
         r0 = n * beam
@@ -361,6 +426,8 @@ def beam_results(beam: int, positions: int, eos: int, scores, best_score, best_r
             seq = beam_backtrack(hp, ht, int(best_row[n]), int(best_pos[n])) + [eos]
         if not done[n] and float(scores[r0]) > score:
             score, seq = float(scores[r0]), beam_backtrack(hp, ht, 0, positions)
+        if seq is None and dead_end is not None and done[n]:
+            score, seq = float(scores[r0]), beam_backtrack(hp, ht, 0, int(dead_end[n]))
         if seq is None:
             raise RuntimeError(f"beam search: input {n} has neither a finished nor a live hypothesis")
         out.append((seq, score))

@@ -1249,3 +1249,99 @@ def ctc_greedy(logits: Tensor, frame_len: Tensor, V: int, blank: int):
     lib().call("omr_ctc_greedy", dtype_code(logits.dtype), ptr(logits), ldv, ptr(frame_len), ptr(arg), ptr(val), ptr(tokens), ptr(lengths), B, fmax, V,
                blank, cur_stream())
     return tokens, lengths, arg, val
+
+
+# ------------------------------------------------------------------------------------------------ CTC prefix scores (csrc/ctc_prefix.hip)
+
+def check_ctc_decode(weight) -> float:
+    """The range of `ctc_decode` (the CTC weight of the joint beam search): a number strictly between 0 and 1, also as the fp32 the kernels mix
+    with; refused here, before anything is encoded, allocated or launched."""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)):
+        raise ValueError(f"ctc_decode must be a number, got {weight!r}")
+    weight = float(weight)
+    lam32 = ctypes.c_float(weight).value
+    if not (0.0 < weight < 1.0 and 0.0 < lam32 < 1.0):
+        raise ValueError(f"ctc_decode must lie strictly between 0.0 and 1.0, got {weight}")
+    return weight
+
+
+def ctc_mix_weights(weight: float) -> Tuple[float, float]:
+    """(wa, wc) as omr_beam_select_ctc rounds them: wc = (float)weight, wa = (float)(1 - (double)wc); both exactly representable in fp32."""
+    wc = ctypes.c_float(weight).value
+    return ctypes.c_float(1.0 - wc).value, wc
+
+
+class _CtcBeamDesc(ctypes.Structure):
+    """omr_ctc_beam_desc of include/omr_hip.h."""
+    WS_FIELDS = ("lse", "state0", "state1", "last0", "last1", "logpsi", "cand_tok", "cand_val", "advanced")
+    _fields_ = [(n, ctypes.c_int) for n in ("dtype", "N", "beam", "V", "Fmax", "blank", "sos", "eos")] + [("ldv", ctypes.c_long), ("lam", ctypes.c_float)] + [
+        (n, ctypes.c_void_p) for n in ("logits", "frame_len", "ws")] + [("ws_bytes", ctypes.c_long)] + [(n, ctypes.c_void_p) for n in WS_FIELDS]
+
+
+class CtcPrefixBlock:
+    """The CTC side of a joint beam search over N inputs of `beam` rows each (include/omr_hip.h, omr_ctc_beam_desc): the head's logits
+    [N, Fmax, >= V] (kept alive here), one device block with the frames' lse, the two parities of the hypotheses' gn / gb rows, their last
+    tokens and logpsi, and the descriptor.  Creating it runs omr_ctc_prefix_init: every row holds the empty hypothesis in parity 0."""
+
+    def __init__(self, logits: Tensor, frame_len: Tensor, V: int, beam: int, blank: int, sos: int, eos: int, weight: float):
+        self.weight = check_ctc_decode(weight)
+        N, fmax, ldv = _ctc_logits(logits, frame_len, V)
+        self.N, self.beam, self.rows, self.fmax, self.V = N, beam, N * beam, fmax, V
+        self.logits, self.frame_len = logits, frame_len
+        d = self.desc = _CtcBeamDesc()
+        d.dtype, d.N, d.beam, d.V, d.Fmax, d.blank, d.sos, d.eos = dtype_code(logits.dtype), N, beam, V, fmax, blank, sos, eos
+        d.ldv, d.lam, d.logits, d.frame_len, d.ws = ldv, self.weight, logits.data_ptr(), frame_len.data_ptr(), None
+        nbytes = lib().query("omr_ctc_beam_workspace_bytes", ctypes.byref(d))
+        if nbytes <= 0:
+            raise ValueError(f"the CTC prefix state takes N >= 1, Fmax >= 1 and 1 <= beam <= 8, got N = {N}, Fmax = {fmax}, beam = {beam}")
+        self._off = {n: int(getattr(d, n) or 0) for n in _CtcBeamDesc.WS_FIELDS}          # ws == NULL: the fields are offsets
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+        d.ws, d.ws_bytes = self.ws.data_ptr(), nbytes
+        if lib().query("omr_ctc_beam_workspace_bytes", ctypes.byref(d)) != nbytes:
+            raise RuntimeError("libomr_hip: omr_ctc_beam_workspace_bytes changed its answer")
+        lib().call("omr_ctc_prefix_init", ctypes.byref(d), cur_stream())
+
+    def byref(self):
+        return ctypes.byref(self.desc)
+
+    def _view(self, name: str, dtype: torch.dtype, *shape: int) -> Tensor:
+        n = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
+        return self.ws[self._off[name]:self._off[name] + n].view(dtype).view(*shape)
+
+    def lse(self) -> Tensor:
+        """fp32 [N, Fmax] (frames >= F_n are not written)."""
+        return self._view("lse", torch.float32, self.N, self.fmax)
+
+    def state(self, parity: int) -> Tensor:
+        """fp32 [rows, 2, Fmax]: every row's gn and gb of that parity (a view of the block)."""
+        return self._view(f"state{parity}", torch.float32, self.rows, 2, self.fmax)
+
+    def last(self, parity: int) -> Tensor:
+        return self._view(f"last{parity}", torch.int32, self.rows)
+
+    def logpsi(self) -> Tensor:
+        return self._view("logpsi", torch.float32, self.rows)
+
+    def advanced(self) -> Tensor:
+        """int32 [N]: the advances that took each input since the block was initialised (in a search: the position at which it stopped)."""
+        return self._view("advanced", torch.int32, self.N)
+
+    def scores(self, parity: int, cand: Tensor, out: Optional[Tensor] = None) -> Tensor:
+        """delta fp32 [rows, beam] of the candidates cand int64 [rows, beam] against the rows' hypotheses (omr_ctc_prefix_scores)."""
+        require_cuda(cand, out)
+        assert cand.dtype == torch.int64 and cand.is_contiguous() and tuple(cand.shape) == (self.rows, self.beam), tuple(cand.shape)
+        if out is None:
+            out = torch.empty((self.rows, self.beam), dtype=torch.float32, device=cand.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.rows, self.beam)
+        lib().call("omr_ctc_prefix_scores", self.byref(), parity, ptr(cand), ptr(out), cur_stream())
+        return out
+
+    def advance(self, parity: int, parents: Tensor, tokens: Tensor, scores: Optional[Tensor] = None, done: Optional[Tensor] = None) -> None:
+        """New row i continues the LOCAL row parents[i] (int32 [rows]) of its input by tokens[i] (int64 [rows]): written into the other parity
+        (omr_ctc_prefix_advance).  scores fp64 [rows] / done int32 [N] (both optional): dead rows and finished inputs are skipped."""
+        require_cuda(parents, tokens, scores, done)
+        assert parents.dtype == torch.int32 and parents.is_contiguous() and parents.numel() == self.rows
+        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.numel() == self.rows
+        assert scores is None or (scores.dtype == torch.float64 and scores.is_contiguous() and scores.numel() == self.rows)
+        assert done is None or (done.dtype == torch.int32 and done.is_contiguous() and done.numel() == self.N)
+        lib().call("omr_ctc_prefix_advance", self.byref(), parity, ptr(parents), ptr(tokens), ptr(scores), ptr(done), cur_stream())

@@ -19,7 +19,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import lib
-from .evaluation import no_draft_option, refill_option
+from .evaluation import no_ctc_decode_option, no_draft_option, refill_option
 
 START, END, GAP = "¡", "!", "-"          # the reference's sentinel / gap symbols (smith_waterman.py:5,31-32)
 
@@ -107,6 +107,7 @@ def fuse(r: List[str], r_prob: List[float], q: List[str], q_prob: List[float], m
     return [t for t in fused if t not in (START, END)]          # undo_swalign_preprocess (smith_waterman.py:162-173)
 
 
+@no_ctc_decode_option
 @no_draft_option
 @refill_option
 def sw_predict(pairs: Iterable, img_model, audio_model, batch_size: int = 32, match: int = 2, mismatch: int = -1,
@@ -121,6 +122,7 @@ def sw_predict(pairs: Iterable, img_model, audio_model, batch_size: int = 32, ma
     return [fuse(ri, rpi, qi, qpi, match, mismatch, gap_penalty) for ri, rpi, qi, qpi in zip(r, r_prob, q, q_prob)]
 
 
+@no_ctc_decode_option
 @no_draft_option
 @refill_option
 def sw_evaluate(batches: Iterable, img_model, audio_model, batch_size: int = 32, match: int = 2, mismatch: int = -1,

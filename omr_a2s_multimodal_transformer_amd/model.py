@@ -21,8 +21,8 @@ from ._lib import lib
 from .config import DistillConfig, ModelConfig
 from .decoder import MAX_BEAM, Decoder, Linear, MultiheadAttention, _to_dev, takes_ragged_state
 from .encoder import HEIGHT_REDUCTION, WIDTH_REDUCTION, Encoder
-from .evaluation import (WINDOW_BATCHES, Alignment, active_grammar, active_spec, cells_and_boxes, decode_rows, decode_spec, decode_stream,
-                         grammar_option, grid_of, plan_align_groups, plan_groups, plan_pair_groups, refill_enabled, refill_option, spec_option,
+from .evaluation import (WINDOW_BATCHES, Alignment, active_ctc_decode, active_grammar, active_spec, cells_and_boxes, ctc_decode_option, decode_rows,
+                         decode_spec, decode_stream, grammar_option, grid_of, plan_align_groups, plan_groups, plan_pair_groups, refill_enabled, refill_option, spec_option,
                          stream_order)
 from .grammar import host_mask
 from .lightning_shim import LightningModule
@@ -402,10 +402,11 @@ class _Base(FlatModuleMixin, LightningModule):
             rows = max(1, batch_size // beam)
 
             def decode_single(mem):
-                return self.beam_search(mem, beam)[0], None
+                return self.beam_search(mem, beam)[0], None        # with ctc_decode= (evaluation.ctc_decode_option): the joint search
 
             def decode_group(group):
-                return [(seq, None) for seq, _ in self._beam_state(group, beam, 8)]
+                ctc = self._ctc_group(group) if active_ctc_decode() is not None else None
+                return [(seq, None) for seq, _ in self._beam_state(group, beam, 8, ctc=ctc)]
         else:
             rows = batch_size
 
@@ -520,6 +521,7 @@ class _Base(FlatModuleMixin, LightningModule):
         finally:
             self.train(was_training)
 
+    @ctc_decode_option(4, beam_at=1)
     @grammar_option
     @torch.no_grad()
     def beam_search(self, memory: torch.Tensor, beam: int = 4) -> Tuple[List[str], float]:
@@ -527,8 +529,16 @@ class _Base(FlatModuleMixin, LightningModule):
         `beam` hypotheses are the batch rows of the KV-cached step; scores are sums of log-probabilities (no length
         normalisation); beam = 1 reproduces `_greedy` token for token.  Returns (words incl. <eos> if reached, score).
         Keyword `grammar` (evaluation.grammar_option): the logits of the tokens the automaton forbids in a hypothesis' state are
-        -inf before the log-softmax, and a candidate the table forbids is dropped whatever its value."""
+        -inf before the log-softmax, and a candidate the table forbids is dropped whatever its value.
+        Keyword `ctc_decode` (evaluation.ctc_decode_option; Transformer with a CTC head, beam >= 2): the joint CTC / attention search.  Every
+        candidate's value becomes fl32(fl32(wa * log-probability) + fl32(wc * delta)), delta its CTC prefix score against the hypothesis it
+        extends (include/omr_hip.h, omr_ctc_prefix_scores; `memory` must be what `encode` returned: its grid travels with it); the candidate
+        list, the order, the walk and the stop rule stay.  This loop is the yardstick of the batched route."""
         assert memory.shape[0] == 1 and beam >= 1
+        ctc = None
+        if active_ctc_decode() is not None:
+            ctc = K.CtcPrefixBlock(*self._ctc_group([memory]), len(self.w2i), beam, blank=self.padding_idx, sos=self.w2i[SOS_TOKEN],
+                                   eos=self.w2i[EOS_TOKEN], weight=active_ctc_decode())
         grammar = active_grammar(self)
         gstates = [grammar.start] * beam if grammar is not None else None
         sos, eos = self.w2i[SOS_TOKEN], self.w2i[EOS_TOKEN]
@@ -540,12 +550,16 @@ class _Base(FlatModuleMixin, LightningModule):
         seqs: List[List[int]] = [[] for _ in range(beam)]
         best_done: Tuple[float, Optional[List[int]]] = (float("-inf"), None)
         exhausted = True                                     # the loop ran out of positions with hypotheses still alive
-        for _ in range(self.max_seq_len):
+        for pos in range(self.max_seq_len):
             logits = self.decoder.decode_step(tok, state)
             logits = logits if logits.dim() == 2 else logits.view(1, -1)
             if grammar is not None:
                 logits = logits.masked_fill(~host_mask(grammar, gstates, logits.device), float("-inf"))
             idx, val = K.topk_logprob(logits.contiguous(), beam)
+            if ctc is not None:                                       # the mix of omr_beam_select_ctc, in numpy float32: two products, one add
+                wa, wc = (np.float32(w) for w in K.ctc_mix_weights(ctc.weight))
+                with np.errstate(invalid="ignore"):
+                    val = torch.from_numpy(wa * val.cpu().numpy() + wc * ctc.scores(pos & 1, idx).cpu().numpy())
             idx_h, val_h = idx.cpu().tolist(), val.cpu().tolist()
             cands = [(scores[b] + val_h[b][j], b, idx_h[b][j]) for b in range(beam) if scores[b] > float("-inf") for j in range(beam)]
             if grammar is not None:
@@ -569,12 +583,17 @@ class _Base(FlatModuleMixin, LightningModule):
             state.reorder_rows(pidx)
             tok = torch.tensor(new_tok, dtype=torch.int64, device=dev).view(beam, 1)
             scores, seqs = new_scores, new_seqs
+            if ctc is not None:                                       # the survivors' prefix states, into the other parity
+                ctc.advance(pos & 1, pidx.to(torch.int32), tok.view(-1))
             if grammar is not None:
                 gstates = [grammar.walk([t], gstates[b])[0] for b, t in zip(parents, new_tok)]
         if exhausted and scores[0] > best_done[0]:
             best_done = (scores[0], seqs[0])                          # ran out of length: the best unfinished hypothesis wins
+        if ctc is not None and best_done[1] is None:
+            best_done = (scores[0], seqs[0])                          # a dead end: no label fits the frames left and <eos> was no candidate
         return [self._i2w(t) for t in best_done[1]], best_done[0]
 
+    @ctc_decode_option(4, beam_at=1)
     @grammar_option
     @torch.no_grad()
     def beam_search_batch(self, memories, beam: int = 4, sync_every: int = 8) -> List[Tuple[List[str], float]]:
@@ -583,11 +602,16 @@ class _Base(FlatModuleMixin, LightningModule):
         (tests/test_beam_batch_gpu.py).  memories: a list of [1, S_b, d] / [S_b, d] of different lengths.  The selection, the
         scores and the cache reorder stay on the device; the host reads the `done` flags every `sync_every` positions only
         and the whole state once at the end.  Memories of at most 64 or more than 16 384 tokens go through `beam_search`.
-        Keyword `grammar` (evaluation.grammar_option): the constrained selection (omr_beam_decode_steps_grammar)."""
+        Keyword `grammar` (evaluation.grammar_option): the constrained selection (omr_beam_decode_steps_grammar).
+        Keyword `ctc_decode` (evaluation.ctc_decode_option): the joint CTC / attention search of `beam_search`, on the device
+        (omr_beam_decode_steps_ctc); the memories must be what `encode` returned ([1, S_b, d] each)."""
         if not 1 <= beam <= MAX_BEAM:
             raise ValueError(f"beam must be in 1..{MAX_BEAM}, got {beam}")
         if sync_every < 1:
             raise ValueError(f"sync_every must be >= 1, got {sync_every}")
+        joint = active_ctc_decode() is not None
+        if joint:
+            memories = list(memories)                    # the CTC head reads each memory as `encode` returned it, grid attached
         mems = self.decoder.memory_list(memories, refuse_long=False)
         out: List[Optional[Tuple[List[str], float]]] = [None] * len(mems)
         batched = []
@@ -595,16 +619,35 @@ class _Base(FlatModuleMixin, LightningModule):
             if takes_ragged_state(m.shape[0]):
                 batched.append(i)
             else:                                        # alone, such a memory takes another attention kernel: search it alone
-                out[i] = self.beam_search(m.unsqueeze(0), beam)
+                out[i] = self.beam_search(memories[i] if joint else m.unsqueeze(0), beam)
         if batched:
-            for i, result in zip(batched, self._beam_state([mems[i] for i in batched], beam, sync_every)):
+            ctc = self._ctc_group([memories[i] for i in batched]) if joint else None
+            for i, result in zip(batched, self._beam_state([mems[i] for i in batched], beam, sync_every, ctc=ctc)):
                 out[i] = result
         return out
 
-    def _beam_state(self, mems, beam: int, sync_every: int) -> List[Tuple[List[str], float]]:
-        """The search of `beam_search_batch` over memories that all take a ragged state: one BeamDecodeState, run to the end."""
+    def _ctc_group(self, memories):
+        """For the joint CTC / attention search: the CTC head's logits of every memory of a group, each computed from that memory alone as
+        `encode` returned it (batch size 1, its own dense grid), copied into ONE zeroed buffer [N, Fmax, round_up(V, 8)] -> (its
+        [N, Fmax, V] view, frame counts int32 [N]): what BeamDecodeState.attach_ctc takes.  A group of one goes the same way, so the
+        per-input loop and the batched state read the same bits."""
+        parts = [self._ctc_logits_of(m) for m in memories]
+        V, fmax = len(self.w2i), max(lg.shape[1] for lg, _ in parts)
+        buf = torch.zeros((len(parts), fmax, K.round_up(V, 8)), dtype=parts[0][0].dtype, device=parts[0][0].device)
+        for n, (lg, _) in enumerate(parts):
+            buf[n, :lg.shape[1], :V] = lg[0]
+        return buf[:, :, :V], torch.cat([fl for _, fl in parts])
+
+    def _ctc_logits_of(self, memory: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        raise ValueError("ctc_decode= is for Transformer: this model has no CTC head")
+
+    def _beam_state(self, mems, beam: int, sync_every: int, ctc=None) -> List[Tuple[List[str], float]]:
+        """The search of `beam_search_batch` over memories that all take a ragged state: one BeamDecodeState, run to the end.
+        ctc: `_ctc_group` of these memories for the joint search (None: the attention scores alone)."""
         state = self.decoder.init_beam_decode(mems, beam, sos=self.w2i[SOS_TOKEN], eos=self.w2i[EOS_TOKEN])
         state.constrain(active_grammar(self))
+        if ctc is not None:
+            state.attach_ctc(*ctc, active_ctc_decode())
         left = self.max_seq_len
         while left > 0:
             n = min(sync_every, left)
@@ -664,7 +707,10 @@ class Transformer(_Base):
         x = x.to(flat.device, non_blocking=True)
         f = self.encoder.forward_nhwc(x, flat.compute_dtype).permute(0, 3, 1, 2)
         self._memory_grid = (None, (f.shape[2], f.shape[3]))       # every sample's grid is the whole plane
-        return self._boundary(_flatten_memory(self.pos_2d(f)))
+        mem = self._boundary(_flatten_memory(self.pos_2d(f)))
+        if self.ctc_weight > 0:
+            mem.ctc_grid = self._memory_grid[1]                    # travels with the memory: `predict` encodes many before it decodes one (`_ctc_logits_of`)
+        return mem
 
     def _encode_packed(self, x: torch.Tensor, sizes: torch.Tensor) -> Tuple[torch.Tensor, List[int], torch.Tensor]:
         """Ragged batch: x [B, C, Hmax, Wmax] with sample b's sizes[b] = (h_b, w_b) pixels in the top-left corner -> (memory
@@ -711,6 +757,17 @@ class Transformer(_Base):
         frames, frame_len = Fn.CTCFramesFn.apply(mem, grid_dev, gh, gw, self.ctc_pool, fmax)
         V = len(self.w2i)
         return Fn.linear(frames, self.ctc_head.weight, self.ctc_head.bias, out_ld=K.round_up(V, 8)), frame_len
+
+    def _ctc_logits_of(self, memory: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`_ctc_logits` of ONE memory [1, S, d] by the grid `encode` attached to it, whatever was encoded since."""
+        grid = getattr(memory, "ctc_grid", None)
+        if grid is None or memory.dim() != 3 or memory.shape[0] != 1:
+            raise ValueError("ctc_decode= takes memories as `encode` returned them ([1, S, d], one input each): a slice or a copy has lost its grid")
+        before, self._memory_grid = getattr(self, "_memory_grid", None), (None, grid)
+        try:
+            return self._ctc_logits(memory.contiguous())
+        finally:
+            self._memory_grid = before
 
     _is_pixel_sizes = staticmethod(_is_pixel_sizes)
 
@@ -854,6 +911,7 @@ class Transformer(_Base):
         assert x.size(0) == 1, "predict takes inputs of batch size 1 ([1, C, H, W]); their sizes may differ"
         return self.encode(x)
 
+    @ctc_decode_option(1)
     @spec_option
     @grammar_option
     @refill_option
@@ -880,6 +938,7 @@ class Transformer(_Base):
         Keyword `grammar` (evaluation.grammar_option): the values are the top-1 ALLOWED logits."""
         return self._predict(xs, self._encode_input, batch_size, want_probs=True)
 
+    @ctc_decode_option(1)
     @spec_option
     @grammar_option
     @refill_option
@@ -1111,6 +1170,7 @@ class MultimodalTransformer(_Base):
         x, _ = self.encoder_forward(xi=xi, xa=xa, xli=None, xla=None, apply_teacher_forcing_modality=False)
         return x
 
+    @ctc_decode_option(1)
     @spec_option
     @grammar_option
     @refill_option
@@ -1125,6 +1185,7 @@ class MultimodalTransformer(_Base):
         unimodal Transformer on the pair's image / audio (`draft_source`); same predictions."""
         return self._predict(pairs, self._encode_input, batch_size)
 
+    @ctc_decode_option(1)
     @spec_option
     @grammar_option
     @refill_option

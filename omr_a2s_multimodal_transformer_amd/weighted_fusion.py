@@ -34,7 +34,7 @@ import torch
 from . import kernels as K
 from ._lib import cur_stream, lib, ptr
 from .decoder import MAX_BEAM, WeightedBeamState, takes_ragged_state
-from .evaluation import (WINDOW_BATCHES, active_grammar, decode_rows, decode_stream, grammar_option, no_draft_option, plan_pair_groups, refill_enabled, refill_option,
+from .evaluation import (WINDOW_BATCHES, active_grammar, decode_rows, decode_stream, grammar_option, no_ctc_decode_option, no_draft_option, plan_pair_groups, refill_enabled, refill_option,
                          stream_order)
 from .grammar import host_mask
 from .metrics import compute_metrics
@@ -351,6 +351,7 @@ def _weighted_predict(pairs: Iterable, img_model, audio_model, alphas: List[floa
         del mems_i, mems_a
 
 
+@no_ctc_decode_option
 @no_draft_option
 @grammar_option
 @beam_option
@@ -371,6 +372,7 @@ def weighted_predict(pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], img_mod
     return dict(zip(alphas, preds)) if many else preds[0]
 
 
+@no_ctc_decode_option
 @no_draft_option
 @grammar_option
 @beam_option
