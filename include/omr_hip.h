@@ -65,7 +65,9 @@ int omr_weighted_argmax_rows(const float* logits_a, long lda, const float* logit
 /* audio front end (preprocessing.py:17-30): after the windowed DFT -- ONE omr_gemm of the centred,
  * hop-strided frames (lda = hop) against the Hann-weighted [cos | -sin] basis of the kept bins -- spec [frames][2*bins] holds
  * (re | im); this turns it into the reference's normalised log-spectrogram out [bins][frames] =
- * amplitude_to_db(|S|, ref=max, top_db=80) / 80 + 1.  spec is overwritten (magnitudes); max_ws: 4 bytes of device scratch. */
+ * amplitude_to_db(|S|, ref=max, top_db=80) / 80 + 1.  spec is overwritten (magnitudes); max_ws: 4 bytes of device scratch,
+ * cleared by the call.  As with numpy's maxima, one NaN magnitude makes every output NaN; the element that holds the maximum is
+ * exactly 1.0, also when the maximum is +inf (every finite element is 0.0 then). */
 int omr_log_stft_post(float* spec, long frames, int bins, unsigned* max_ws, float* out, void* stream);
 /* score-image front end (preprocessing.py:44-52: PIL convert("L") -> Image.resize (Pillow's default BICUBIC, antialiased,
  * 8-bit fixed point) -> ToTensor).  Bit-exact with Pillow.

@@ -23,6 +23,7 @@ from ._lib import cur_stream, lib, ptr
 
 N_FFT, HOP, SR, FMAX = 2048, 512, 22050, 2093.0
 NUM_FREQ_BINS = sum(1 for k in range(N_FFT // 2 + 1) if k * SR / N_FFT <= FMAX)      # 195 (preprocessing.py:13)
+MAX_PLAN_ENTRIES = 1 << 24                                                           # of a resampling plan's H (64 MiB in fp32); 22050 -> 16000 has 2.3e6
 
 
 @lru_cache(maxsize=4)
@@ -56,7 +57,9 @@ def _resample_plan(up: int, down: int, device: str):
     """Filter phases of scipy.signal.resample_poly(window=("kaiser", 5.0)) as a GEMM operand.  Output n = q*G + p (G = g*up
     outputs per row, g the smallest count that makes the row stride g*down a multiple of 4 samples = 16 bytes) is
     sum_i' x[q*g*down + i'] h[(p + r0)*down - i'*up]: the matrix H[p][i' - lo] does not depend on q.
-    -> (H [G, K] fp32 on the device, lo = first i' with a non-zero tap, g)."""
+    -> (H [G, K] fp32 on the device, lo = first i' with a non-zero tap, g).
+    H has about 20 g^2 up max(up, down) entries: near-coprime rates (22051 -> 22050) would need tens of GB, so a plan of more
+    than MAX_PLAN_ENTRIES is refused with ValueError before H is built."""
     import numpy as np
     max_rate = max(up, down)
     half_len = 10 * max_rate
@@ -76,12 +79,12 @@ def _resample_plan(up: int, down: int, device: str):
     hi = ((G - 1 + r0) * down) // up                                 # largest: index >= 0 at p = G - 1
     lo -= lo % 4                                                     # frame rows start 16-byte aligned
     K_ = (hi - lo + 1 + 7) // 8 * 8
+    if G * K_ > MAX_PLAN_ENTRIES:
+        raise ValueError(f"resample_poly: the plan for up = {up}, down = {down} has {G} x {K_} filter entries, more than {MAX_PLAN_ENTRIES}")
     H = np.zeros((G, K_))
-    for p in range(G):
-        for ip in range(lo, hi + 1):
-            j = (p + r0) * down - ip * up
-            if 0 <= j < len(h):
-                H[p, ip - lo] = h[j]
+    j = (np.arange(G)[:, None] + r0) * down - np.arange(lo, hi + 1)[None, :] * up     # tap of phase p at sample i' (outside h: none)
+    inside = (j >= 0) & (j < len(h))
+    H[:, :hi - lo + 1] = np.where(inside, h[np.clip(j, 0, len(h) - 1)], 0.0)
     return torch.from_numpy(H.astype(np.float32)).to(device), lo, g
 
 

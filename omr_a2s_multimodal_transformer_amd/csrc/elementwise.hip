@@ -266,29 +266,41 @@ __global__ void weighted_topk_logprob_kernel(const float* __restrict__ la0, long
 
 // ---------------------------------------------------------------- log-STFT post-processing (audio front end)
 // spec [frames][2*bins] = (re | im) halves of the windowed DFT (one fp32 GEMM against the Hann-weighted cos / -sin basis).
-// Pass 1: magnitude in place of `re` and the global maximum (non-negative floats order like their bit patterns).
+// Pass 1: magnitude in place of `re` and the global maximum, carried as its bit pattern: non-negative floats order like their
+// bits, and a NaN (either sign) sorts above +inf, so one non-finite magnitude reaches pass 2 instead of being dropped by fmaxf.
 __global__ void stft_mag_max_kernel(float* __restrict__ spec, long frames, int bins, unsigned* __restrict__ maxbits) {
     const long n = frames * bins;
-    float mx = 0.f;
+    unsigned mx = 0u;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const long f = i / bins; const int k = (int)(i % bins);
         const float re = spec[f * 2 * bins + k], im = spec[f * 2 * bins + bins + k];
         const float m = sqrtf(re * re + im * im);
         spec[f * 2 * bins + k] = m;
-        mx = fmaxf(mx, m);
+        const unsigned b = __float_as_uint(m);
+        mx = b > mx ? b : mx;
     }
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) atomicMax(maxbits, __float_as_uint(mx));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)mx, o, 64); mx = t > mx ? t : mx; }
+    if ((threadIdx.x & 63) == 0) atomicMax(maxbits, mx);
 }
 // Pass 2: out[bin][frame] = max(20 log10(max(amin, m)) - 20 log10(max(amin, max)), -top_db) / top_db + 1
-// (librosa.amplitude_to_db(ref=np.max) with its default top_db = 80, then the reference's /80 + 1; preprocessing.py:27-28)
+// (librosa.amplitude_to_db(ref=np.max) with its default top_db = 80, then the reference's /80 + 1; preprocessing.py:27-28).
+// The maxima are written as comparisons that keep a NaN, as numpy's do: a NaN magnitude makes the whole output NaN.  A
+// magnitude equal to the maximum after the amin clamp is 0 dB by definition: the contracted 20 * log - ref_db leaves the
+// product's rounding error there (up to 1 ulp of the output under 1.0), and a maximum of +inf would give inf - inf.
 __global__ void stft_db_kernel(const float* __restrict__ spec, long frames, int bins, const unsigned* __restrict__ maxbits, float* __restrict__ out) {
     const float amin = 1e-5f, top_db = 80.f;
-    const float ref_db = 20.f * log10f(fmaxf(amin, __uint_as_float(*maxbits)));
+    const float mx_raw = __uint_as_float(*maxbits);
+    const float mx = mx_raw < amin ? amin : mx_raw;
+    const float ref_db = 20.f * log10f(mx);
     const long n = frames * bins;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int k = (int)(i / frames); const long f = i % frames;       // output-major: coalesced stores
-        const float db = fmaxf(20.f * log10f(fmaxf(amin, spec[f * 2 * bins + k])) - ref_db, -top_db);
+        const float m_raw = spec[f * 2 * bins + k];
+        const float m = m_raw < amin ? amin : m_raw;
+        float db = 20.f * log10f(m) - ref_db;
+        if (m == mx) db = 0.f;
+        db = db < -top_db ? -top_db : db;
         out[i] = db / top_db + 1.f;
     }
 }
