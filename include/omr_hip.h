@@ -73,11 +73,18 @@ int omr_log_stft_post(float* spec, long frames, int bins, unsigned* max_ws, floa
  * 8-bit fixed point) -> ToTensor).  Bit-exact with Pillow.
  *   omr_resample_ksize / omr_resample_coeffs: HOST functions (no GPU work): taps per output pixel, and the tables
  *     bounds [out_size][2] = (first input index, count), coefs [out_size][ksize] (22 fractional bits); coeffs returns ksize.
- *   omr_image_gray_hpass: interleaved 8-bit pixels (channels 1 = L, 3 = RGB, 4 = RGBA; row_stride in bytes) -> luma ->
- *     horizontal pass -> dst [h][out_w] uint8.  bounds = coefs = NULL (out_w == w): conversion only.
- *   omr_image_vpass_to_float: vertical pass over src [h][w] uint8 -> value / 255 as out_dtype (OMR_F32 / OMR_BF16) into
- *     dst rows of dst_row_stride elements (a sample's slot inside the padded batch tensor, preprocessing.py:55-75).
- *     bounds = coefs = NULL (out_h == h): conversion only. */
+ *   omr_image_gray_hpass: interleaved 8-bit pixels (channels 1 = L, 3 = RGB, 4 = RGBA, alpha ignored) -> luma ->
+ *     horizontal pass -> dst [h][out_w] uint8, packed.  Strides of src: the bytes of a pixel are adjacent, pixels are
+ *     `channels` bytes apart, rows row_stride BYTES apart with row_stride >= w * channels (any alignment; the bytes between
+ *     rows are not read).  No other pixel or channel pitch is expressible: such views are packed by the caller.
+ *     bounds = coefs = NULL (out_w == w): conversion only (channels == 1: a row-packing copy).
+ *   omr_image_vpass_to_float: vertical pass over src [h][w] uint8, PACKED (rows w bytes apart) -> value / 255 as out_dtype
+ *     (OMR_F32 / OMR_BF16) into dst rows dst_row_stride ELEMENTS apart, dst_row_stride >= w, unit stride inside a row (a
+ *     sample's slot inside the padded batch tensor, preprocessing.py:55-75); only the out_h x w elements are written.
+ *     bounds = coefs = NULL (out_h == h): conversion only.
+ *   Both: a null src / dst, a size <= 0, channels outside {1, 3, 4}, one of bounds / coefs without the other, no tables with
+ *     another output size, tables with ksize <= 0, a stride below the row length: OMR_ERR_ARG; another out_dtype:
+ *     OMR_ERR_UNSUPPORTED; nothing is written then. */
 int omr_resample_ksize(int in_size, int out_size);
 int omr_resample_coeffs(int in_size, int out_size, int* bounds, int* coefs);
 int omr_image_gray_hpass(const unsigned char* src, int h, int w, int channels, long row_stride, const int* bounds, const int* coefs,

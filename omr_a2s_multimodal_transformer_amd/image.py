@@ -3,7 +3,9 @@
 ``ToTensor``, and ``pad_batch_inputs`` = right/bottom padding of a ragged list to the batch maximum.  The decoded pixels
 go to the GPU as bytes (one H2D of h*w*channels uint8 instead of H*W fp32), both resampling passes and the /255 run as HIP
 kernels (csrc/image.hip) and the result lands directly in its slot of the padded batch tensor, in the compute dtype.
-Bit-exact with Pillow on the uint8 image, hence equal floats (tests/test_image_gpu.py, oracle.ref_cpu.pil_*).
+Bit-exact with Pillow on the uint8 image, hence equal floats (tests/test_image_gpu.py, tests/test_image_branches_gpu.py,
+oracle.ref_cpu.pil_*).  Strides: ``preprocess_image_into`` takes any [h, w, c] view (see there for what reaches the kernel as it
+is and what is packed first); its output is a 2-D view with unit inner stride and any row stride >= W.
 There is no CPU path: tensors must be CUDA tensors."""
 from __future__ import annotations
 
@@ -66,15 +68,30 @@ def resized_width(h: int, w: int, img_height: Optional[int]) -> Tuple[int, int]:
     return img_height, int(img_height * w / h)
 
 
-def preprocess_image_into(pixels: Tensor, img_height: Optional[int], out: Tensor) -> Tuple[int, int]:
-    """pixels: CUDA uint8 [h, w, c]; out: CUDA fp32/bf16 2-D view [>=H, >=W] (unit inner stride) whose top-left H x W
-    receives the image.  Returns (H, W)."""
-    if not (pixels.is_cuda and out.is_cuda):
-        raise RuntimeError("omr_a2s_multimodal_transformer_amd.image runs on the GPU only (HIP kernels); there is no CPU fallback")
-    h, w, c = pixels.shape
+def _checked_size(h: int, w: int, img_height: Optional[int]) -> Tuple[int, int]:
+    """resized_width, refusing an empty result (a host check: callers make it before they touch the device)."""
     H, W = resized_width(h, w, img_height)
     if H <= 0 or W <= 0:
         raise ValueError(f"resized image would be {H}x{W}")
+    return H, W
+
+
+def preprocess_image_into(pixels: Tensor, img_height: Optional[int], out: Tensor) -> Tuple[int, int]:
+    """pixels: CUDA uint8 [h, w, c], any view: interleaved pixels (stride(2) == 1, stride(1) == c) whose rows are at least w * c
+    bytes apart go to the kernel as they are, with stride(0) as its row_stride (a height or width slice, rows padded to a
+    pitch); every other view (a channel slice such as rgba[:, :, :3], a permuted image, overlapping rows) is made contiguous on
+    the device first.  out: CUDA fp32/bf16 2-D view [>=H, >=W] (unit inner stride, any row stride >= W) whose top-left H x W
+    receives the image; nothing else of it is written.  Returns (H, W)."""
+    if not (pixels.is_cuda and out.is_cuda):
+        raise RuntimeError("omr_a2s_multimodal_transformer_amd.image runs on the GPU only (HIP kernels); there is no CPU fallback")
+    if pixels.dtype != torch.uint8 or pixels.dim() != 3 or pixels.shape[2] not in (1, 3, 4):
+        raise ValueError("expected uint8 pixels [h, w, c] with c in (1, 3, 4)")
+    h, w, c = pixels.shape
+    # the stride of a dimension of size 1 says nothing: torch leaves it arbitrary
+    if not ((c == 1 or pixels.stride(2) == 1) and (w == 1 or pixels.stride(1) == c) and (h == 1 or pixels.stride(0) >= w * c)):
+        pixels = pixels.contiguous()
+    row_stride = pixels.stride(0) if h > 1 else w * c
+    H, W = _checked_size(h, w, img_height)
     assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= H and out.shape[1] >= W
     dev = pixels.device
     dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
@@ -84,11 +101,11 @@ def preprocess_image_into(pixels: Tensor, img_height: Optional[int], out: Tensor
         bh, ch, ksh = _tables(w, W, dev_index)
     if H != h:
         bv, cv, ksv = _tables(h, H, dev_index)
-    if W != w or c != 1:
-        tmp = torch.empty((h, W), dtype=torch.uint8, device=dev)
-        lib().call("omr_image_gray_hpass", ptr(pixels), h, w, c, pixels.stride(0), ptr(bh), ptr(ch), ksh, W, ptr(tmp), cur_stream())
+    if W != w or c != 1 or row_stride != w:
+        tmp = torch.empty((h, W), dtype=torch.uint8, device=dev)     # c == 1 at a pitch, same width: the kernel's conversion-only path packs the rows
+        lib().call("omr_image_gray_hpass", ptr(pixels), h, w, c, row_stride, ptr(bh), ptr(ch), ksh, W, ptr(tmp), cur_stream())
     else:
-        tmp = pixels.view(h, w)
+        tmp = pixels                                                  # packed gray bytes already: the vertical pass reads them in place
     lib().call("omr_image_vpass_to_float", ptr(tmp), h, W, ptr(bv), ptr(cv), ksv, H, dtype_code(out.dtype), ptr(out), out.stride(0), cur_stream())
     return H, W
 
@@ -97,7 +114,7 @@ def preprocess_image(raw, img_height: Optional[int] = None, dtype: torch.dtype =
     """preprocessing.py:44-52 -> [1, H, W] on the GPU."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     px = as_hwc_uint8(raw)
-    H, W = resized_width(px.shape[0], px.shape[1], img_height)
+    H, W = _checked_size(px.shape[0], px.shape[1], img_height)
     out = torch.empty((1, H, W), dtype=dtype, device=device)
     preprocess_image_into(px.to(device, non_blocking=True), img_height, out[0])
     return out
@@ -144,7 +161,7 @@ def image_batch(raws: Sequence, img_height: Optional[int], pad_value: float = 1.
     resampled straight into its slot of the padded batch.  Returns (x [B, 1, Hmax, Wmax], widths int32 [B])."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     px = [as_hwc_uint8(r) for r in raws]
-    sizes = [resized_width(p.shape[0], p.shape[1], img_height) for p in px]
+    sizes = [_checked_size(p.shape[0], p.shape[1], img_height) for p in px]
     Hm, Wm = max(s[0] for s in sizes), max(s[1] for s in sizes)
     out = torch.full((len(px), 1, Hm, Wm), pad_value, dtype=dtype, device=device)
     for i, p in enumerate(px):
