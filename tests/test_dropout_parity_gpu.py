@@ -30,33 +30,9 @@ pytestmark = pytest.mark.gpu
 from omr_a2s_multimodal_transformer_amd import synthetic as syn  # noqa: E402
 from omr_a2s_multimodal_transformer_amd.config import ModelConfig  # noqa: E402
 from oracle import ref_cpu as R  # noqa: E402
+from bf16_grad_refs import load, materialise, oracle_grads  # noqa: E402  (shared with tests/test_bf16_grad_parity_gpu.py)
 
 DEV = "cuda:0"
-
-
-def materialise(trace, relu_trace):
-    """The HIP run's dropout masks (from (kind, p, seed, mode), through omr_dropout / omr_attn_dropout_mask) and ReLU masks
-    as CPU tensors in the oracle's layouts; dropout masks are built lazily because their shapes come from the oracle."""
-    from omr_a2s_multimodal_transformer_amd import kernels as K
-    cache = {}
-
-    def drop_mask(site, kind, p, shape, channel):
-        tkind, tp, seed, tch = trace[site]
-        assert tkind == kind and abs(tp - p) < 1e-12 and tch == channel, (site, trace[site], kind, p, channel)
-        if site not in cache:
-            if kind == "attn":
-                B, H, T, S = shape
-                m = K.attn_dropout_mask(B, H, T, S, p, seed, DEV).float() / (1.0 - p)
-            elif kind == "nhwc":
-                B, C, Hh, W = shape
-                m = K.dropout(torch.ones((B, Hh, W, C), device=DEV, dtype=torch.float32), p, seed, channel).permute(0, 3, 1, 2)
-            else:
-                m = K.dropout(torch.ones(shape, device=DEV, dtype=torch.float32), p, seed, False)
-            cache[site] = m.cpu().contiguous()
-        return cache[site]
-
-    relu_masks = [(m.permute(0, 3, 1, 2) if m.dim() == 4 else m).cpu().contiguous() for m in relu_trace]      # NHWC -> NCHW
-    return drop_mask, relu_masks
 
 
 class CheckingPlan(R.DropPlan):
@@ -79,20 +55,6 @@ class CheckingPlan(R.DropPlan):
         if diff.any():
             self.worst = max(self.worst, float(x.detach()[diff].abs().max()))
         return y
-
-
-def oracle_grads(fwd, sd32, dtype, drop_mask, relu_masks):
-    sd = {k: v.detach().to(dtype).requires_grad_(True) for k, v in sd32.items()}
-    plan = R.DropPlan(lambda *a: drop_mask(*a).to(dtype), relu_fn=lambda site, shape: relu_masks[site].to(dtype))
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(dtype)          # the oracle's sinusoid tables follow the default dtype
-    try:
-        logits, loss = fwd(sd, plan)
-        loss.backward()
-    finally:
-        torch.set_default_dtype(prev)
-    assert plan.relu_sites == len(relu_masks)
-    return {k: v.grad for k, v in sd.items()}
 
 
 def check_against_oracle(model, logits, loss, fwd, sd, trace, relu_trace, rseed):
@@ -123,13 +85,6 @@ def check_against_oracle(model, logits, loss, fwd, sd, trace, relu_trace, rseed)
         worst = max(worst, (err, n))
     assert worst[0] < 1e-3, worst
     return worst
-
-
-def load(module, shapes, seed):
-    sd = syn.seeded_state_dict(shapes, seed)
-    missing, unexpected = module.load_state_dict(sd, strict=False)
-    assert not unexpected and all(m.endswith("pe") or m.endswith("pe_hwc") for m in missing)
-    return sd
 
 
 @pytest.mark.parametrize("rseed", [2, 6, 9])      # together: MixDropout at position 1 / 2 / 3, nn.Dropout and nn.Dropout2d, in ConvBlocks and DSCBlocks
